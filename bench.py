@@ -59,7 +59,13 @@ def parse():
                          "(1280x720, 128 frames: 273 600 token rows), reported as its own workload, DiT step only")
     ap.add_argument("--gemm-variant", type=int, default=0, help="lab: vsys_tune_gemm_variant id (0 = shipped shape dispatch)")
     ap.add_argument("--flash-variant", type=int, default=0, help="lab: vsys_tune_flash_variant id (0 = shipped)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the model output of the CFG pair and the "
+                         "updated latent) as DIR/<name>.npy in float32; the inputs are seeded, so two builds compare output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(n: int) -> int:
@@ -100,7 +106,7 @@ def main():
     import __graft_entry__ as ge
 
     if rank == 0:
-        ge.build()
+        build_or_load(ge)
     if world > 1:
         import torch.distributed as dist
 
@@ -167,6 +173,7 @@ def main():
         nxt = timesteps[(i + 1) % STEPS_PER_VIDEO] if (i % STEPS_PER_VIDEO) < STEPS_PER_VIDEO - 1 else torch.zeros(1)
         dt = float(t[0] - nxt[0]) / 1000.0
         ops.cfg_euler_step(z, out, 7.0, dt)
+        return out
 
     def barrier():
         if world > 1:
@@ -180,9 +187,12 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        one_step(args.warmup + i)
+        last_out = one_step(args.warmup + i)
     barrier()
     dt_s = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # (before the instrumented replays below, which step the latent further)
+        dump_outputs(args.dump_outputs, {"model_out": last_out, "latent": z})
     if world > 1:
         import torch.distributed as dist
 
@@ -464,6 +474,33 @@ def main():
         dist.destroy_process_group()
 
 
+def build_or_load(ge):
+    """``build()`` (compile what changed, import the package, load the library) where this process may write the tree.  A tree
+    built beforehand and read-only to this process cannot be rebuilt here: the library that build() left in it is loaded as it
+    is, with build()'s own checks (a missing library or a missing torch.ops.vsys fragment still fails)."""
+    man = os.path.join(ge.CSRC, "build", "lab" if ge.LAB else "ship", "manifest.json")
+    paths = [p for p in (os.path.dirname(ge.LIB), os.path.dirname(man), man, ge.TORCH_LIB + ".key") if os.path.exists(p)]
+    if all(os.access(p, os.W_OK) for p in paths):
+        ge.build()
+        return
+    from videosys_amd import _lib
+
+    lib = _lib.load()
+    assert lib.vsys_abi_version() == 1
+    assert _lib.torch_ops() is not None or os.environ.get("VSYS_TORCH_OPS") == "0" or os.environ.get("VSYS_LIB"), "torch.ops.vsys did not load"
+    print(f"[bench] the tree is read-only here: loaded the library build() left ({ge.LIB})", file=sys.stderr, flush=True)
+
+
+def dump_outputs(d, arrays):
+    """What the last timed step handed its caller, as float32 .npy files: ``model_out`` = STDiT3 output of the CFG pair
+    [2, 8, T, H, W] (the sampler reads it), ``latent`` = z after the CFG / Euler update [1, 4, T, H, W]."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a.detach().float().cpu().numpy())
+
+
 def cpu_baseline(cfg, T, Hl, Wl, L, budget_s=80.0):
     """The reference's CPU PyTorch path on this box's host cores, as SURVEY.md §8(d) prescribes: the oracle (an fp32 port of the
     reference STDiT3, ``kind: "port"``) on the FULL config-2 token count, timed with ``valid_depth`` 1 and 2 (what the reference
@@ -488,20 +525,7 @@ def cpu_baseline(cfg, T, Hl, Wl, L, budget_s=80.0):
              model_max_length=300)
     sd = O.synth_state_dict(**c, seed=1)
     m = O.STDiT3Oracle(sd, 2, cfg.hidden_size, cfg.num_heads)
-    kind = "port"
-    try:   # where the reference tree exists (the build container; never the GPU box) its OWN STDiT3 class is what gets timed
-        from oracle import ref_loader
-
-        if ref_loader.reference_available():
-            ref_model = ref_loader.build_reference_stdit3(c, sd)
-
-            class _Ref:    # same call shape as the oracle: forward(x, t, y, valid_depth=, mask=, fps=, height=, width=)
-                def forward(self, x, t, y, **kw_):
-                    return ref_model(x, t, y, **kw_)
-
-            m, kind = _Ref(), "reference"
-    except Exception:
-        kind = "port"
+    kind = "port"   # the benchmark reads nothing outside the repository: always the in-tree oracle
     g = torch.Generator().manual_seed(0)
     y = torch.randn(2, 1, 300, cfg.caption_channels, generator=g) * 0.1
     mask = torch.zeros(1, 300, dtype=torch.long)
@@ -568,8 +592,7 @@ def cpu_baseline(cfg, T, Hl, Wl, L, budget_s=80.0):
         "host_fp32_gemm_tflops": round(gemm_tf, 3),
         "lower_bound_s_at_gemm_rate": round(89.4 / gemm_tf, 2),
         "sample_seconds": round(time.perf_counter() - t_start, 1),
-        "sample": (("the reference's own STDiT3 class (videosys/models/transformers/open_sora_transformer_3d.py through oracle/ref_loader.py, fp32, CPU)"
-                    if kind == "reference" else "CPU oracle (fp32 PyTorch port of the reference STDiT3)") +
+        "sample": ("CPU oracle (fp32 PyTorch port of the reference STDiT3)" +
                    f" on {Ts} of {T} latent frames x 1024 tokens, CFG batch 2, "
                    f"{L} text tokens: valid_depth 1 and 2, warm-up + {reps} repeats each (minimum taken), fitted fixed + 28 x pair"
                    + ("" if Ts == T else f", scaled x{scale:.2f} in tokens")),

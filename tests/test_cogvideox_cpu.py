@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import load_golden
+from ref_trace import ref_trace  # noqa: F401  (fixture; tests/golden/ref_traces/)
 from oracle import cogvideox_oracle as CO
 
 
@@ -79,21 +80,25 @@ def test_host_scheduler_and_tables_mirror_oracle():
     assert (p.spatial_threshold, p.spatial_range, p.spatial_broadcast) == ([100, 850], 2, True)
 
 
-def test_oracle_vs_live_reference():
-    from oracle import ref_loader
-
-    if not ref_loader.reference_available():
-        pytest.skip("reference tree not present (GPU box)")
+def test_oracle_vs_live_reference(ref_trace):
+    """The oracle against the reference's CogVideoXTransformer3DModel on inputs beside the golden's (its output replayed from
+    tests/golden/ref_traces/)."""
     fx = load_golden("cogvideox_fwd_small.pt")
     cfg = fx["rope"]["cfg"]
     o, sd = _oracle(fx, cfg)
-    model = ref_loader.build_reference_cogvideox(cfg, sd)
     g = torch.Generator().manual_seed(3)
     x, y = torch.randn(1, 2, 16, 8, 8, generator=g), torch.randn(1, 7, 128, generator=g)
     rope = CO.rope_3d(64, ((0, 0), (4, 4)), (4, 4), 2)
     t = torch.tensor([321])
-    with torch.no_grad():
-        ref = model(x, y, t, image_rotary_emb=rope, return_dict=False)[0]
+
+    def live():
+        from oracle import ref_loader
+
+        model = ref_loader.build_reference_cogvideox(cfg, sd)
+        with torch.no_grad():
+            return model(x, y, t, image_rotary_emb=rope, return_dict=False)[0]
+
+    ref = ref_trace.value(live)
     torch.testing.assert_close(o(x, y, t, rope), ref, rtol=2e-4, atol=2e-4)
 
 
@@ -114,7 +119,7 @@ def _drive(sched, steps, seed, shape):
     return ts, traj, x0s
 
 
-def test_dpm_scheduler_matches_the_reference_class():
+def test_dpm_scheduler_matches_the_reference_class(ref_trace):
     """videosys_amd.pipeline_cogvideox.CogVideoXDPMScheduler against the fixture minted from the reference's own class
     (schedulers/scheduling_dpm_cogvideox.py:119-483 driven as pipeline_cogvideox.py:679-721 drives it: x0 of the previous step and its
     timestep handed back in, one seeded CPU generator): timesteps, every step's latents and x0 prediction for the 2b / 5b settings and
@@ -141,12 +146,14 @@ def test_dpm_scheduler_matches_the_reference_class():
         if case["kwargs"]["rescale_betas_zero_snr"]:
             sa, sb, m1, m2, m3, m4, mn, second = sched.multipliers(ts[0], None)
             assert sa == 0.0 and sb == 1.0 and m1 == 0.0 and m3 is None and abs(m2 * m2 + mn * mn - 1.0) < 1e-12
-    from oracle import ref_loader
+    kw = dict(prediction_type="v_prediction", timestep_spacing="trailing", rescale_betas_zero_snr=True, snr_shift_scale=1.0)
 
-    if ref_loader.reference_available():
-        kw = dict(prediction_type="v_prediction", timestep_spacing="trailing", rescale_betas_zero_snr=True, snr_shift_scale=1.0)
-        ref = ref_loader.load_reference_cogvideox_dpm_scheduler(**kw)
-        a = _drive(ref, 7, 99, (1, 2, 16, 4, 4))
-        b = _drive(CogVideoXDPMScheduler(**kw), 7, 99, (1, 2, 16, 4, 4))
-        assert a[0] == b[0]
-        assert all((x - y).abs().max().item() <= 2e-5 for x, y in zip(a[1], b[1]))
+    def live():   # the reference class driven the same way (replayed from tests/golden/ref_traces/)
+        from oracle import ref_loader
+
+        return _drive(ref_loader.load_reference_cogvideox_dpm_scheduler(**kw), 7, 99, (1, 2, 16, 4, 4))
+
+    a = ref_trace.value(live)
+    b = _drive(CogVideoXDPMScheduler(**kw), 7, 99, (1, 2, 16, 4, 4))
+    assert a[0] == b[0]
+    assert all((x - y).abs().max().item() <= 2e-5 for x, y in zip(a[1], b[1]))

@@ -11,6 +11,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from conftest import GOLDEN, ROOT, load_golden
+from ref_trace import ref_trace  # noqa: F401  (fixture)
 from oracle import stdit3_oracle as O
 
 
@@ -221,8 +222,8 @@ def test_dsp_two_ranks_gloo(T, S):
 
 
 def _ref_comm_worker(rank, world, port, ret):
-    """Runs the REFERENCE's comm.py functions (imported from /root/reference through oracle/ref_loader.py) and this build's
-    videosys_amd.comm on the same tensors over the same gloo group.  gloo has no list all-to-all, so ``dist.all_to_all`` — the one
+    """Runs the REFERENCE's comm.py functions (replayed per rank from tests/golden/ref_traces/; live through oracle/ref_loader.py
+    while minting) and this build's videosys_amd.comm on the same tensors over the same gloo group.  gloo has no list all-to-all, so ``dist.all_to_all`` — the one
     collective the reference's ``_all_to_all_func`` issues — is served by all_to_all_single here; the reference's own
     tensor_split / contiguous / cat / pad / narrow logic runs unchanged."""
     try:
@@ -236,9 +237,21 @@ def _ref_comm_worker(rank, world, port, ret):
                 o.copy_(r)
 
         dist.all_to_all = list_all_to_all
-        from oracle import ref_loader
+        from ref_trace import Trace
 
-        R = ref_loader.load_reference_modules()["comm"]
+        tr = Trace(f"test_host_cpu__comm_gloo_rank{rank}")
+
+        class _R:   # the reference's comm.py, live only while minting the trace (tests/ref_trace.py)
+            def __getattr__(self, name):
+                def call(*a, **k):
+                    def live():
+                        from oracle import ref_loader
+
+                        return getattr(ref_loader.load_reference_modules()["comm"], name)(*a, **k)
+                    return tr.value(live)
+                return call
+
+        R = _R()
         from videosys_amd import comm as M
 
         g = torch.Generator().manual_seed(7)
@@ -267,6 +280,7 @@ def _ref_comm_worker(rank, world, port, ret):
             f = torch.randn(2 * 5, 3, 4, generator=g)
             R.set_pad("temporal", 5, grp), M.set_pad("temporal", 5, grp)
             assert torch.equal(R.split_from_second_dim(f, 2, grp), M.split_from_second_dim(f, 2, grp))
+        tr.close()
         ret.put((rank, "ok"))
     except Exception:  # noqa
         import traceback
@@ -280,8 +294,6 @@ def _ref_comm_worker(rank, world, port, ret):
 def test_comm_operators_equal_the_reference_functions_over_gloo():
     """SURVEY §8a row a13 at the function level: split_sequence / all_to_all_with_pad / all_to_all_comm / split_from_second_dim /
     set_pad of videosys_amd.comm against the reference's comm.py itself, two real processes, bit-equal."""
-    if not os.path.isdir("/root/reference/videosys"):
-        pytest.skip("reference tree not present on this box")
     ctx = mp.get_context("spawn")
     ret = ctx.Queue()
     port = _free_port()
@@ -439,80 +451,81 @@ def test_ulysses_two_ranks_gloo(Lt, Lv):
         assert status == "ok", f"rank {rank}: {status}"
 
 
-def test_timestep_transform_bitwise_equals_reference_function():
-    """videosys_amd.rflow.timestep_transform against the reference function itself (scheduling_rflow_open_sora.py:47-70, imported
-    from /root/reference when present) on 5250 (geometry, step) pairs: the fp32 results must be bit-identical."""
+def _ref_rflow_module(name):
+    """The reference's scheduling_rflow_open_sora.py, live (only while minting a trace)."""
     import importlib.util
-    import itertools
-    import os
 
-    ref_path = "/root/reference/videosys/schedulers/scheduling_rflow_open_sora.py"
-    if not os.path.exists(ref_path):
-        pytest.skip("reference tree not present on this box")
-    spec = importlib.util.spec_from_file_location("ref_rflow", ref_path)
+    from oracle import ref_loader
+
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ref_loader.REFERENCE_ROOT, "videosys/schedulers/scheduling_rflow_open_sora.py"))
     ref = importlib.util.module_from_spec(spec)
-    try:
-        spec.loader.exec_module(ref)
-    except Exception as e:  # the module imports tqdm / its own utils; skip if that environment is missing
-        pytest.skip(f"reference scheduler not importable here: {e}")
+    spec.loader.exec_module(ref)
+    return ref
+
+
+def test_timestep_transform_bitwise_equals_reference_function(ref_trace):
+    """videosys_amd.rflow.timestep_transform against the reference function itself (scheduling_rflow_open_sora.py:47-70; its
+    results replayed from tests/golden/ref_traces/) on 5250 (geometry, step) pairs: the fp32 results must be bit-identical."""
+    import itertools
+
     from videosys_amd.rflow import timestep_transform
 
-    for H, W, F in itertools.product([256., 360., 480., 512., 720.], [256., 480., 512., 640., 1280.], [1., 17., 34., 51., 64., 102., 128.]):
-        kw = dict(height=torch.tensor([H]), width=torch.tensor([W]), num_frames=torch.tensor([F]))
-        for k in range(30):
-            t = torch.tensor([(1 - k / 30) * 1000.0])
-            assert torch.equal(timestep_transform(t, kw, num_timesteps=1000), ref.timestep_transform(t, kw, num_timesteps=1000))
+    cases = [dict(height=torch.tensor([H]), width=torch.tensor([W]), num_frames=torch.tensor([F]))
+             for H, W, F in itertools.product([256., 360., 480., 512., 720.], [256., 480., 512., 640., 1280.], [1., 17., 34., 51., 64., 102., 128.])]
+    steps = [torch.tensor([(1 - k / 30) * 1000.0]) for k in range(30)]
+
+    def live():
+        ref = _ref_rflow_module("ref_rflow")
+        return torch.stack([ref.timestep_transform(t, kw, num_timesteps=1000) for kw in cases for t in steps])
+
+    want = ref_trace.value(live)
+    got = torch.stack([timestep_transform(t, kw, num_timesteps=1000) for kw in cases for t in steps])
+    assert want.shape == got.shape and want.dtype == got.dtype and torch.equal(got, want)
 
 
-def test_timestep_transform_bf16_geometry_equals_reference_function():
+def test_timestep_transform_bf16_geometry_equals_reference_function(ref_trace):
     """The reference hands height / width / num_frames to timestep_transform as tensors of the MODEL dtype
     (data_process.py:798-805: bf16, so 854 arrives as 856 and the ratio is computed in bf16 before the fp32 timestep promotes
-    it).  The pipeline builds them the same way (open_sora_geometry.prepare_multi_resolution_info): bitwise equal schedules."""
-    import importlib.util
+    it).  The pipeline builds them the same way (open_sora_geometry.prepare_multi_resolution_info): bitwise equal schedules
+    (the reference function's results replayed from tests/golden/ref_traces/)."""
     import itertools
 
-    ref_path = "/root/reference/videosys/schedulers/scheduling_rflow_open_sora.py"
-    if not os.path.exists(ref_path):
-        pytest.skip("reference tree not present on this box")
-    spec = importlib.util.spec_from_file_location("ref_rflow_bf16", ref_path)
-    ref = importlib.util.module_from_spec(spec)
-    try:
-        spec.loader.exec_module(ref)
-    except Exception as e:
-        pytest.skip(f"reference scheduler not importable here: {e}")
     from videosys_amd import open_sora_geometry as G
     from videosys_amd.rflow import RFLOW, timestep_transform
 
+    steps = [torch.tensor([(1 - k / 30) * 1000.0]) for k in range(30)]
     for (H, W), F in itertools.product([(480, 854), (720, 1280), (512, 512), (240, 426), (1080, 1920)], [1, 51, 64, 102, 408]):
         kw = G.prepare_multi_resolution_info(1, (H, W), F, 24, dtype=torch.bfloat16)
         assert kw["width"].dtype == torch.bfloat16 and float(kw["width"][0]) == float(torch.tensor(float(W)).to(torch.bfloat16))
-        for k in range(30):
-            t = torch.tensor([(1 - k / 30) * 1000.0])
-            assert torch.equal(timestep_transform(t, kw, num_timesteps=1000), ref.timestep_transform(t, kw, num_timesteps=1000))
+        want = ref_trace.value(lambda: torch.stack([_ref_rflow_module("ref_rflow_bf16").timestep_transform(t, kw, num_timesteps=1000) for t in steps]))
+        for t, w in zip(steps, want.unbind(0)):
+            assert torch.equal(timestep_transform(t, kw, num_timesteps=1000), w)
         # and through the sampler's own schedule builder
         ts = RFLOW(num_sampling_steps=30, use_timestep_transform=True).prepare_timesteps(1, kw)
-        want = [ref.timestep_transform(torch.tensor([(1 - k / 30) * 1000.0]), kw, num_timesteps=1000) for k in range(30)]
-        assert all(torch.equal(a, b) for a, b in zip(ts, want))
+        assert len(ts) == len(want) and all(torch.equal(a, b) for a, b in zip(ts, want.unbind(0)))
 
 
-def test_open_sora_geometry_vocabulary_matches_reference_tables():
+def test_open_sora_geometry_vocabulary_matches_reference_tables(ref_trace):
     """Every (resolution, aspect_ratio) pair of generate()'s vocabulary returns exactly the reference's size — or fails the same
     assert — and the duration names map to the same frame counts (golden minted from data_process.py by
-    oracle/make_golden_geometry.py; re-derived live from the reference file when it is present)."""
+    oracle/make_golden_geometry.py; the tables re-derived from the reference file replayed from tests/golden/ref_traces/)."""
     from videosys_amd import open_sora_geometry as G
 
     with open(os.path.join(GOLDEN, "opensora_image_sizes.json")) as f:
         gold = json.load(f)
     assert len(gold["image_sizes"]) == 13 * 17
-    tables = [gold]
-    if os.path.exists("/root/reference/videosys/pipelines/open_sora/data_process.py"):
+
+    def live_tables():
         from oracle.make_golden_geometry import reference_tables
 
         lit, res_tab = reference_tables()
         live = {f"{res}|{ar}": (list(lit[tab][key]) if key in lit[tab] else None)
                 for res, tab in res_tab.items() for ar, key in lit["ASPECT_RATIO_MAP"].items()}
-        assert live == gold["image_sizes"], "golden out of date with the reference file"
-        tables.append(dict(image_sizes=live, ratio_keys=lit["ASPECT_RATIO_MAP"], num_frames=lit["NUM_FRAMES_MAP"]))
+        return dict(image_sizes=live, ratio_keys=dict(lit["ASPECT_RATIO_MAP"]), num_frames=dict(lit["NUM_FRAMES_MAP"]))
+
+    live = ref_trace.value(live_tables)
+    assert live["image_sizes"] == gold["image_sizes"], "golden out of date with the reference file"
+    tables = [gold, live]
     for tab in tables:
         for pair, want in tab["image_sizes"].items():
             res, ar = pair.split("|")
@@ -591,16 +604,36 @@ def test_videosys_alias_package_exports_reference_names():
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stderr[-800:]
 
 
-def test_reference_module_paths_resolve_to_this_build():
+def _reference_videosys_imports():
+    """Every ``from videosys... import`` of the reference's examples / eval scripts / tests as [file, module, [names]], live only
+    while minting a trace."""
+    import ast
+    import glob
+
+    from oracle import ref_loader
+
+    ref, out = ref_loader.REFERENCE_ROOT, []
+    for pat in ("examples/**/*.py", "eval/**/*.py", "tests/**/*.py"):
+        for f in sorted(glob.glob(os.path.join(ref, pat), recursive=True)):
+            with open(f) as fh:
+                tree = ast.parse(fh.read())
+            for n in ast.walk(tree):
+                if isinstance(n, ast.ImportFrom) and n.module and n.module.split(".")[0] == "videosys":
+                    out.append([os.path.relpath(f, ref), n.module, [a.name for a in n.names]])
+    return out
+
+
+def test_reference_module_paths_resolve_to_this_build(ref_trace):
     """The submodule imports of the reference's inference examples, eval scripts and tests (``from videosys.core.pab.pab_mgr import
-    ...``) resolve through the alias table of videosys/__init__.py; with the reference tree present, every ``from videosys... import``
-    of its examples / eval / tests is checked, except the families and the training stack outside the hot path.  Subprocess: see the
-    test above."""
+    ...``) resolve through the alias table of videosys/__init__.py; every ``from videosys... import`` of its examples / eval / tests
+    (the list replayed from tests/golden/ref_traces/) is checked, except the families and the training stack outside the hot path.
+    Subprocess: see the test above."""
     import subprocess
     import sys
 
+    imports = ref_trace.value(_reference_videosys_imports)
     code = r"""
-import ast, glob, importlib, os
+import importlib, json, os
 import videosys, videosys_amd
 from videosys.core.pab.pab_mgr import PABConfig, set_pab_manager, update_steps, enable_pab, if_broadcast_spatial, get_mlp_output
 from videosys.utils.utils import save_video, set_seed, batch_func, str_to_dtype, all_exists
@@ -629,40 +662,27 @@ assert videosys_amd.pab.PAB_MANAGER is not None and alias.PAB_MANAGER is videosy
 set_pab_manager(None)
 o = VideoSysPipelineOutput(video=7)
 assert o["video"] == 7 and o[0] == 7 and o.to_tuple() == (7,)
-ref = "/root/reference"
 skip = ("videosys.training", "videosys.core.dcp", "videosys.utils.training", "videosys.models.open_sora")
 skip_names = {"OpenSoraPlanConfig", "OpenSoraPlanV110PABConfig", "OpenSoraPlanV120PABConfig", "VchitectConfig", "VchitectPABConfig",
               "DynamicParallelManager", "set_distributed_state", "merge_args"}
 bad, seen = [], 0
-if os.path.isdir(ref):
-    for pat in ("examples/**/*.py", "eval/**/*.py", "tests/**/*.py"):
-        for f in glob.glob(os.path.join(ref, pat), recursive=True):
-            for n in ast.walk(ast.parse(open(f).read())):
-                if isinstance(n, ast.ImportFrom) and n.module and n.module.split(".")[0] == "videosys" and not n.module.startswith(skip):
-                    m = importlib.import_module(n.module)
-                    for a in n.names:
-                        seen += 1
-                        if a.name not in skip_names and not hasattr(m, a.name):
-                            bad.append((os.path.relpath(f, ref), n.module, a.name))
-    assert seen > 50 and not bad, bad
+for f, module, names in json.loads(os.environ["VSYS_REF_IMPORTS"]):
+    if not module.startswith(skip):
+        m = importlib.import_module(module)
+        for name in names:
+            seen += 1
+            if name not in skip_names and not hasattr(m, name):
+                bad.append((f, module, name))
+assert seen > 50 and not bad, bad
 print("ok")
 """
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=180)
+    env = dict(os.environ, VSYS_REF_IMPORTS=json.dumps(imports))
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=180)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stderr[-1500:]
 
 
-def test_reference_example_scripts_run_against_this_build():
-    """The reference's own examples/inference/{open_sora,latte,cogvideox}/sample.py and its pipeline tests, executed unchanged with
-    this repo in front on sys.path: every config they build is accepted and every ``engine.generate(...)`` call binds to the
-    pipeline's ``generate`` signature.  The engine is replaced by a recorder (no GPU here); the same call shapes run on the device in
-    tests/test_gpu_pipeline.py.  Subprocess: see the alias test above."""
-    import subprocess
-    import sys
-
-    if not os.path.isdir("/root/reference/examples/inference"):
-        pytest.skip("reference tree not present on this box")
-    code = r"""
-import inspect, os, runpy, sys, types
+_EXAMPLE_ENGINE = r"""
+import inspect, json, os, sys, types
 import videosys
 
 calls = []
@@ -678,13 +698,60 @@ class Engine:
         return types.SimpleNamespace(video=["frames"])
     def save_video(self, video, path):
         assert video == "frames" and path.endswith(".mp4")
+"""
 
-videosys.VideoSysEngine = Engine
+
+def _reference_example_calls():
+    """Runs the reference's examples/inference/{open_sora,latte,cogvideox}/sample.py and tests/pipelines/<family>/test_<family>.py
+    unchanged against this build with a recording engine (live only while minting a trace) and returns what they did as data:
+    per engine, the config it was given (class name + arguments) and its generate / save_video calls in order."""
+    import subprocess
+    import sys
+
+    from oracle import ref_loader
+
+    code = _EXAMPLE_ENGINE + r"""
+import runpy
+
+keep, made, engines = [], {}, []
+
+def enc(v):
+    if id(v) in made:
+        return {"__config__": made[id(v)]}
+    json.dumps(v)                             # plain data only
+    return v
+
+def recording(name, cls):
+    def make(*a, **k):
+        obj = cls(*a, **k)
+        keep.append(obj)
+        made[id(obj)] = [name, [enc(x) for x in a], {kk: enc(x) for kk, x in k.items()}]
+        return obj
+    return make
+
+for n in dir(videosys):
+    if n.endswith("Config"):
+        setattr(videosys, n, recording(n, getattr(videosys, n)))
+
+class RecordingEngine(Engine):
+    def __init__(self, config):
+        super().__init__(config)
+        self.rec = {"config": made[id(config)], "calls": []}
+        engines.append(self.rec)
+    def generate(self, *a, **k):
+        self.rec["calls"].append(["generate", [enc(x) for x in a], {kk: enc(x) for kk, x in k.items()}])
+        return super().generate(*a, **k)
+    def save_video(self, video, path):
+        self.rec["calls"].append(["save_video", path])
+        return super().save_video(video, path)
+
+videosys.VideoSysEngine = RecordingEngine
 import torch
 torch.cuda.empty_cache = lambda: None
 ran = 0
+ref = sys.argv[1]
 for fam in ("open_sora", "latte", "cogvideox"):
-    for path in (f"/root/reference/examples/inference/{fam}/sample.py", f"/root/reference/tests/pipelines/{fam}/test_{fam}.py"):
+    for path in (f"{ref}/examples/inference/{fam}/sample.py", f"{ref}/tests/pipelines/{fam}/test_{fam}.py"):
         ns = runpy.run_path(path, run_name="not_main")
         for name, fn in ns.items():
             if callable(fn) and getattr(fn, "__module__", None) is None or name.startswith(("run_", "test_")):
@@ -696,11 +763,49 @@ for fam in ("open_sora", "latte", "cogvideox"):
                 for combo in itertools.product(*[m.args[1] for m in marks]):
                     fn(**dict(zip(names, combo)))
                     ran += 1
+print(json.dumps({"ran": ran, "engines": engines}))
+"""
+    r = subprocess.run([sys.executable, "-c", code, ref_loader.REFERENCE_ROOT], cwd=ROOT, capture_output=True, text=True, timeout=180)
+    assert r.returncode == 0, r.stderr[-1500:]
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def test_reference_example_scripts_run_against_this_build(ref_trace):
+    """The reference's own examples/inference/{open_sora,latte,cogvideox}/sample.py and its pipeline tests, as they drive the
+    engine (every config they build, every ``engine.generate(...)`` / ``save_video`` call, replayed from tests/golden/ref_traces/;
+    _reference_example_calls mints it by running the scripts unchanged against this build): every config is accepted and every
+    generate call binds to the pipeline's ``generate`` signature.  The engine is replaced by a recorder (no GPU here); the same call
+    shapes run on the device in tests/test_gpu_pipeline.py.  Subprocess: see the alias test above."""
+    import subprocess
+    import sys
+
+    recorded = ref_trace.value(_reference_example_calls)
+    code = _EXAMPLE_ENGINE + r"""
+data = json.loads(os.environ["VSYS_REF_EXAMPLES"])
+
+def dec(v):
+    return build(v["__config__"]) if isinstance(v, dict) and "__config__" in v else v
+
+def build(rec):
+    name, a, k = rec
+    return getattr(videosys, name)(*[dec(x) for x in a], **{kk: dec(x) for kk, x in k.items()})
+
+import torch
+torch.cuda.empty_cache = lambda: None
+for e in data["engines"]:
+    engine = Engine(build(e["config"]))
+    for c in e["calls"]:
+        if c[0] == "generate":
+            engine.generate(*[dec(x) for x in c[1]], **{k: dec(x) for k, x in c[2].items()})
+        else:
+            engine.save_video("frames", c[1])
+ran = data["ran"]
 assert ran >= 18 and len(calls) >= ran, (ran, len(calls))
 assert {c[0] for c in calls} == {"OpenSoraPipeline", "LattePipeline", "CogVideoXPipeline"}
 print("ok", ran, len(calls))
 """
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=180)
+    env = dict(os.environ, VSYS_REF_EXAMPLES=json.dumps(recorded))
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=180)
     assert r.returncode == 0 and "ok" in r.stdout, (r.stdout[-400:], r.stderr[-1500:])
 
 
@@ -978,38 +1083,44 @@ def test_every_entry_point_of_the_header_cites_what_it_replaces():
     assert not missing, missing
 
 
-def test_generate_accepts_every_keyword_of_the_reference():
+def _ref_class_ast(rel, cls):
+    """The ClassDef node of ``cls`` in the reference file ``rel`` (videosys/...), live only while minting a trace."""
+    import ast
+
+    from oracle import ref_loader
+
+    with open(os.path.join(ref_loader.REFERENCE_ROOT, "videosys", rel)) as fh:
+        return next(n for n in ast.parse(fh.read()).body if isinstance(n, ast.ClassDef) and n.name == cls)
+
+
+def test_generate_accepts_every_keyword_of_the_reference(ref_trace):
     """Every keyword of the reference's ``generate`` (Open-Sora, Latte, CogVideoX pipelines) exists on this build's ``generate``
     (values the path cannot honour are refused with an error that says so, not with a TypeError about the keyword)."""
     import ast
     import inspect
 
-    ref_root = "/root/reference/videosys/pipelines"
-    if not os.path.isdir(ref_root):
-        pytest.skip("reference tree not present on this box")
     from videosys_amd.pipeline_cogvideox import CogVideoXPipeline
     from videosys_amd.pipeline_latte import LattePipeline
     from videosys_amd.pipeline_open_sora import OpenSoraPipeline
 
-    for path, cls, ours in (("open_sora/pipeline_open_sora.py", "OpenSoraPipeline", OpenSoraPipeline),
-                            ("latte/pipeline_latte.py", "LattePipeline", LattePipeline),
-                            ("cogvideox/pipeline_cogvideox.py", "CogVideoXPipeline", CogVideoXPipeline)):
-        src = open(os.path.join(ref_root, path)).read()
-        fn = next(it for n in ast.parse(src).body if isinstance(n, ast.ClassDef) and n.name == cls
-                  for it in n.body if isinstance(it, ast.FunctionDef) and it.name == "generate")
-        want = [a.arg for a in fn.args.args + fn.args.kwonlyargs if a.arg != "self"]
+    def keywords(path, cls):   # the reference's generate() parameter names (replayed from tests/golden/ref_traces/)
+        fn = next(it for it in _ref_class_ast(path, cls).body if isinstance(it, ast.FunctionDef) and it.name == "generate")
+        return [a.arg for a in fn.args.args + fn.args.kwonlyargs if a.arg != "self"]
+
+    for path, cls, ours in (("pipelines/open_sora/pipeline_open_sora.py", "OpenSoraPipeline", OpenSoraPipeline),
+                            ("pipelines/latte/pipeline_latte.py", "LattePipeline", LattePipeline),
+                            ("pipelines/cogvideox/pipeline_cogvideox.py", "CogVideoXPipeline", CogVideoXPipeline)):
+        want = ref_trace.value(lambda: keywords(path, cls))
+        assert len(want) > 3, (cls, want)
         have = set(inspect.signature(ours.generate).parameters)
         assert not [a for a in want if a not in have], (cls, [a for a in want if a not in have])
 
 
-def test_pipelines_and_engine_have_every_method_of_the_reference_classes():
+def test_pipelines_and_engine_have_every_method_of_the_reference_classes(ref_trace):
     """Every method / property name of the reference's pipeline classes and of its engine exists on this build's classes (a call
     site written against the reference finds what it calls)."""
     import ast
 
-    ref_root = "/root/reference/videosys"
-    if not os.path.isdir(ref_root):
-        pytest.skip("reference tree not present on this box")
     from videosys_amd.engine import VideoSysEngine
     from videosys_amd.pipeline_cogvideox import CogVideoXPipeline
     from videosys_amd.pipeline_latte import LattePipeline
@@ -1020,8 +1131,8 @@ def test_pipelines_and_engine_have_every_method_of_the_reference_classes():
                             ("pipelines/latte/pipeline_latte.py", "LattePipeline", LattePipeline),
                             ("pipelines/cogvideox/pipeline_cogvideox.py", "CogVideoXPipeline", CogVideoXPipeline),
                             ("core/engine/engine.py", "VideoSysEngine", VideoSysEngine)):
-        node = next(n for n in ast.parse(open(os.path.join(ref_root, path)).read()).body if isinstance(n, ast.ClassDef) and n.name == cls)
-        names = [it.name for it in node.body if isinstance(it, ast.FunctionDef)]
+        names = ref_trace.value(lambda: [it.name for it in _ref_class_ast(path, cls).body if isinstance(it, ast.FunctionDef)])
+        assert len(names) > 3, (cls, names)
         missing = [n for n in names if not hasattr(ours, n) and n not in internal]
         assert not missing, (cls, missing)
 
@@ -1208,7 +1319,7 @@ def test_local_checkpoint_directories_are_read_like_from_pretrained(tmp_path, mo
     assert seen["latte"] == (3, 64, []) and seen["latte_sd"] == ["w"] and lp.vae_decoder == ("svd", ["d"])
 
 
-def test_pipeline_constructors_take_the_reference_components(tmp_path, monkeypatch):
+def test_pipeline_constructors_take_the_reference_components(tmp_path, monkeypatch, ref_trace):
     """The constructors keep the reference's parameter names and order (pipeline_open_sora.py:194-204, pipeline_latte.py:192-202,
     pipeline_cogvideox.py:124-134); ready-made components are adopted: a torch module holding reference weights is read through
     state_dict() / config, this build's own objects and schedulers are used as they are, a local ``text_encoder/`` + ``tokenizer``
@@ -1223,16 +1334,16 @@ def test_pipeline_constructors_take_the_reference_components(tmp_path, monkeypat
     from videosys_amd import pipeline_cogvideox as PC, pipeline_latte as PL, pipeline_open_sora as PO
     import videosys_amd.t5 as T5
 
-    ref_root = "/root/reference/videosys/pipelines"
-    if os.path.isdir(ref_root):
-        for path, cls, ours in (("open_sora/pipeline_open_sora.py", "OpenSoraPipeline", PO.OpenSoraPipeline),
-                                ("latte/pipeline_latte.py", "LattePipeline", PL.LattePipeline),
-                                ("cogvideox/pipeline_cogvideox.py", "CogVideoXPipeline", PC.CogVideoXPipeline)):
-            node = next(n for n in ast.parse(open(os.path.join(ref_root, path)).read()).body if isinstance(n, ast.ClassDef) and n.name == cls)
-            init = next(it for it in node.body if isinstance(it, ast.FunctionDef) and it.name == "__init__")
-            want = [a.arg for a in init.args.args]
-            have = [k for k, v in inspect.signature(ours.__init__).parameters.items() if v.kind == v.POSITIONAL_OR_KEYWORD]
-            assert have == want, (cls, have, want)
+    def init_params(path, cls):   # the reference constructor's parameter names (replayed from tests/golden/ref_traces/)
+        init = next(it for it in _ref_class_ast(path, cls).body if isinstance(it, ast.FunctionDef) and it.name == "__init__")
+        return [a.arg for a in init.args.args]
+
+    for path, cls, ours in (("pipelines/open_sora/pipeline_open_sora.py", "OpenSoraPipeline", PO.OpenSoraPipeline),
+                            ("pipelines/latte/pipeline_latte.py", "LattePipeline", PL.LattePipeline),
+                            ("pipelines/cogvideox/pipeline_cogvideox.py", "CogVideoXPipeline", PC.CogVideoXPipeline)):
+        want = ref_trace.value(lambda: init_params(path, cls))
+        have = [k for k, v in inspect.signature(ours.__init__).parameters.items() if v.kind == v.POSITIONAL_OR_KEYWORD]
+        assert have == want, (cls, have, want)
 
     seen = {}
 
@@ -1363,14 +1474,12 @@ def test_progress_wrap_is_a_bar_on_request_only():
     assert type(bar).__name__.startswith("tqdm") and list(bar) == items
 
 
-def test_caption_cleaner_equals_the_reference_on_generated_text():
+def test_caption_cleaner_equals_the_reference_on_generated_text(ref_trace):
     """Property test (hypothesis): caption.clean_caption / text_preprocessing against the reference's own functions compiled from
     its files (oracle/make_golden_caption.reference_cleaners), Open-Sora and Latte variants, on text assembled from the token
     classes the rules target (urls, html, entities, ids, sizes, CJK, dashes, quotes, shipping spam ...).  The two third-party steps
     are the same stand-ins on both sides (NFC for ftfy.fix_text, the standard library's html.parser for BeautifulSoup(...).text),
-    so what is compared is the rule sequence."""
-    if not os.path.isdir("/root/reference/videosys/pipelines"):
-        pytest.skip("reference tree not present on this box")
+    so what is compared is the rule sequence.  The reference's results are replayed from tests/golden/ref_traces/."""
     import unicodedata
 
     from hypothesis import HealthCheck, given, settings, strategies as st
@@ -1389,7 +1498,14 @@ def test_caption_cleaner_equals_the_reference_on_generated_text():
         pytest.skip("ftfy present: the product uses it, the stand-in comparison does not apply")
     except ImportError:
         pass
-    ref_os, ref_latte = reference_cleaners(fix_text=lambda t: unicodedata.normalize("NFC", t), soup_text=soup)
+    cleaners = []
+
+    def reference(s):   # live only while minting the trace
+        if not cleaners:
+            cleaners.extend(reference_cleaners(fix_text=lambda t: unicodedata.normalize("NFC", t), soup_text=soup))
+        ref_os, ref_latte = cleaners
+        return (ref_os._clean_caption(s), ref_os.text_preprocessing(s), ref_os.text_preprocessing(s, False), ref_latte._clean_caption(s),
+                ref_latte._text_preprocessing(s, clean_caption=True)[0])
     pieces = st.sampled_from([
         "a cat", "Sunset", "over the sea", " ", "  ", ",", ".", "..", "...", ":", " : ", ";", "!", "?", "-", "_", "--", "—", "–", "\\n", "\n",
         "https://example.com/a/b", "www.test.org", "http://x.co", "foo.com/page", "mail@host.ru", "@user_1", "#12", "#123456", "1234567",
@@ -1405,34 +1521,41 @@ def test_caption_cleaner_equals_the_reference_on_generated_text():
     @settings(max_examples=400, deadline=None, derandomize=True, suppress_health_check=list(HealthCheck))   # (a loaded box is not a failure)
     @given(text)
     def check(s):
-        assert C.clean_caption(s) == ref_os._clean_caption(s), ("open-sora once", s)
-        assert C.text_preprocessing(s) == ref_os.text_preprocessing(s), ("open-sora twice", s)
-        assert C.text_preprocessing(s, False) == ref_os.text_preprocessing(s, False), ("open-sora plain", s)
-        assert C.clean_caption(s, mid_strip=False) == ref_latte._clean_caption(s), ("latte once", s)
-        assert C.text_preprocessing(s, True, mid_strip=False) == ref_latte._text_preprocessing(s, clean_caption=True)[0], ("latte twice", s)
+        os_once, os_twice, os_plain, latte_once, latte_twice = ref_trace.lookup(s, lambda: reference(s))
+        assert C.clean_caption(s) == os_once, ("open-sora once", s)
+        assert C.text_preprocessing(s) == os_twice, ("open-sora twice", s)
+        assert C.text_preprocessing(s, False) == os_plain, ("open-sora plain", s)
+        assert C.clean_caption(s, mid_strip=False) == latte_once, ("latte once", s)
+        assert C.text_preprocessing(s, True, mid_strip=False) == latte_twice, ("latte twice", s)
 
     check()
 
 
-def test_mask_strategy_helpers_equal_the_reference_on_generated_cases():
+def test_mask_strategy_helpers_equal_the_reference_on_generated_cases(ref_trace):
     """Property test (hypothesis): parse_mask_strategy / find_nearest_point / apply_mask_strategy / append_generated /
     dframe_to_frame of open_sora_condition.py against the reference's own functions compiled from pipeline_open_sora.py:795-875,
-    over generated strategies (all six fields, negative starts, several groups, several loops, alignment on / off)."""
-    path = "/root/reference/videosys/pipelines/open_sora/pipeline_open_sora.py"
-    if not os.path.isfile(path):
-        pytest.skip("reference tree not present on this box")
+    over generated strategies (all six fields, negative starts, several groups, several loops, alignment on / off).  The reference's
+    results are replayed from tests/golden/ref_traces/."""
     import ast
 
     from hypothesis import HealthCheck, given, settings, strategies as st
 
     from videosys_amd import open_sora_condition as K
 
-    want = {"MASK_DEFAULT", "parse_mask_strategy", "find_nearest_point", "apply_mask_strategy", "append_generated", "dframe_to_frame"}
-    ns = {"torch": torch}
-    for node in ast.parse(open(path).read()).body:
-        name = getattr(node, "name", None) or (node.targets[0].id if isinstance(node, ast.Assign) and isinstance(node.targets[0], ast.Name) else None)
-        if name in want:
-            exec(compile(ast.Module([node], []), path, "exec"), ns)
+    ns = {}
+
+    def ref(name):   # the reference function, live only while minting the trace
+        if not ns:
+            from oracle import ref_loader
+
+            path = os.path.join(ref_loader.REFERENCE_ROOT, "videosys/pipelines/open_sora/pipeline_open_sora.py")
+            want = {"MASK_DEFAULT", "parse_mask_strategy", "find_nearest_point", "apply_mask_strategy", "append_generated", "dframe_to_frame"}
+            ns["torch"] = torch
+            for node in ast.parse(open(path).read()).body:
+                name_ = getattr(node, "name", None) or (node.targets[0].id if isinstance(node, ast.Assign) and isinstance(node.targets[0], ast.Name) else None)
+                if name_ in want:
+                    exec(compile(ast.Module([node], []), path, "exec"), ns)
+        return ns[name]
 
     group = st.tuples(st.integers(0, 2), st.integers(0, 1), st.integers(-6, 6), st.integers(-6, 12), st.integers(0, 8),
                       st.sampled_from([0.0, 0.3, 0.5, 1.0]), st.integers(1, 6))
@@ -1443,13 +1566,19 @@ def test_mask_strategy_helpers_equal_the_reference_on_generated_cases():
            st.integers(0, 10 ** 6))
     def check(groups, loop_i, align, Tz, Tref, seed):
         ms = to_str(groups)
-        assert K.parse_mask_strategy(ms) == ns["parse_mask_strategy"](ms)
+        assert K.parse_mask_strategy(ms) == ref_trace.lookup(("parse", ms), lambda: ref("parse_mask_strategy")(ms))
         g = torch.Generator().manual_seed(seed)
         z = torch.randn(1, 4, Tz, 2, 2, generator=g)
         refs = [[torch.randn(4, Tref, 2, 2, generator=g), torch.randn(4, Tref + 2, 2, 2, generator=g)]]
-        za, zb = z.clone(), z.clone()
+        zb = z.clone()
+
+        def reference():
+            za = z.clone()
+            masks = ref("apply_mask_strategy")(za, refs, [ms], loop_i, align=align)
+            return za, masks
+
         try:
-            want_masks = ns["apply_mask_strategy"](za, refs, [ms], loop_i, align=align)
+            za, want_masks = ref_trace.lookup(("apply", ms, loop_i, align, Tz, Tref, seed), reference)
         except Exception as e:     # e.g. a start beyond the clip: whatever the reference raises, this build raises too
             with pytest.raises(type(e)):
                 K.apply_mask_strategy(zb, refs, [ms], loop_i, align=align)
@@ -1461,9 +1590,9 @@ def test_mask_strategy_helpers_equal_the_reference_on_generated_cases():
     for v in range(0, 40):
         for p in (1, 3, 5):
             for m in (5, 15, 38):
-                assert K.find_nearest_point(v, p, m) == ns["find_nearest_point"](v, p, m)
+                assert K.find_nearest_point(v, p, m) == ref_trace.lookup(("nearest", v, p, m), lambda: ref("find_nearest_point")(v, p, m))
     for n in (0, 5, 10, 35):
-        assert K.dframe_to_frame(n) == ns["dframe_to_frame"](n)
+        assert K.dframe_to_frame(n) == ref_trace.lookup(("dframe", n), lambda: ref("dframe_to_frame")(n))
     with pytest.raises(AssertionError):
         K.dframe_to_frame(7)
 
@@ -1473,7 +1602,7 @@ def test_mask_strategy_helpers_equal_the_reference_on_generated_cases():
 
     vid = torch.arange(2 * 4 * 6 * 2 * 2, dtype=torch.float32).view(2, 4, 6, 2, 2)
     # (an entry without references is [] in the reference's flow — its `refs is None` branch dies on len(None) two lines later)
-    ra, ma = ns["append_generated"](Vae(), vid, [[], [torch.zeros(4, 1, 2, 2)]], [None, "0"], 1, 5, 0.0)
+    ra, ma = ref_trace.value(lambda: ref("append_generated")(Vae(), vid, [[], [torch.zeros(4, 1, 2, 2)]], [None, "0"], 1, 5, 0.0))
     rb, mb = K.append_generated(Vae().encode, vid, [[], [torch.zeros(4, 1, 2, 2)]], [None, "0"], 1, 5, 0.0)
     assert ma == mb and len(ra) == len(rb) and all(len(x) == len(y) and all(torch.equal(p, q) for p, q in zip(x, y)) for x, y in zip(ra, rb))
 

@@ -1,5 +1,5 @@
 """CPU: pins oracle/latte_oracle.py against the fixtures minted from the reference's LatteT2V class
-(oracle/make_golden_latte.py) and, when /root/reference is present, against the live reference; checks the host-side
+(oracle/make_golden_latte.py) and against the reference class on another grid (tests/golden/ref_traces/); checks the host-side
 DDIM scheduler mirror against the oracle / the diffusers restatement."""
 import math
 
@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from conftest import load_golden
+from ref_trace import ref_trace  # noqa: F401  (fixture; tests/golden/ref_traces/)
 from oracle import latte_oracle as LO
 
 
@@ -69,20 +70,24 @@ def test_latte_config_defaults_mirror_reference():
     assert sorted(p.mlp_spatial_broadcast_config) == [400, 480, 560, 640, 720] and p.mlp_broadcast
 
 
-def test_latte_oracle_vs_live_reference():
-    from oracle import ref_loader
-
-    if not ref_loader.reference_available():
-        pytest.skip("reference tree not present (GPU box)")
+def test_latte_oracle_vs_live_reference(ref_trace):
+    """The oracle against the reference's LatteT2V on a grid beside the golden's (its output replayed from
+    tests/golden/ref_traces/)."""
     fx = load_golden("latte_fwd_small.pt")
     o, sd = _oracle(fx)
-    model = ref_loader.build_reference_latte(fx["cfg"], sd)
     g = torch.Generator().manual_seed(5)
     x = torch.randn(2, 4, 4, 12, 20, generator=g)  # non-square grid, not the sample_size grid
     y = torch.randn(2, 9, 64, generator=g)
     t = torch.tensor([801, 801])
-    with torch.no_grad():
-        ref = model(x, timestep=t, encoder_hidden_states=y, encoder_attention_mask=None,
-                    added_cond_kwargs={"resolution": None, "aspect_ratio": None}, enable_temporal_attentions=True,
-                    return_dict=False)[0]
+
+    def live():
+        from oracle import ref_loader
+
+        model = ref_loader.build_reference_latte(fx["cfg"], sd)
+        with torch.no_grad():
+            return model(x, timestep=t, encoder_hidden_states=y, encoder_attention_mask=None,
+                         added_cond_kwargs={"resolution": None, "aspect_ratio": None}, enable_temporal_attentions=True,
+                         return_dict=False)[0]
+
+    ref = ref_trace.value(live)
     torch.testing.assert_close(o(x, t, y, None), ref, rtol=2e-4, atol=2e-4)

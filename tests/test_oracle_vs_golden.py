@@ -1,5 +1,5 @@
 """Pins oracle/stdit3_oracle.py (the CPU restatement) against fixtures minted from the REAL reference
-(oracle/make_golden.py) and, when /root/reference is present, against the live reference."""
+(oracle/make_golden.py) and against the reference class on another case (tests/golden/ref_traces/)."""
 import json
 import os
 
@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, load_golden
+from ref_trace import ref_trace  # noqa: F401  (fixture; tests/golden/ref_traces/)
 from oracle import stdit3_oracle as O
 
 
@@ -202,13 +203,10 @@ def test_dsp_layout_roundtrip():
     torch.testing.assert_close(O.dsp_gather_sequence(back, 2, sp), x)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/videosys"), reason="live reference only in the build container")
-def test_live_reference_forward():
-    from oracle import ref_loader
-
+def test_live_reference_forward(ref_trace):
+    """The oracle against the reference's STDiT3 on a small odd-sized case (its output replayed from tests/golden/ref_traces/)."""
     cfg = dict(depth=1, hidden_size=144, num_heads=2, caption_channels=32, model_max_length=8)
     sd = O.synth_state_dict(**cfg, seed=5)
-    ref = ref_loader.build_reference_stdit3(cfg, sd)
     model = O.STDiT3Oracle(sd, 1, 144, 2)
     g = torch.Generator().manual_seed(3)
     x = torch.randn(2, 4, 3, 9, 7, generator=g)  # odd H/W exercises the patch padding + unpatchify crop
@@ -217,6 +215,12 @@ def test_live_reference_forward():
     kw = dict(mask=mask, fps=torch.tensor([24.0, 24.0]), height=torch.tensor([72.0, 72.0]),
               width=torch.tensor([56.0, 56.0]))
     t = torch.tensor([333.0, 333.0])
-    with torch.no_grad():
-        r = ref(x, t, y, **kw)
+
+    def live():
+        from oracle import ref_loader
+
+        with torch.no_grad():
+            return ref_loader.build_reference_stdit3(cfg, sd)(x, t, y, **kw)
+
+    r = ref_trace.value(live)
     close(model.forward(x, t, y, **kw), r, 2e-4, 2e-4)

@@ -1,22 +1,54 @@
-"""CPU: videosys_amd.pab against the reference's own videosys/core/pab/pab_mgr.py (dependency-free, imported from /root/reference
-when present) on randomised schedules: every attention / cross / MLP decision, counter, skip range and the MLP output cache
-(store, fetch, delete-at-window-end, missing-entry error) must agree call for call."""
+"""CPU: videosys_amd.pab against the reference's own videosys/core/pab/pab_mgr.py (dependency-free) on randomised schedules: every
+attention / cross / MLP decision, counter, skip range and the MLP output cache (store, fetch, delete-at-window-end, missing-entry
+error) must agree call for call.  The reference's answers are replayed from tests/golden/ref_traces/ (tests/ref_trace.py)."""
 import importlib.util
 import os
 import random
 
 import pytest
 
-REF = "/root/reference/videosys/core/pab/pab_mgr.py"
+from ref_trace import ref_trace  # noqa: F401  (fixture; tests/golden/ref_traces/)
+
+REF_REL = "videosys/core/pab/pab_mgr.py"
 
 
 def _ref_module():
-    if not os.path.exists(REF):
-        pytest.skip("reference tree not present on this box")
-    spec = importlib.util.spec_from_file_location("ref_pab_mgr", REF)
+    """The live reference module (only while minting the trace)."""
+    from oracle import ref_loader
+
+    spec = importlib.util.spec_from_file_location("ref_pab_mgr", os.path.join(ref_loader.REFERENCE_ROOT, REF_REL))
     m = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(m)
     return m
+
+
+class _RefReplay:
+    """The calls the test makes on the reference module, each through the trace."""
+
+    def __init__(self, tr):
+        self.tr, self.m = tr, None
+
+    def __getattr__(self, name):
+        def call(*a, **k):
+            def live():
+                if self.m is None:
+                    self.m = _ref_module()
+                return getattr(self.m, name)(*a, **k)
+            return self.tr.value(live)
+        return call
+
+    def start(self, kw):
+        def live():
+            self.m = self.m or _ref_module()
+            self.m.set_pab_manager(self.m.PABConfig(**kw))
+        return self.tr.value(live)
+
+    def output_keys(self):
+        return self.tr.value(lambda: (set(self.m.PAB_MANAGER.config.mlp_spatial_outputs), set(self.m.PAB_MANAGER.config.mlp_temporal_outputs)))
+
+    def reset(self):
+        if self.m is not None:
+            self.m.PAB_MANAGER = None
 
 
 def _cfg_kwargs(rng):
@@ -31,13 +63,13 @@ def _cfg_kwargs(rng):
 
 
 @pytest.mark.parametrize("seed", range(8))
-def test_pab_decisions_match_reference_module(seed):
-    ref = _ref_module()
+def test_pab_decisions_match_reference_module(seed, ref_trace):
+    ref = _RefReplay(ref_trace)
     from videosys_amd import pab as mine
 
     rng = random.Random(seed)
     ts, kw = _cfg_kwargs(rng)
-    ref.set_pab_manager(ref.PABConfig(**kw))
+    ref.start(kw)
     mine.set_pab_manager(mine.PABConfig(**kw))
     try:
         ref.update_steps(len(ts))
@@ -70,11 +102,11 @@ def test_pab_decisions_match_reference_module(seed):
                     elif nxt:
                         ref.save_mlp_output(timestep=t, block_idx=b, ff_output=("ff", t, b, temporal), is_temporal=temporal)
                         mine.save_mlp_output(timestep=t, block_idx=b, ff_output=("ff", t, b, temporal), is_temporal=temporal)
-            rc, mc = ref.PAB_MANAGER.config, mine.PAB_MANAGER.config
-            assert set(rc.mlp_spatial_outputs) == set(mc.mlp_spatial_outputs) and set(rc.mlp_temporal_outputs) == set(mc.mlp_temporal_outputs)
+            mc = mine.PAB_MANAGER.config
+            assert ref.output_keys() == (set(mc.mlp_spatial_outputs), set(mc.mlp_temporal_outputs))
     finally:
         mine.set_pab_manager(None)
-        ref.PAB_MANAGER = None
+        ref.reset()
 
 
 def test_pab_disabled_paths():

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import stdit3_oracle as O
+from ref_trace import ref_trace  # noqa: F401  (fixture; tests/golden/ref_traces/)
 
 
 def _zeros(shape, like=None, dtype=torch.bfloat16):
@@ -584,19 +585,36 @@ def test_generate_conditioning_and_loop_host_flow():
             pipe.generate(refs=[img], ms="0", **kw)
 
 
-def test_pipeline_adopts_the_reference_transformer_module():
-    """OpenSoraPipeline(config, transformer=<the reference's own STDiT3 module>): geometry from its config, weights from its
-    state_dict() (INTEGRATION.md "Handing over components") — the live reference class, imported through oracle/ref_loader.py."""
-    from oracle import ref_loader
+class _ReplayedModule:
+    """What a pipeline reads of a torch module handed to it (``config``, ``state_dict()``), rebuilt from a reference trace."""
 
-    if not ref_loader.reference_available():
-        pytest.skip("reference tree not present on this box")
+    def __init__(self, config, sd):
+        self.config, self._sd = config, sd
+
+    def state_dict(self):
+        return dict(self._sd)
+
+
+def test_pipeline_adopts_the_reference_transformer_module(ref_trace):
+    """OpenSoraPipeline(config, transformer=<the reference's own STDiT3 module>): geometry from its config, weights from its
+    state_dict() (INTEGRATION.md "Handing over components") — the reference class built through oracle/ref_loader.py; what the
+    pipeline reads of it (its config and state dict) is replayed from tests/golden/ref_traces/: the config as it is, the state dict
+    as the keys it holds, each either the weight it was loaded with or (where it differs) the tensor itself."""
     from videosys_amd import OpenSoraConfig, OpenSoraPipeline
+    from videosys_amd.pipeline import module_state
     from videosys_amd.stdit3 import STDiT3
 
     cfg = dict(CFG)
     sd = {k: v.to(torch.bfloat16).float() for k, v in O.synth_state_dict(**cfg, seed=3).items()}
-    ref = ref_loader.build_reference_stdit3(cfg, sd)
+
+    def live():
+        from oracle import ref_loader
+
+        rcfg, rsd = module_state(ref_loader.build_reference_stdit3(cfg, sd))
+        return rcfg, {k: ("loaded" if k in sd and v.dtype == sd[k].dtype and torch.equal(v, sd[k]) else v) for k, v in rsd.items()}
+
+    rcfg, rsd = ref_trace.value(live)
+    ref = _ReplayedModule(rcfg, {k: (sd[k].clone() if isinstance(v, str) else v) for k, v in rsd.items()})
     with fake_ops():
         pipe = OpenSoraPipeline(OpenSoraConfig(num_sampling_steps=2), transformer=ref, device="cpu")
         m = pipe.transformer

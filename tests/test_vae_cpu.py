@@ -1,12 +1,13 @@
 """CPU: the VAE-decode oracle (oracle/vae_oracle.py) against the golden minted from the reference's VideoAutoencoderPipeline
-(oracle/make_golden_vae.py), the decode-side parameter inventory against the reference's own state_dict (when
-/root/reference is present), and the host-side size helpers against the values SURVEY.md §8d derives from the reference."""
+(oracle/make_golden_vae.py), the decode-side parameter inventory against the reference's own state_dict (replayed from
+tests/golden/ref_traces/), and the host-side size helpers against the values SURVEY.md §8d derives from the reference."""
 import os
 
 import pytest
 import torch
 
 from conftest import load_golden
+from ref_trace import ref_trace  # noqa: F401  (fixture; tests/golden/ref_traces/)
 
 
 @pytest.fixture(scope="module")
@@ -32,17 +33,20 @@ def test_vae_oracle_matches_reference_golden(gold):
     assert (xz - gold["x_z_first"]).abs().max().item() < 1e-4
 
 
-def test_decoder_param_inventory_matches_reference():
+def _ref_vae_shapes():
+    """Parameter names and shapes of the reference's VideoAutoencoderPipeline, live only while minting a trace."""
     from oracle import ref_loader
 
-    if not ref_loader.reference_available():
-        pytest.skip("reference tree not present on this box")
+    return {k: tuple(v.shape) for k, v in ref_loader.build_reference_opensora_vae().state_dict().items()}
+
+
+def test_decoder_param_inventory_matches_reference(ref_trace):
+    """The decoder's parameter inventory against the reference class (replayed from tests/golden/ref_traces/)."""
     from videosys_amd.vae_open_sora import decoder_param_shapes
 
-    model = ref_loader.build_reference_opensora_vae()
-    ref = {k: tuple(v.shape) for k, v in model.state_dict().items()
+    ref = {k: v for k, v in ref_trace.value(_ref_vae_shapes).items()
            if "encoder" not in k and ".quant_conv" not in k and k not in ("scale", "shift")}
-    assert decoder_param_shapes() == ref
+    assert len(ref) > 10 and decoder_param_shapes() == ref
 
 
 def test_latent_size_helpers():
@@ -65,22 +69,23 @@ def test_vae_needs_gpu():
         OpenSoraVAE({}, device="cpu")
 
 
-def test_vae_oracle_matches_live_reference_class():
-    """oracle/vae_oracle.py against the reference's VideoAutoencoderPipeline run here (another seed, another latent size, three
-    micro-batches incl. a 1-latent-frame tail) when /root/reference is present."""
-    from oracle import ref_loader
-
-    if not ref_loader.reference_available():
-        pytest.skip("reference tree not present on this box")
+def test_vae_oracle_matches_live_reference_class(ref_trace):
+    """oracle/vae_oracle.py against the reference's VideoAutoencoderPipeline (another seed, another latent size, three
+    micro-batches incl. a 1-latent-frame tail; its output replayed from tests/golden/ref_traces/)."""
     from oracle import vae_oracle as VO
     from videosys_amd.vae_open_sora import synth_state_dict
 
     sd = synth_state_dict(21)
-    model = ref_loader.build_reference_opensora_vae(sd)
     g = torch.Generator().manual_seed(4)
     z = torch.randn(1, 4, 11, 4, 6, generator=g)       # 5 + 5 + 1 latent frames -> 17 + 17 + 4 = 38 frames
-    with torch.no_grad():
-        ref = model.decode(z, num_frames=38)
+
+    def live():
+        from oracle import ref_loader
+
+        with torch.no_grad():
+            return ref_loader.build_reference_opensora_vae(sd).decode(z, num_frames=38)
+
+    ref = ref_trace.value(live)
     out = VO.decode(sd, z, 38)
     assert out.shape == ref.shape == (1, 3, 38, 32, 48)
     assert (out - ref).abs().max().item() < 1e-4
@@ -107,36 +112,36 @@ def test_vae_encode_oracle_matches_reference_golden():
     assert (z - gold["z_fp32"]).abs().max().item() < 1e-4
 
 
-def test_encoder_param_inventory_matches_reference():
-    from oracle import ref_loader
-
-    if not ref_loader.reference_available():
-        pytest.skip("reference tree not present on this box")
+def test_encoder_param_inventory_matches_reference(ref_trace):
+    """The encoder's parameter inventory against the reference class (replayed from tests/golden/ref_traces/)."""
     from videosys_amd.vae_open_sora import decoder_param_shapes, encoder_param_shapes, synth_state_dict
 
-    model = ref_loader.build_reference_opensora_vae()
-    ref = {k: tuple(v.shape) for k, v in model.state_dict().items() if "encoder" in k or ".quant_conv" in k}
-    assert encoder_param_shapes() == ref
+    ref = {k: v for k, v in ref_trace.value(_ref_vae_shapes).items() if "encoder" in k or ".quant_conv" in k}
+    assert len(ref) > 10 and encoder_param_shapes() == ref
     a, b = synth_state_dict(5), synth_state_dict(5, encoder=True)
     assert set(b) == set(decoder_param_shapes()) | set(encoder_param_shapes())
     assert all(torch.equal(a[k], b[k]) for k in a)          # decode-side weights do not depend on the flag
 
 
-def test_vae_encode_oracle_matches_live_reference_class():
-    from oracle import ref_loader
-
-    if not ref_loader.reference_available():
-        pytest.skip("reference tree not present on this box")
+def test_vae_encode_oracle_matches_live_reference_class(ref_trace):
+    """oracle/vae_oracle.py encode against the reference's VideoAutoencoderPipeline.encode on the same seeded noise stream (its
+    output replayed from tests/golden/ref_traces/)."""
     from oracle import vae_oracle as VO
     from videosys_amd.vae_open_sora import synth_state_dict
 
     sd = synth_state_dict(21, encoder=True)
-    model = ref_loader.build_reference_opensora_vae(sd)
     g = torch.Generator().manual_seed(4)
     x = torch.randn(2, 3, 5, 16, 24, generator=g).clamp(-1, 1)     # two samples, one 5-frame micro batch (3 pad frames)
-    torch.manual_seed(99)
-    with torch.no_grad():
-        ref = model.encode(x)
+
+    def live():
+        from oracle import ref_loader
+
+        model = ref_loader.build_reference_opensora_vae(sd)
+        torch.manual_seed(99)
+        with torch.no_grad():
+            return model.encode(x)
+
+    ref = ref_trace.value(live)
     torch.manual_seed(99)
     out = VO.encode(sd, x)
     assert out.shape == ref.shape == (2, 4, 2, 2, 3)
