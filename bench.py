@@ -13,12 +13,17 @@ over the N GPUs with Dynamic Sequence Parallelism (strong scaling).  ``value`` =
 minute of the 30-step denoising loop (DiT only — T5 text encode and VAE decode are the "next" rows of SURVEY.md §8f and
 are not in the number; said so in config).
 
-Extra objects on the JSON line:
+A plain run does only what the headline figure needs: set-up (build check, model, inputs), the W warm-up steps, the K timed
+steps, --dump-outputs DIR if given, and the JSON line.  ``--full`` adds everything else the benchmark measures, each in runs
+of its own after the timed steps (the headline figure is the same either way); without it these objects of the line are null:
   roofline      dominant kernel = the bf16 MFMA GEMM family (91 % of the step's FLOPs): algorithmic FLOPs per launch /
                 average launch duration measured with HIP events on the launch stream in an instrumented replay of
                 the same steps; peak 2500 TFLOP/s dense bf16 (MI355X_MICROARCH.md).
+  dsp           (N > 1) per-rank communication time, both overlap modes and the exchange path, from short replays.
   cpu_baseline  the CPU oracle (a port of the reference's fp32 PyTorch path) timed on this box's host cores at the full
                 token count: valid_depth 1 and 2, warm-up + 3 repeats, thread-count sweep, fitted to depth 28.
+  vae_decode    the Open-Sora VAE decode of the final latent (sharded over the ranks for N > 1).
+  t5_encode     the T5-v1.1-XXL encode of a 300-token prompt (N = 1).
 """
 from __future__ import annotations
 
@@ -44,9 +49,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--depth", type=int, default=28, help="debug only; the reported config is depth 28")
     ap.add_argument("--pab", action="store_true", help="BASELINE config 3: attention-only PAB (reported as a separate workload)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-vae", action="store_true", help="skip the (untimed-region) VAE decode measurement")
-    ap.add_argument("--no-t5", action="store_true", help="skip the (untimed-region) T5 encode measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: the roofline replay, the DSP "
+                         "communication replays (N > 1), the CPU baseline, the VAE decode and the T5 encode (off: those objects are null)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-vae", action="store_true", help="with --full: skip the (untimed-region) VAE decode measurement")
+    ap.add_argument("--no-t5", action="store_true", help="with --full: skip the (untimed-region) T5 encode measurement")
     ap.add_argument("--text-len", type=int, default=300)
     ap.add_argument("--no-cp", action="store_true",
                     help="N = 2: plain sequence parallelism over both ranks (the reference pipeline's default) instead of the reference's "
@@ -130,7 +138,7 @@ def main():
     # ---- workload: BASELINE config 2 (config 3 with --pab)
     frames, height, width = (64, 512, 512) if args.geometry == "512x512x64f" else (128, 720, 1280)
     base_geo = args.geometry == "512x512x64f"
-    if not base_geo:
+    if not base_geo or not args.full:
         args.no_cpu_baseline = args.no_vae = args.no_t5 = True
     T, Hl, Wl = get_latent_size(frames, height, width)
     cfg = STDiT3Config(depth=args.depth)
@@ -190,6 +198,10 @@ def main():
         last_out = one_step(args.warmup + i)
     barrier()
     dt_s = time.perf_counter() - t0
+    if world > 1:
+        from videosys_amd import dsp as vdsp
+
+        vdsp.check_exchange(model)   # a timed-out peer-to-peer exchange in the timed steps must fail the bench, not shape its number
     if args.dump_outputs and rank == 0:
         # (before the instrumented replays below, which step the latent further)
         dump_outputs(args.dump_outputs, {"model_out": last_out, "latent": z})
@@ -201,9 +213,10 @@ def main():
         dt_s = float(tt.item())
     step_s = dt_s / args.steps
 
-    # ---- roofline of the dominant kernel family (instrumented replay; HIP events on the launch stream)
+    # ---- roofline of the dominant kernel family (--full: instrumented replay; HIP events on the launch stream)
     roof = None
-    if rank == 0:
+    nrep = min(args.steps, 3)
+    if rank == 0 and args.full:
         ev = []
         real_gemm = ops.gemm
 
@@ -249,23 +262,23 @@ def main():
             ev.append((s, e, 2.0 * x.shape[0] * w.shape[0] * x.shape[1], 6))
             return r
 
-    barrier()
-    nrep = min(args.steps, 3)
-    if rank == 0:
-        ops.gemm_gate_res_add = timed_gemm_gra
-        ops.gemm, ops.gemm_ln, ops.gemm_stats = timed_gemm, timed_gemm_ln, timed_gemm_stats  # every rank replays the steps (DSP collectives); only rank 0 is instrumented
-    was_prog = model.use_programs
-    model.use_programs = False   # the instrumented replay issues every launch from Python (a recorded launch program would bypass
-    try:                         # the event brackets); the TIMED region above ran the product default
-        for i in range(nrep):
-            one_step(i)
-        torch.cuda.synchronize()
-    finally:
-        model.use_programs = was_prog
+    if args.full:
+        barrier()
         if rank == 0:
-            ops.gemm, ops.gemm_ln, ops.gemm_stats = real_gemm, real_gemm_ln, real_gemm_stats
-            ops.gemm_gate_res_add = real_gemm_gra
-    if rank == 0:
+            ops.gemm_gate_res_add = timed_gemm_gra
+            ops.gemm, ops.gemm_ln, ops.gemm_stats = timed_gemm, timed_gemm_ln, timed_gemm_stats  # every rank replays the steps (DSP collectives); only rank 0 is instrumented
+        was_prog = model.use_programs
+        model.use_programs = False   # the instrumented replay issues every launch from Python (a recorded launch program would bypass
+        try:                         # the event brackets); the TIMED region above ran the product default
+            for i in range(nrep):
+                one_step(i)
+            torch.cuda.synchronize()
+        finally:
+            model.use_programs = was_prog
+            if rank == 0:
+                ops.gemm, ops.gemm_ln, ops.gemm_stats = real_gemm, real_gemm_ln, real_gemm_stats
+                ops.gemm_gate_res_add = real_gemm_gra
+    if rank == 0 and args.full:
         # drop the once-per-prompt kv_linear launches (none after warm-up) and aggregate
         tot_ms = sum(s.elapsed_time(e) for s, e, _, _ in ev)
         tot_fl = sum(f for _, _, f, _ in ev)
@@ -304,17 +317,15 @@ def main():
             "gemm_ms_per_step": round(tot_ms / nrep, 2),
             "per_epilogue_tflops": {str(k): round(v[1] / (v[0] * 1e-3) / 1e12, 1) for k, v in by_epi.items()},
         }
-    if world > 1:
+    if world > 1 and args.full:
         barrier()
 
-    # ---- DSP communication (N > 1): HIP-event brackets around every collective of a rank in short replays — all-to-all time
+    # ---- DSP communication (N > 1, --full): HIP-event brackets around every collective of a rank in short replays — all-to-all time
     # per step and rank with the exchanges serialized on the main stream (overlap off), the step time both ways, and the
     # fraction of the serialized communication time the default two-stream overlap hides
     dsp_info = None
-    if world > 1:
+    if world > 1 and args.full:
         import torch.distributed as dist
-
-        from videosys_amd import dsp as vdsp
 
         def replay(overlap):
             model._overlap = bool(overlap) and model._side is not None
@@ -369,7 +380,7 @@ def main():
                 "note": "event brackets include the wait for the slowest peer; overlap_fraction = (step_off - step_on) / serialized comm; these replays issue every launch from Python (eager) so that the brackets run",
             }
 
-    # ---- CPU baseline (rank 0, N == 1 only): oracle = fp32 port of the reference path at the full token count
+    # ---- CPU baseline (rank 0, N == 1 only, --full): oracle = fp32 port of the reference path at the full token count
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.pab:
         try:
@@ -377,7 +388,7 @@ def main():
         except Exception as e:  # a reported baseline, never a reason to lose the measurement
             cpu = {"error": f"{type(e).__name__}: {e}"[:300]}
 
-    # ---- VAE decode of the final latent (rank 0, N == 1; outside the timed region; row a14): one warm-up + one timed call
+    # ---- VAE decode of the final latent (rank 0, N == 1, --full; outside the timed region; row a14): one warm-up + one timed call
     vae = None
     if rank == 0 and world == 1 and not args.no_vae:
         try:
@@ -397,7 +408,7 @@ def main():
         except Exception as e:  # the extra terms must never cost the bench line
             vae = {"error": f"{type(e).__name__}: {e}"[:300]}
 
-    # ---- N > 1: the VAE decode sharded over the ranks by output frame + one all-gather of uint8 frames (outside the timed region;
+    # ---- N > 1, --full: the VAE decode sharded over the ranks by output frame + one all-gather of uint8 frames (outside the timed region;
     # the reference decodes the whole video on every rank).  Every rank takes part; the slowest rank's time is reported.
     if world > 1 and not args.no_vae:
         import torch.distributed as dist
@@ -423,7 +434,7 @@ def main():
             vae = {"error": f"{type(e).__name__}: {e}"[:300]}
         barrier()
 
-    # ---- T5-v1.1-XXL prompt encode (rank 0, N == 1; outside the timed region): 300-token prompt, device-generated weights
+    # ---- T5-v1.1-XXL prompt encode (rank 0, N == 1, --full; outside the timed region): 300-token prompt, device-generated weights
     t5 = None
     if rank == 0 and world == 1 and not args.no_t5:
         try:
@@ -458,7 +469,7 @@ def main():
                               f"latent [4,{T},{Hl},{Wl}], CFG batch 2 = {2 * T * (Hl // 2) * (Wl // 2)} token rows, ") +
                              f"{L} text tokens, depth {args.depth}" + (", PAB attention-only (config 3)" if args.pab else "")),
                 "steps_per_video": STEPS_PER_VIDEO, "parallelism": (f"dsp{world}" if cp_size == 1 else f"cfg-parallel 2 x dsp{sp_size} (the reference's enable_cp; --no-cp: dsp{world})"),
-                "not_included": "value is DiT denoising only; vae_decode / t5_encode report the other two terms of the metric beside it",
+                "not_included": "value is DiT denoising only; with --full, vae_decode / t5_encode report the other two terms of the metric beside it",
                 "algorithmic_tflop_per_step": 89.4 if args.depth == 28 and L == 300 and base_geo else None,
                 "launch_path": ("recorded launch program: " + json.dumps(model.program_stats)) if model.use_programs else "eager (every launch from Python)",
                 "dsp_layout": None if world == 1 else {"scatter": model._scatter, "overlap": str(model._overlap), "switch": model._switch},

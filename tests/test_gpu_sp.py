@@ -394,7 +394,7 @@ def test_bench_two_ranks_dry_run(nproc, cp):
     env = dict(os.environ, VSYS_BENCH_ONE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "2", "--warmup", "1",
-           "--depth", "2", "--no-cpu-baseline", "--no-vae", "--no-t5"] + (["--cp"] if cp and nproc > 2 else ([] if cp or nproc > 2 else ["--no-cp"]))
+           "--depth", "2", "--full", "--no-cpu-baseline", "--no-vae", "--no-t5"] + (["--cp"] if cp and nproc > 2 else ([] if cp or nproc > 2 else ["--no-cp"]))
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -479,7 +479,7 @@ def test_bench_plain_form_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["VSYS_BENCH_ONE_GPU"] = "1"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--depth", "2",
-           "--no-cpu-baseline", "--no-t5"]
+           "--full", "--no-cpu-baseline", "--no-t5"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -488,6 +488,41 @@ def test_bench_plain_form_launches_its_own_ranks():
     assert j["n_gpus"] == 2 and j["value"] > 0 and j["config"]["parallelism"].startswith("cfg-parallel 2 x dsp1")
     v = j["vae_decode"]      # N > 1: the decode is sharded by output frame and gathered once
     assert v.get("sharded_over_ranks") == 2 and v["frames_per_rank"] == [32, 32] and v["output"] == [1, 64, 512, 512, 3], v
+
+
+@pytest.mark.parametrize("nproc", [1, 2])
+def test_bench_plain_run_is_the_headline_only(nproc, tmp_path):
+    """Without --full, bench.py times the steps and prints the line, and nothing else: roofline, dsp, cpu_baseline, vae_decode and
+    t5_encode are null.  What the timed steps compute does not depend on --full: the arrays --dump-outputs writes are the same
+    bit for bit with and without it (N = 2: the plain form starting its own ranks, both on the box's one GPU over gloo)."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    from conftest import ROOT
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env["VSYS_BENCH_ONE_GPU"] = "1"
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-vae", "--no-t5"])):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--depth", "2",
+               "--dump-outputs", str(tmp_path / mode)] + extra
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        js = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(js) == 1, r.stdout[-2000:]
+        lines[mode] = json.loads(js[0])
+    j = lines["plain"]
+    assert j["n_gpus"] == nproc and j["steps"] == 2 and j["warmup"] == 1 and j["value"] > 0 and j["ms_per_step"] > 0
+    assert j["unit"] == "videos/min" and j["higher_is_better"] is True and j["dtype"] == "bf16"
+    assert all(j[k] is None for k in ("roofline", "dsp", "cpu_baseline", "vae_decode", "t5_encode")), j
+    assert lines["full"]["roofline"]["frac"] > 0 and (lines["full"]["dsp"] is not None) == (nproc > 1)
+    for name, shape in (("model_out", (2, 8, 19, 64, 64)), ("latent", (1, 4, 19, 64, 64))):
+        a, b = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert a.shape == shape and a.dtype == np.float32 and np.isfinite(a).all()
+        assert np.array_equal(a, b), name
 
 
 def test_batched_copy_executor_matches_plan_semantics():

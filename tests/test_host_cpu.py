@@ -1669,6 +1669,28 @@ def test_bench_plain_form_starts_its_own_ranks(monkeypatch):
         assert not seen
 
 
+def test_bench_full_is_opt_in(monkeypatch):
+    """A plain bench.py command line measures the headline figure only; --full (off by default) adds the other measurements and
+    is handed on to the ranks a plain ``--gpus N`` starts."""
+    import subprocess
+    import sys
+
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--full"])
+    assert bench.parse().full is True
+    seen = {}
+    monkeypatch.setattr(subprocess, "call", lambda cmd, env=None: seen.setdefault("cmd", cmd) and 0)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--full"])
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 0 and seen["cmd"][-3:] == ["--gpus", "2", "--full"]
+
+
 @pytest.mark.parametrize("B,T,S,P,chunks", [(2, 5, 12, 4, False), (1, 38, 36, 8, False), (2, 19, 10, 4, True), (1, 10, 7, 8, True),
                                             (2, 3, 9, 2, False)])
 def test_p2p_plans_equal_pack_exchange_unpack(B, T, S, P, chunks):
