@@ -226,7 +226,11 @@ def test_gemm_rejects_bad_shapes(ops):
 
 def test_gemm_config2_shapes_linearity(ops):
     """Full BASELINE config-2 token count (N = 38912) for the four weight shapes: checked against torch fp32 on
-    sampled rows and through linearity gemm(x1 + x2) ~= gemm(x1) + gemm(x2) with bias = 0."""
+    sampled rows, then on EVERY row against float64 (tests/numerics.py: acc(K) + one rounding of the output), and through
+    linearity gemm(x1 + x2) ~= gemm(x1) + gemm(x2) with bias = 0, where x1 / x2 split the entries of x (x1 + x2 = x exactly):
+    |gemm(x) - (gemm(x1) + gemm(x2))| <= bound(x) + 2^-8 (1 + 2^-7) (|gemm(x1)| + |gemm(x2)|) + acc(K) of x1 and x2."""
+    import numerics as nm
+
     M = 38912
     g = torch.Generator().manual_seed(1)
     for N, K in ((3456, 1152), (1152, 1152), (4608, 1152), (1152, 4608)):
@@ -240,6 +244,20 @@ def test_gemm_config2_shapes_linearity(ops):
         # last / first tile rows exact position check
         ref_edge = x[-3:].float() @ w.float().t()
         check(out[-3:], ref_edge, what="tail rows")
+        half = torch.rand(M, K, generator=g).to(dev()) < 0.5
+        x1 = torch.where(half, x, torch.zeros_like(x))
+        x2 = x - x1
+        o1, o2 = ops.gemm(x1, w, None), ops.gemm(x2, w, None)
+        every, lin = nm.Bound(f"c2 gemm {N}x{K} every row"), nm.Bound(f"c2 gemm {N}x{K} linearity")
+        for r0, r1 in nm.row_chunks(M, 4096):
+            ref, s = nm.matmul_ref(x[r0:r1], w)
+            bound = nm.acc(K, s) + nm.rnd(ref)
+            every.add(out[r0:r1], ref, bound, r0)
+            parts = o1[r0:r1].double() + o2[r0:r1].double()
+            lin.add(out[r0:r1].double() - parts, torch.zeros_like(ref),
+                    2 * nm.acc(K, s) + nm.rnd(ref) + nm.U_BF16 * (1 + 2.0**-7) * (o1[r0:r1].double().abs() + o2[r0:r1].double().abs()), r0)
+        every.check()
+        lin.check()
 
 
 def test_linear_small(ops):

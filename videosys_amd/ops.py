@@ -379,7 +379,9 @@ def kv_pad_len(kv_len: int) -> int:
 def alloc_kv_buffers(batch, heads, kv_len, device):
     kv_pad = kv_pad_len(kv_len)
     kp = torch.zeros(batch, heads, kv_pad, HEAD_DIM, dtype=torch.bfloat16, device=device)
-    vt = torch.zeros(batch, heads, VT_ROWS, kv_pad, dtype=torch.bfloat16, device=device)  # rows 72..95 stay zero
+    # Vt rows 72 and 76 are written by attn_prep_kv (1.0 over the valid keys: the softmax denominator rides on the PV MFMA); rows
+    # 73..75 and 77..95 are never written by it, so they must be zero on entry: this zero fill is part of the contract
+    vt = torch.zeros(batch, heads, VT_ROWS, kv_pad, dtype=torch.bfloat16, device=device)
     return kp, vt
 
 
