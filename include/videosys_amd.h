@@ -220,6 +220,33 @@ int vsys_flash_attn_d72_exact(const void* q, int64_t q_stride, const void* q_nor
                               int64_t out_stride, int64_t batch, int64_t heads, int64_t q_len, int64_t kv_len, int64_t kv_pad,
                               float eps, void* stream);
 
+/* vsys_attn_prep_kv for a batch whose samples have DIFFERENT key counts: the reference's varlen cross-attention path
+ * (attentions.py:240-258; the packed text of open_sora_transformer_3d.py:526-537).  k / v are rows of the PACKED text
+ * (sum(lens) rows, sample after sample), cu_seqlens is a device int32[batch + 1] of row offsets (cu[0] = first row of sample 0,
+ * lens[b] = cu[b + 1] - cu[b]).  kp[b] / vt[b] get exactly what vsys_attn_prep_kv writes for kv_len = lens[b]: scale folded into Kp,
+ * ones rows 72 and 76 of Vt over the valid keys, zeros behind lens[b] up to kv_pad (Vt rows 73..75, 77..95 are not written: zero
+ * them once, as for vsys_attn_prep_kv).  One launch for the batch.  cu_seqlens_host is a HOST copy of the same batch + 1 numbers:
+ * the entry point validates with it (no device read-back) — any lens[b] < 1 or > kv_pad, or cu[0] < 0, is VSYS_ERR_SHAPE and
+ * nothing is launched.  The caller guarantees that k and v hold cu[batch] rows. */
+int vsys_attn_prep_kv_varlen(const void* k, int64_t k_stride, const void* v, int64_t v_stride, const void* k_norm_w,
+                             const int* cu_seqlens, const int* cu_seqlens_host, void* kp, void* vt, int64_t batch, int64_t heads,
+                             int64_t kv_pad, float eps, void* stream);
+
+/* vsys_flash_attn_d72_exact for a batch whose samples have DIFFERENT key counts, in one launch: sample b attends to its own
+ * kv_lens[b] keys (attentions.py:240-258, flash_attn_varlen_func over the packed text; open_sora_transformer_3d.py:526-537).
+ * kv_lens is a device int32[batch]: the workgroup of (b, h) reads its count there (one scalar load), so a recorded launch program
+ * replays the call with no key count baked in.  Carries the padding promise of vsys_flash_attn_d72_exact PER SAMPLE: (kp, vt) were
+ * written by vsys_attn_prep_kv_varlen for exactly these counts into zero-initialised buffers; the underflow guard of that entry
+ * point applies per query block.  kv_lens_host is a HOST copy of the same numbers, read at every call (also at every replay of a
+ * recorded call: keep it alive and unchanged).  With it the entry point validates — any count < 1 or > kv_pad is VSYS_ERR_SHAPE,
+ * nothing is launched — and picks the kernel: max(kv_lens) <= 320 keys runs the resident-K/V kernel once for the whole batch; what
+ * that kernel does not take (longer text, q_len * q_stride past its 32-bit staging offsets, VSYS_FLASH_VARIANT or VSYS_FLASH_EXACT
+ * selecting another kernel) is answered by one vsys_flash_attn_d72_exact launch per sample with kv_len = kv_lens_host[b] — same
+ * results, batch launches. */
+int vsys_flash_attn_d72_varlen(const void* q, int64_t q_stride, const void* q_norm_w, const void* kp, const void* vt,
+                               const int* kv_lens, const int* kv_lens_host, void* out, int64_t out_stride, int64_t batch,
+                               int64_t heads, int64_t q_len, int64_t kv_pad, float eps, void* stream);
+
 /* vsys_flash_attn_d72 (attentions.py:75,100) with a promise about the keys: k_norm_bound >= the Euclidean norm of every Kp row (as stored: normed, scaled
  * by log2(e) / sqrt(72)).  For an RMS-normed key that is sqrt(72) max|k_norm.weight| log2(e) / sqrt(72) (1 + rounding), a property
  * of the WEIGHTS (normalization.py:28-33): the caller computes it once per block.  By Cauchy-Schwarz m_i = |q_i| k_norm_bound bounds
@@ -509,7 +536,9 @@ int vsys_softmax_rows(const void* s_f32, void* p, int64_t rows, int64_t n, int64
 #define VSYS_OP_VAE_FIRST_IM2COL             52
 #define VSYS_OP_EXTRACT_PLANAR               53
 #define VSYS_OP_SOFTMAX_ROWS                 54
-#define VSYS_OP_COUNT 55
+#define VSYS_OP_ATTN_PREP_KV_VARLEN          55
+#define VSYS_OP_FLASH_ATTN_D72_VARLEN        56
+#define VSYS_OP_COUNT 57
 /* <<< VSYS_OP codes */
 
 #define VSYS_CMD_MAX_INT 24

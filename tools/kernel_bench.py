@@ -137,6 +137,33 @@ def main():
         for tag, ex in (("masked", False), ("exact", True)):
             ms = timeit(lambda: ops.flash_attn(x, None, kpc, vtc, ao, 2, H, 19456, 300, keys_exact=ex), args.reps)
             res.setdefault("flash_cross_L300_" + tag, []).append((ms, 4.0 * 2 * H * 19456 * 300 * 72 / (ms * 1e-3) / 1e12))
+    # cross_varlen (CFG batch 4 at the config-2 shape): per-sample key counts read on the device (vsys_flash_attn_d72_varlen), interleaved
+    # with the fixed-length exact launch on the same work (all lengths 300), with the four per-sample launches the one launch replaces,
+    # and a ragged batch (less work: 300 + 41 + 128 + 7 keys)
+    if not os.environ.get("VSYS_KB_SPATIAL_ONLY"):
+        x4, ao4 = rnd(4 * 19456, C), torch.empty(4 * 19456, C, dtype=torch.bfloat16, device=dev)
+        kv4 = rnd(1200, 2 * C)
+        kp4, vt4 = ops.alloc_kv_buffers(4, H, 300, dev)
+        ops.attn_prep_kv(kv4[:, :C], kv4[:, C:], None, kp4, vt4, 4, H, 300)
+        same = ops.VarlenKeys([300] * 4, dev)
+        rag = ops.VarlenKeys([300, 41, 128, 7], dev)
+        kpr, vtr = ops.alloc_kv_buffers(4, H, 300, dev)
+        ops.attn_prep_kv_varlen(kv4[:, :C], kv4[:, C:], None, rag, kpr, vtr, H)
+
+        def per_sample():
+            for b in range(4):
+                ops.flash_attn(x4[b * 19456:(b + 1) * 19456], None, kp4[b:b + 1], vt4[b:b + 1], ao4[b * 19456:(b + 1) * 19456], 1, H, 19456, 300,
+                               keys_exact=True)
+
+        cases = (("flash_cross_b4_L300_exact", lambda: ops.flash_attn(x4, None, kp4, vt4, ao4, 4, H, 19456, 300, keys_exact=True), 1200),
+                 ("flash_cross_varlen_b4_L300", lambda: ops.flash_attn_varlen(x4, None, kp4, vt4, same, ao4, H, 19456), 1200),
+                 ("flash_cross_b4_L300_four_launches", per_sample, 1200),
+                 ("flash_cross_varlen_b4_ragged_300_41_128_7", lambda: ops.flash_attn_varlen(x4, None, kpr, vtr, rag, ao4, H, 19456), 476))
+        for rd in range(args.rounds):
+            for tag, fn, nkeys in cases:
+                ms = timeit(fn, args.reps)
+                res.setdefault(tag, []).append((ms, 4.0 * H * 19456 * nkeys * 72 / (ms * 1e-3) / 1e12))
+        del x4, ao4
     # every flash variant must give the default's bits (they differ in schedule only)
     ref_s, ref_c = torch.empty_like(ao), torch.empty_like(ao)
     ops.flash_attn(qkv[:, :C], qw, kp, vt, ref_s, 38, H, 1024, 1024)

@@ -42,24 +42,36 @@ constexpr float NEG_BIG = -1.0e30f;
 // attn_prep_kv: k,v rows (strided, heads interleaved) -> Kp[batch][H][kv_pad][72] (RMS-normed, rows >= kv_len zero)
 //                                                     -> Vt[batch][H][96][kv_pad] (transposed; cols >= kv_len zero)
 // grid: (kv_pad/64, batch*H); block 256.
+// VARLEN (vsys_attn_prep_kv_varlen): k / v are the rows of the PACKED text; sample b owns rows cu_seqlens[b] .. cu_seqlens[b + 1]
+// (device int32[batch + 1]) and its own key count takes the place of kv_len — same tiles, same arithmetic, same bits per sample.
 // ---------------------------------------------------------------------------------------------------------
+template <bool VARLEN>
 __global__ __launch_bounds__(256) void attn_prep_kv_kernel(const bf16_t* __restrict__ k, int64_t k_stride,
                                                            const bf16_t* __restrict__ v, int64_t v_stride,
                                                            const bf16_t* __restrict__ k_norm_w, bf16_t* __restrict__ kp,
-                                                           bf16_t* __restrict__ vt, int heads, int kv_len, int kv_pad,
-                                                           float eps, float kscale) {
+                                                           bf16_t* __restrict__ vt, int heads, int kv_len_arg, int kv_pad,
+                                                           float eps, float kscale, const int* __restrict__ cu_seqlens) {
   __shared__ __attribute__((aligned(16))) bf16_t vs[64][HD + 8];  // [token][d], 160-byte rows
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int s0 = blockIdx.x * 64;
   const int bh = blockIdx.y;
   const int b = bh / heads, h = bh - b * heads;
+  // first source row and key count of this sample (wave-uniform: b comes from the workgroup id).  VARLEN clamps the count to the
+  // buffer's kv_pad: the launcher validated the host copy of the offsets, the clamp only keeps a disagreeing device array in bounds
+  int64_t row0 = (int64_t)b * kv_len_arg;
+  int kv_len = kv_len_arg;
+  if constexpr (VARLEN) {
+    const int c0 = cu_seqlens[b], n = cu_seqlens[b + 1] - c0;
+    row0 = c0;
+    kv_len = n < 0 ? 0 : (n > kv_pad ? kv_pad : n);
+  }
 
   // ---- V tile -> LDS (64 tokens x 9 chunks)
   for (int q = tid; q < 64 * 9; q += 256) {
     const int r = q / 9, c = q - r * 9;
     const int s = s0 + r;
     uint4 val = make_uint4(0, 0, 0, 0);
-    if (s < kv_len) val = *reinterpret_cast<const uint4*>(v + ((int64_t)b * kv_len + s) * v_stride + h * HD + c * 8);
+    if (s < kv_len) val = *reinterpret_cast<const uint4*>(v + (row0 + s) * v_stride + h * HD + c * 8);
     *reinterpret_cast<uint4*>(&vs[r][c * 8]) = val;
   }
 
@@ -73,7 +85,7 @@ __global__ __launch_bounds__(256) void attn_prep_kv_kernel(const bf16_t* __restr
 #pragma unroll
     for (int e = 0; e < 24; ++e) x[e] = 0.f;
     if (active && s < kv_len) {
-      const bf16_t* src = k + ((int64_t)b * kv_len + s) * k_stride + h * HD + part * 24;
+      const bf16_t* src = k + (row0 + s) * k_stride + h * HD + part * 24;
 #pragma unroll
       for (int c = 0; c < 3; ++c) unpack8(*reinterpret_cast<const uint4*>(src + c * 8), x + c * 8);
     }
@@ -141,6 +153,7 @@ struct FlashParams {
   int chunks;                              // RES kernel: workgroups per (batch, head), each walks nqb / chunks query blocks
   float eps;
   unsigned long long* dbg;                 // lab variant 2 only: 5 phase-cycle accumulators
+  const int* kv_lens;                      // VARLEN instantiation only: [batch] key counts in device memory (kv_len is then unused)
 };
 
 // WPS = waves per SIMD the register allocation targets: 2 (two workgroups per CU, no spills) or 3 (168 registers: the peeled
@@ -162,7 +175,7 @@ constexpr int RES_Q_BYTES = 5 * 1024;   // per-wave Q image (32 rows x 144 B = 4
 // block of five tiles) is compiled out.  The only thing a padding key still touches is the running max (it sees the logit 0); that is
 // harmless unless EVERY real logit of a row lies ~100 (exp2 domain) below zero — the block's denominator then underflows, which is
 // detected per block and answered by recomputing that block with the masked tile sequence (cold path, same bits as the masked kernel).
-template <int ABL, int WPS, bool RES = false, bool EXACT = false>
+template <int ABL, int WPS, bool RES = false, bool EXACT = false, bool VARLEN = false>
 __global__ __launch_bounds__(RES ? 512 : 256, RES ? 2 : WPS) void flash_attn_d72_kernel(FlashParams p) {
 #if __HIP_DEVICE_COMPILE__  // buffer-resource types exist in the device pass only
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -176,6 +189,17 @@ __global__ __launch_bounds__(RES ? 512 : 256, RES ? 2 : WPS) void flash_attn_d72
   const int b = bh / p.heads, h = bh - b * p.heads;
   constexpr int NW = RES ? 8 : 4;
   int q0 = qb * 128 + wave * 32;   // (RES: set per query block below)
+  // key count of this workgroup: the launch's scalar, or (VARLEN) sample b's own count read from device memory.  b comes from the
+  // workgroup id, so the read is one scalar load and the value is wave-uniform; clamped to what the LDS stages and the buffers hold
+  // (the launcher validated the host copy of the same numbers, the clamp only keeps a disagreeing device array inside the allocation)
+  int kv_len_ = p.kv_len;
+  if constexpr (VARLEN) {
+    static_assert(RES && EXACT, "per-sample key counts: resident-K/V kernel with the padding promise only");
+    const int cap = p.kv_pad < RES_MAX_TILES * 64 ? p.kv_pad : RES_MAX_TILES * 64;
+    const int n = __builtin_amdgcn_readfirstlane(p.kv_lens[b]);
+    kv_len_ = n < 1 ? 1 : (n > cap ? cap : n);
+  }
+  const int kv_len = kv_len_;
 
   // ---- K/V staging by LDS-DMA: 9 K pieces (1 KiB each, the tile is contiguous) + 10 Vt pieces (8 rows x 128 B each,
   // rows 0..79; rows 80..95 of the LDS image are zeroed once and never overwritten); wave w issues pieces w, w+4, ...
@@ -231,7 +255,7 @@ __global__ __launch_bounds__(RES ? 512 : 256, RES ? 2 : WPS) void flash_attn_d72
   };
   // the first K/V tile is requested BEFORE the Q rows: both round trips are in flight together (with 300 text keys a workgroup
   // lives for five tiles only, so a serialized prologue is a tenth of it)
-  const int ntiles = (p.kv_len + 63) / 64;  // tiles made only of keys >= kv_len are never touched (kv_pad is the stride)
+  const int ntiles = (kv_len + 63) / 64;  // tiles made only of keys >= kv_len are never touched (kv_pad is the stride)
   if constexpr (RES) {
     for (int t = 0; t < ntiles; ++t) stage(t, t);   // every tile of this (batch, head), once
     for (int q = tid; q < ntiles * 128; q += 512)
@@ -383,7 +407,7 @@ __global__ __launch_bounds__(RES ? 512 : 256, RES ? 2 : WPS) void flash_attn_d72
 
     // ---- online softmax (lane: query l31; keys 64t + 32kt + 16hi + r).  Only the last tile of a ragged kv_len masks.
     if (masked) {
-      const int lim = p.kv_len - (t * 64 + 16 * hi);  // keys with 32kt + r >= lim are padding
+      const int lim = kv_len - (t * 64 + 16 * hi);  // keys with 32kt + r >= lim are padding
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -468,7 +492,7 @@ __global__ __launch_bounds__(RES ? 512 : 256, RES ? 2 : WPS) void flash_attn_d72
     const int qb0 = (int)((int64_t)qb * nqb / p.chunks), qb1 = (int)((int64_t)(qb + 1) * nqb / p.chunks);
     // (The mask of a ragged last tile stays: kv_len may be SHORTER than what the K / Vt buffers were prepared for — Latte's per-sample
     // text lengths inside one buffer, test_flash_attn_short_key_length_inside_a_longer_buffer — so the keys behind it are not zero.)
-    const bool ragged = !EXACT && (p.kv_len & 63) != 0;
+    const bool ragged = !EXACT && (kv_len & 63) != 0;
     // The Q rows of query block i + 1 travel HBM -> LDS (wave-private 5 KiB image: 32 rows x 144 B, contiguous 16-byte units) by
     // LDS-DMA under the tiles of block i: a register prefetch (20 VGPRs) makes hipcc spill inside tile(), and without a prefetch
     // the global round trip (~2 us) is exposed once per five tiles.
@@ -542,7 +566,7 @@ __global__ __launch_bounds__(RES ? 512 : 256, RES ? 2 : WPS) void flash_attn_d72
         // mask (last ragged tile) and tile max: VALU only, scheduled beside the PV MFMAs of the previous tile
         auto tile_max = [&](int t, f32x16 (&d)[2], const bool masked) -> float {
           if (masked) {   // (wave-uniform, last tile of a ragged kv_len only)
-            const int lim = p.kv_len - (t * 64 + 16 * hi);
+            const int lim = kv_len - (t * 64 + 16 * hi);
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -648,7 +672,7 @@ __global__ __launch_bounds__(RES ? 512 : 256, RES ? 2 : WPS) void flash_attn_d72
         if (__builtin_amdgcn_ballot_w64(!(o[2][4] >= 0x1p-100f)) != 0) {
           asm volatile("; exact-keys guard (cold): masked recompute of this query block" ::: "memory");
           reset_acc();
-          for (int t = 0; t < ntiles; ++t) tile(t, t, t == ntiles - 1 && (p.kv_len & 63) != 0);
+          for (int t = 0; t < ntiles; ++t) tile(t, t, t == ntiles - 1 && (kv_len & 63) != 0);
         }
       }
       store_o();
@@ -667,7 +691,7 @@ __global__ __launch_bounds__(RES ? 512 : 256, RES ? 2 : WPS) void flash_attn_d72
       __syncthreads();                                   // ... and so have everybody else's
       FLASH_STAMP(4);
     }
-    if (p.kv_len & 63) tile(ntiles - 1, (ntiles - 1) & 1, true);
+    if (kv_len & 63) tile(ntiles - 1, (ntiles - 1) & 1, true);
     else tile(ntiles - 1, (ntiles - 1) & 1, false);
 
     if (ABL == 2 && lane == 0 && p.dbg != nullptr) {
@@ -999,8 +1023,30 @@ int launch_attn_prep_kv(const bf16_t* k, int64_t k_stride, const bf16_t* v, int6
   if (batch <= 0 || heads <= 0 || kv_len <= 0) return 0;
   if (kv_pad % 64 != 0 || kv_pad < kv_len || (k_stride % 8) || (v_stride % 8)) return VSYS_ERR_SHAPE;
   dim3 grid(kv_pad / 64, batch * heads);
-  hipLaunchKernelGGL(attn_prep_kv_kernel, grid, dim3(256), 0, stream, k, k_stride, v, v_stride, k_norm_w, kp, vt, heads,
-                     kv_len, kv_pad, eps, 0.11785113019775793f * 1.4426950408889634f /* 72^-0.5 * log2(e) */);
+  hipLaunchKernelGGL(attn_prep_kv_kernel<false>, grid, dim3(256), 0, stream, k, k_stride, v, v_stride, k_norm_w, kp, vt, heads,
+                     kv_len, kv_pad, eps, 0.11785113019775793f * 1.4426950408889634f /* 72^-0.5 * log2(e) */, (const int*)nullptr);
+  return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
+}
+
+// host-side check of per-sample key counts (both varlen entry points): every count in 1 .. kv_pad
+static bool varlen_counts_ok(const int* lens, int batch, int kv_pad) {
+  for (int b = 0; b < batch; ++b)
+    if (lens[b] < 1 || lens[b] > kv_pad) return false;
+  return true;
+}
+
+int launch_attn_prep_kv_varlen(const bf16_t* k, int64_t k_stride, const bf16_t* v, int64_t v_stride, const bf16_t* k_norm_w,
+                               const int* cu_seqlens, const int* cu_seqlens_host, bf16_t* kp, bf16_t* vt, int batch, int heads,
+                               int kv_pad, float eps, hipStream_t stream) {
+  if (batch <= 0 || heads <= 0) return 0;
+  if (kv_pad % 64 != 0 || kv_pad <= 0 || (k_stride % 8) || (v_stride % 8) || cu_seqlens_host[0] < 0) return VSYS_ERR_SHAPE;
+  for (int b = 0; b < batch; ++b) {
+    const int64_t n = (int64_t)cu_seqlens_host[b + 1] - cu_seqlens_host[b];
+    if (n < 1 || n > kv_pad) return VSYS_ERR_SHAPE;
+  }
+  dim3 grid(kv_pad / 64, batch * heads);
+  hipLaunchKernelGGL(attn_prep_kv_kernel<true>, grid, dim3(256), 0, stream, k, k_stride, v, v_stride, k_norm_w, kp, vt, heads, 0,
+                     kv_pad, eps, 0.11785113019775793f * 1.4426950408889634f /* 72^-0.5 * log2(e) */, cu_seqlens);
   return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
 }
 
@@ -1012,6 +1058,7 @@ int launch_flash_attn_d72(const bf16_t* q, int64_t q_stride, const bf16_t* q_nor
   FlashParams p;
   p.q = q; p.q_stride = q_stride; p.q_norm_w = q_norm_w; p.kp = kp; p.vt = vt; p.out = out; p.out_stride = out_stride;
   p.heads = heads; p.q_len = q_len; p.kv_len = kv_len; p.kv_pad = kv_pad; p.eps = eps;
+  p.kv_lens = nullptr;
   p.nqb = (q_len + 127) / 128;
   p.chunks = 1;
   const int64_t nblk = (int64_t)p.nqb * batch * heads;
@@ -1101,6 +1148,47 @@ int launch_flash_attn_d72(const bf16_t* q, int64_t q_stride, const bf16_t* q_nor
     hipLaunchKernelGGL((flash_attn_d72_kernel<0, 3>), grid, dim3(256), lds, stream, p);
   else hipLaunchKernelGGL((flash_attn_d72_kernel<0, 2>), grid, dim3(256), lds, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
+}
+
+// One launch for a batch whose samples have their own key counts (vsys_flash_attn_d72_varlen): the resident-K/V kernel's EXACT form
+// with the count read per workgroup from kv_lens (device).  kv_lens_host (the same numbers) is what this function decides with:
+// validation, and — where the resident kernel does not take the problem — one launch_flash_attn_d72 per sample.
+int launch_flash_attn_d72_varlen(const bf16_t* q, int64_t q_stride, const bf16_t* q_norm_w, const bf16_t* kp, const bf16_t* vt,
+                                 const int* kv_lens, const int* kv_lens_host, bf16_t* out, int64_t out_stride, int batch, int heads,
+                                 int q_len, int kv_pad, float eps, hipStream_t stream) {
+  if (batch <= 0 || heads <= 0 || q_len <= 0) return 0;
+  if (kv_pad % 64 != 0 || kv_pad <= 0 || (q_stride % 8) || (out_stride % 4) || !varlen_counts_ok(kv_lens_host, batch, kv_pad))
+    return VSYS_ERR_SHAPE;
+  int kv_max = 0;
+  for (int b = 0; b < batch; ++b) kv_max = kv_lens_host[b] > kv_max ? kv_lens_host[b] : kv_max;
+  const int g_flash_variant = g_flash_variant_a.load(std::memory_order_relaxed);
+  static const bool exact_ok = [] { const char* e = getenv("VSYS_FLASH_EXACT"); return !(e && e[0] == '0'); }();
+  const bool fits = (int64_t)q_len * q_stride * 2 < 0x7fffffff;   // 32-bit row offsets in the Q staging
+  if ((g_flash_variant == 0 || g_flash_variant == 8) && exact_ok && fits && (kv_max + 63) / 64 <= RES_MAX_TILES) {
+    FlashParams p;
+    p.q = q; p.q_stride = q_stride; p.q_norm_w = q_norm_w; p.kp = kp; p.vt = vt; p.out = out; p.out_stride = out_stride;
+    p.heads = heads; p.q_len = q_len; p.kv_len = 0; p.kv_pad = kv_pad; p.eps = eps;
+    p.kv_lens = kv_lens;
+    p.dbg = nullptr;
+    const int nqb = (q_len + 255) / 256;
+    int chunks = cu_count_this_device() / (batch * heads);
+    chunks = chunks < 1 ? 1 : (chunks > nqb ? nqb : chunks);
+    p.chunks = chunks;
+    p.nqb = nqb;
+    static std::atomic<unsigned long long> attr_seen{0};
+    for (DeviceOnce once(attr_seen); once.todo(); once.done())
+      (void)hipFuncSetAttribute((const void*)flash_attn_d72_kernel<0, 2, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, RES_MAX_TILES * KV_STAGE + 8 * RES_Q_BYTES);
+    hipLaunchKernelGGL((flash_attn_d72_kernel<0, 2, true, true, true>), dim3((unsigned)(chunks * batch * heads)), dim3(512), RES_MAX_TILES * KV_STAGE + 8 * RES_Q_BYTES, stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
+  }
+  // longer text, a forced kernel variant, Q rows past the 32-bit staging offsets: the per-sample launches this entry point replaces
+  for (int b = 0; b < batch; ++b) {
+    const int rc = launch_flash_attn_d72(q + (int64_t)b * q_len * q_stride, q_stride, q_norm_w, kp + (int64_t)b * heads * kv_pad * HD,
+                                         vt + (int64_t)b * heads * HD_ROWS * kv_pad, out + (int64_t)b * q_len * out_stride, out_stride, 1,
+                                         heads, q_len, kv_lens_host[b], kv_pad, eps, 0.f, stream, true);
+    if (rc != 0) return rc;
+  }
+  return 0;
 }
 
 int launch_attn_temporal_d72(const bf16_t* qkv, int64_t row_stride, int C, const bf16_t* q_norm_w, const bf16_t* k_norm_w,

@@ -373,6 +373,24 @@ int vsys_flash_attn_d72_exact(const void* q, int64_t q_stride, const void* q_nor
                                (int)heads, (int)q_len, (int)kv_len, (int)kv_pad, eps, 0.f, S(stream), true);
 }
 
+int vsys_attn_prep_kv_varlen(const void* k, int64_t k_stride, const void* v, int64_t v_stride, const void* k_norm_w,
+                             const int* cu_seqlens, const int* cu_seqlens_host, void* kp, void* vt, int64_t batch, int64_t heads,
+                             int64_t kv_pad, float eps, void* stream) {
+  if (!k || !v || !kp || !vt || !cu_seqlens || !cu_seqlens_host) return VSYS_ERR_ARG;
+  if (!fits_int(batch) || !fits_int(heads) || !fits_int(kv_pad) || batch * heads > 65535) return VSYS_ERR_SHAPE;
+  return launch_attn_prep_kv_varlen(B16(k), k_stride, B16(v), v_stride, B16(k_norm_w), cu_seqlens, cu_seqlens_host, B16(kp), B16(vt),
+                                    (int)batch, (int)heads, (int)kv_pad, eps, S(stream));
+}
+
+int vsys_flash_attn_d72_varlen(const void* q, int64_t q_stride, const void* q_norm_w, const void* kp, const void* vt,
+                               const int* kv_lens, const int* kv_lens_host, void* out, int64_t out_stride, int64_t batch,
+                               int64_t heads, int64_t q_len, int64_t kv_pad, float eps, void* stream) {
+  if (!q || !kp || !vt || !out || !kv_lens || !kv_lens_host) return VSYS_ERR_ARG;
+  if (!fits_int(batch) || !fits_int(heads) || !fits_int(q_len) || !fits_int(kv_pad) || batch * heads > 65535) return VSYS_ERR_SHAPE;
+  return launch_flash_attn_d72_varlen(B16(q), q_stride, B16(q_norm_w), B16(kp), B16(vt), kv_lens, kv_lens_host, B16(out), out_stride,
+                                      (int)batch, (int)heads, (int)q_len, (int)kv_pad, eps, S(stream));
+}
+
 int vsys_flash_attn_d72_kb(const void* q, int64_t q_stride, const void* q_norm_w, const void* kp, const void* vt, void* out,
                            int64_t out_stride, int64_t batch, int64_t heads, int64_t q_len, int64_t kv_len, int64_t kv_pad,
                            float eps, float k_norm_bound, void* stream) {

@@ -202,6 +202,14 @@ int launch_flash_attn_d72(const bf16_t* q, int64_t q_stride, const bf16_t* q_nor
                           bf16_t* out, int64_t out_stride, int batch, int heads, int q_len, int kv_len, int kv_pad,
                           float eps, float k_bound, hipStream_t stream,    // k_bound: see FlashW64Params::k_bound (0 = none)
                           bool keys_exact = false);   // the caller's promise of vsys_flash_attn_d72_exact (attention.hip, EXACT)
+// per-sample key counts in one launch (packed text, vsys_attn_prep_kv_varlen / vsys_flash_attn_d72_varlen): the device arrays are what
+// the kernels read, the host copies of the same numbers are what the launchers validate (and fall back) with
+int launch_attn_prep_kv_varlen(const bf16_t* k, int64_t k_stride, const bf16_t* v, int64_t v_stride, const bf16_t* k_norm_w,
+                               const int* cu_seqlens, const int* cu_seqlens_host, bf16_t* kp, bf16_t* vt, int batch, int heads,
+                               int kv_pad, float eps, hipStream_t stream);
+int launch_flash_attn_d72_varlen(const bf16_t* q, int64_t q_stride, const bf16_t* q_norm_w, const bf16_t* kp, const bf16_t* vt,
+                                 const int* kv_lens, const int* kv_lens_host, bf16_t* out, int64_t out_stride, int batch, int heads,
+                                 int q_len, int kv_pad, float eps, hipStream_t stream);
 // 64 query rows per wave, one wave per SIMD, hand-allocated tile loop (attention_w64.hip); same contract as launch_flash_attn_d72
 bool flash_w64_supports(int q_len, int kv_len, int kv_pad);
 int launch_flash_attn_d72_w64(const bf16_t* q, int64_t q_stride, const bf16_t* q_norm_w, const bf16_t* kp, const bf16_t* vt, bf16_t* out,

@@ -418,6 +418,58 @@ def flash_attn(q, q_norm_w, kp, vt, out, batch, heads, q_len, kv_len, eps=1e-6, 
     return out
 
 
+class VarlenKeys:
+    """Per-sample key counts of a packed text batch, in the two forms the varlen entry points take: device int32 tensors
+    (``cu_seqlens`` [batch + 1], ``kv_lens`` [batch]: what the kernels read) and host ctypes arrays of the same numbers (what the C
+    entry points validate and pick the kernel with).  Build it once per prompt batch; it owns both copies."""
+
+    def __init__(self, lens, device):
+        import ctypes
+
+        self.lens = tuple(int(n) for n in lens)
+        cu = [0]
+        for n in self.lens:
+            cu.append(cu[-1] + n)
+        self.batch = len(self.lens)
+        self.total = cu[-1]
+        self.max_len = max(self.lens) if self.lens else 0
+        self.cu_host = (ctypes.c_int32 * len(cu))(*cu)
+        self.lens_host = (ctypes.c_int32 * max(self.batch, 1))(*self.lens)
+        self.cu_seqlens = torch.tensor(cu, dtype=torch.int32, device=device)
+        self.kv_lens = torch.tensor(list(self.lens), dtype=torch.int32, device=device)
+
+
+def attn_prep_kv_varlen(k, v, k_norm_w, keys: VarlenKeys, kp, vt, heads, eps=1e-6):
+    """attn_prep_kv for PACKED rows: k, v are 2-D row-strided views [sum(lens), >= heads*72]; sample b's ``keys.lens[b]`` rows go to
+    kp[b] / vt[b] exactly as attn_prep_kv writes them for kv_len = lens[b] (one launch for the batch).  A count < 1 or > kv_pad is
+    rejected by the entry point (unsupported shape) before anything is launched."""
+    _chk(k, v, k_norm_w, kp, vt, keys.cu_seqlens)
+    _bf16(k, v, k_norm_w, kp, vt)
+    assert k.stride(1) == 1 and v.stride(1) == 1 and kp.is_contiguous() and vt.is_contiguous()
+    kv_pad = kp.shape[2]
+    assert vt.shape[3] == kv_pad and vt.shape[2] == VT_ROWS and kp.shape[0] == keys.batch and vt.shape[0] == keys.batch
+    assert kp.shape[1] == heads and vt.shape[1] == heads
+    assert k.shape[0] >= keys.total and v.shape[0] >= keys.total, "packed k / v hold fewer rows than sum(lens)"
+    _call("vsys_attn_prep_kv_varlen", _p(k), k.stride(0), _p(v), v.stride(0), _p(k_norm_w), _p(keys.cu_seqlens), keys.cu_host,
+          _p(kp), _p(vt), keys.batch, heads, kv_pad, eps)
+
+
+def flash_attn_varlen(q, q_norm_w, kp, vt, keys: VarlenKeys, out, heads, q_len, eps=1e-6):
+    """flash_attn(..., keys_exact=True) for a batch whose sample b attends to its own ``keys.lens[b]`` keys (kp, vt prepared by
+    attn_prep_kv_varlen for exactly these counts on zeroed buffers): one launch, the count is read on the device."""
+    _chk(q, q_norm_w, kp, vt, out, keys.kv_lens)
+    _bf16(q, q_norm_w, kp, vt, out)
+    assert q.stride(1) == 1 and out.stride(1) == 1
+    kv_pad = kp.shape[2]
+    assert kp.shape[0] == keys.batch and vt.shape[0] == keys.batch and kp.shape[1] == heads and vt.shape[3] == kv_pad
+    assert q.shape[0] >= keys.batch * q_len and out.shape[0] >= keys.batch * q_len
+    if program.active() is not None:
+        program.keep(keys)       # a recorded launch reads the host counts again at every replay
+    _call("vsys_flash_attn_d72_varlen", _p(q), q.stride(0), _p(q_norm_w), _p(kp), _p(vt), _p(keys.kv_lens), keys.lens_host, _p(out),
+          out.stride(0), keys.batch, heads, q_len, kv_pad, eps)
+    return out
+
+
 def rms_key_bound(q_norm_w, k_norm_w, head_dim=HEAD_DIM):
     """The k_norm_bound of flash_attn for RMS-normed q and k (LlamaRMSNorm, normalization.py:28-33: x / rms(x) has norm sqrt(d), then
     the weight elementwise), or None when the promise |q_i| k_norm_bound <= 60 cannot be given from the weights alone.  Host-side,

@@ -297,6 +297,11 @@ class OpenSoraPipeline(VideoSysPipeline):
         ``height=`` / ``width=`` override it — an extension, needed because the reference's own tables cannot name 512x512
         (("512", "1:1") fails its assert).  ``prompt_embeds`` / ``prompt_mask`` bypass the text encoder.
 
+        ``prompt`` may be a list: ``video[i]`` belongs to ``prompt[i]`` (per-prompt ``refs`` / ``ms`` lists likewise).  The prompts
+        need not tokenise to the same count: a ragged batch runs the reference's varlen cross-attention (attentions.py:240-258),
+        every sample attending to exactly its own tokens — one launch per block as for equal lengths, at the cost of one more
+        int32 read per workgroup (its key count comes from device memory).  Equal lengths take the fixed-length kernels unchanged.
+
         Image / video conditioning (:528-535,607-645): ``refs`` names the reference clips of the prompt (';'-separated image
         paths as in the reference, or a list of paths / pixel tensors [3, T, H, W] in [-1, 1] / latents [4, T, h, w]), ``ms`` the
         mask strategy that pastes their latent frames into the start noise (open_sora_condition.py); both may also arrive as a

@@ -111,6 +111,49 @@ class _BlockState:
         self.last_cross: Optional[torch.Tensor] = None
 
 
+
+def text_lengths(mask=None, batch=None, y_lens=None, packed_rows=None):
+    """Per-sample text lengths of a prompt batch and their running offsets: ``(y_lens, cu_seqlens)`` as lists of ints, with
+    ``cu_seqlens[b]`` the first row of sample b in the packed text and ``cu_seqlens[-1] == sum(y_lens)`` — the two arguments of the
+    reference's varlen cross-attention (modules/attentions.py:240-258; the packing is open_sora_transformer_3d.py:526-537).  Pure
+    host code.  Either form of STDiT3.forward's text inputs:
+
+    * ``mask`` [Bm, L] (nested lists or a tensor; nonzero = token): the tokenizer's padding mask.  ``batch`` > Bm repeats it, as
+      the sampler hands ONE mask over for the cond and null halves of a CFG batch.  Every row must be a PREFIX of ones (the packed
+      rows of a sample are then its first y_lens[b] tokens) with at least one token.
+    * ``y_lens`` (skip_y_embedder: the text is already packed): the counts themselves, each >= 1; ``packed_rows``, when given, must
+      equal their sum.
+    Raises ValueError otherwise."""
+    if (mask is None) == (y_lens is None):
+        raise ValueError("text_lengths takes a mask or a list of lengths")
+    if mask is not None:
+        rows = mask.tolist() if hasattr(mask, "tolist") else [list(r) for r in mask]
+        if not rows or not isinstance(rows[0], (list, tuple)):
+            raise ValueError("mask must be 2-D [samples, tokens]")
+        if batch is not None and batch != len(rows):
+            if batch <= 0 or batch % len(rows):
+                raise ValueError(f"a mask of {len(rows)} rows cannot be repeated over a batch of {batch}")
+            rows = rows * (batch // len(rows))
+        lens = []
+        for b, r in enumerate(rows):
+            n = sum(1 for v in r if v)
+            if any(not v for v in r[:n]):
+                raise ValueError(f"text mask of sample {b} is not a prefix of ones")
+            lens.append(n)
+    else:
+        lens = [int(v) for v in y_lens]
+        if batch is not None and batch != len(lens):
+            raise ValueError(f"{len(lens)} text lengths for a batch of {batch}")
+    if not lens or any(n < 1 for n in lens):
+        raise ValueError(f"every sample needs at least one text token, got lengths {lens}")
+    cu = [0]
+    for n in lens:
+        cu.append(cu[-1] + n)
+    if packed_rows is not None and int(packed_rows) != cu[-1]:
+        raise ValueError(f"y holds {int(packed_rows)} tokens, y_lens sum to {cu[-1]}")
+    return lens, cu
+
+
 class STDiT3:
     """Drop-in for the reference STDiT3 at the operator boundary ``model(z_in, t, **model_args)``."""
 
@@ -328,10 +371,10 @@ class STDiT3:
             if mask is None:
                 raise ValueError("skip_y_embedder=True needs the per-sample text lengths in ``mask``")
             y_lens = [int(v) for v in mask.reshape(-1).tolist()]
-            if len(set(y_lens)) != 1:
-                raise ValueError("cross-attention needs equal text lengths per sample (as the reference's torch_impl view does)")
             B = len(y_lens)
             yp = y.to(device=self.device, dtype=self.dtype).reshape(-1, C).contiguous()
+            if len(set(y_lens)) != 1:   # a ragged batch (attentions.py:240-258): every sample its own, non-empty, run of packed rows
+                text_lengths(y_lens=y_lens, packed_rows=yp.shape[0])
             if yp.shape[0] != sum(y_lens):
                 raise ValueError(f"y holds {yp.shape[0]} tokens, y_lens sum to {sum(y_lens)}")
             return self._text_kv(y, mask, yp, y_lens, B, lens_key=tuple(y_lens))
@@ -345,8 +388,8 @@ class STDiT3:
                 m = m.repeat(B // m.shape[0], 1)
             m = m.reshape(B, L)
             y_lens = [int(v) for v in m.sum(dim=1).tolist()]
-            if len(set(y_lens)) != 1:
-                raise ValueError("cross-attention needs equal text lengths per sample (as the reference's torch_impl view does)")
+            if len(set(y_lens)) != 1:   # a ragged batch: the packed rows of a sample must be its first y_lens[b] tokens
+                y_lens, _ = text_lengths(mask=(m != 0).to("cpu"))
             idx = torch.nonzero(m.reshape(-1) != 0, as_tuple=False).reshape(-1).to(self.device)
             yp = ye.reshape(B * L, C).index_select(0, idx).contiguous()  # masked_select packing
         else:
@@ -357,21 +400,34 @@ class STDiT3:
     def _text_kv(self, y, mask, yp, y_lens, B, lens_key=None):
         """Every block's kv_linear(y) and its attention layouts from the packed text tokens yp [B * Lk, C]; fills the cache."""
         w, C, H = self.w, self.hidden_size, self.num_heads
-        Lk = y_lens[0]
+        # equal lengths: sample b's keys are rows b * Lk ...; a ragged batch (the reference's varlen path, attentions.py:240-258):
+        # sample b's y_lens[b] keys start at sum(y_lens[:b]) and the counts travel to the kernels in device memory
+        ragged = len(set(y_lens)) != 1
+        if ragged and self.device.type != "cuda":
+            # the varlen kernels read the key counts from HIP device memory and there is no other implementation of the ragged path
+            raise ValueError(f"text lengths {list(y_lens)} differ per sample: a ragged batch needs the model on a HIP device "
+                             f"(this one is on {self.device}); off the device cross-attention takes equal text lengths only")
+        keys = ops.VarlenKeys(y_lens, self.device) if ragged else None
+        Lk = y_lens[0] if keys is None else keys.max_len
+        if keys is not None and lens_key is None:
+            lens_key = keys.lens
         nblk = 2 * self.depth
         kv_pad = ops.kv_pad_len(Lk)
         kps = torch.zeros(nblk, B, H, kv_pad, ops.HEAD_DIM, dtype=self.dtype, device=self.device)
         vts = torch.zeros(nblk, B, H, ops.VT_ROWS, kv_pad, dtype=self.dtype, device=self.device)
-        kv = torch.empty(B * Lk, 2 * C, dtype=self.dtype, device=self.device)
+        kv = torch.empty(sum(y_lens), 2 * C, dtype=self.dtype, device=self.device)
         for i in range(nblk):
             p = self.block_prefix(i) + ".cross_attn.kv_linear"
             if (2 * C) % 192 == 0 and C % 64 == 0:
                 ops.gemm(yp, w[p + ".weight"], w[p + ".bias"], out=kv)
             else:
                 ops.linear_small(yp, w[p + ".weight"], w[p + ".bias"], out=kv)
-            ops.attn_prep_kv(kv[:, :C], kv[:, C:], None, kps[i], vts[i], B, H, Lk)
+            if keys is None:
+                ops.attn_prep_kv(kv[:, :C], kv[:, C:], None, kps[i], vts[i], B, H, Lk)
+            else:
+                ops.attn_prep_kv_varlen(kv[:, :C], kv[:, C:], None, keys, kps[i], vts[i], H)
         self._text_cache = dict(y=y, y_version=y._version, mask=mask, mask_version=None if mask is None else mask._version,
-                                y_lens=y_lens, kp=kps, vt=vts, Lk=Lk, lens_key=lens_key)
+                                y_lens=y_lens, kp=kps, vt=vts, Lk=Lk, lens_key=lens_key, varlen=keys)
         return self._text_cache
 
     # ------------------------------------------------------------------ AdaLN fold
@@ -434,6 +490,12 @@ class STDiT3:
             Bl = Bfull // cp
             sl = slice(pm.cp_rank * Bl, (pm.cp_rank + 1) * Bl)
             rows = lambda v: v[sl] if (torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == Bfull) else v
+            if bool(getattr(self.config, "skip_y_embedder", False)) and mask is not None and y.shape[0] != Bfull:
+                # packed text [1, sum(y_lens), C] + per-sample lengths: this rank's samples are a run of packed rows (cu_seqlens)
+                lens_all = [int(v) for v in (mask.reshape(-1).tolist() if torch.is_tensor(mask) else mask)]
+                _, cu = text_lengths(y_lens=lens_all, batch=Bfull, packed_rows=y.reshape(-1, y.shape[-1]).shape[0])
+                y = y.reshape(-1, y.shape[-1])[cu[sl.start]:cu[sl.stop]].unsqueeze(0)
+                mask = lens_all[sl]
             x, timestep, y, fps, height, width, mask, x_mask = (rows(v) for v in (x, timestep, y, fps, height, width, mask, x_mask))
         B, _, Tx, Hx, Wx = x.shape
         T, Hp, Wp = self.get_dynamic_size(x)
@@ -487,6 +549,7 @@ class STDiT3:
             sp = self._sp
             key = (B, Tx, Hx, Wx, float(height[0]), float(width[0]), fkey, valid_depth, cp, fold, self.fold_spatial_qkv,
                    None if plan is None else tuple(d[:2] + d[5:7] for d in plan),
+                   None if static[0]["varlen"] is None else static[0]["varlen"].lens,   # a ragged batch: its per-sample text lengths
                    None if sp is None else (sp.P, sp.rank, self._scatter, self._switch, self._overlap))
             ent = self._programs.get(key)
             if ent is not None:       # replay: refresh the two per-step inputs, ONE C call per launch segment
@@ -781,7 +844,10 @@ class STDiT3:
             q = ops.gemm(x, w[p + ".cross_attn.q_linear.weight"], w[p + ".cross_attn.q_linear.bias"], out=_buf("xm", (N, C)))
             ao = _buf("attn_out", (N, C))
             # (the hoisted text K / V were prepared for exactly Lk keys on zeroed buffers, _text_kv: the padding promise holds)
-            ops.flash_attn(q, None, txt["kp"][i], txt["vt"][i], ao, B, H, T * S, txt["Lk"], keys_exact=True)
+            if txt["varlen"] is None:
+                ops.flash_attn(q, None, txt["kp"][i], txt["vt"][i], ao, B, H, T * S, txt["Lk"], keys_exact=True)
+            else:   # ragged batch: sample b attends to its own y_lens[b] keys, the counts are read on the device (one launch)
+                ops.flash_attn_varlen(q, None, txt["kp"][i], txt["vt"][i], txt["varlen"], ao, H, T * S)
             aux = None
             if use_pab and keep_cross:
                 st.last_cross = slab(st.last_cross)
