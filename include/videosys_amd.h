@@ -89,6 +89,24 @@ int vsys_gemm_bf16(const void* x, int64_t ldx, const void* w, int64_t ldw, const
 int vsys_gemm_bf16_ln(const void* x, int64_t ldx, const void* wp, int64_t ldw, const void* cs, const void* cv, void* out, int64_t ldo,
                       int64_t M, int64_t N, int64_t K, int epilogue, const void* stats, int64_t stats_ld, float eps, void* stream);
 
+/* vsys_gemm_bf16_ln (VSYS_EPI_BIAS) of the SPATIAL qkv site followed by vsys_attn_prep_kv, in one launch: the K and V thirds of the
+ * qkv rows never reach memory as rows, the GEMM's epilogue writes the Kp / Vt layouts itself (the k half of the qk-norm and the
+ * softmax scale as vsys_attn_prep_kv applies them, attentions.py:59,75 + normalization.py:28-33; same bits).  N = 216 heads output
+ * columns (a head = 72) in the K/V COLUMN ORDER: windows of 96 columns, 3 heads / 4 windows of Q in the checkpoint's order, then one
+ * window per head h with its 72 K features followed by V features 24 h .. 24 h + 23 (V features counted h_v * 72 + d), then the
+ * remaining V features 96 to a window.  wp, cs, cv must be in that order: vsys_adaln_prescale writes them so for a site whose N word
+ * carries ``heads`` in its upper half.  Row m is key m % S of sample m / S.  Outputs: q[m][0 .. 72 heads) with leading dimension ldq
+ * (what vsys_gemm_bf16_ln stores in its first third), kp [M / S][heads][S][72], vt [M / S][heads][96][S] rows 0-71.  vt rows 72-95 are
+ * NOT written: with every key valid they are constants (rows 72 and 76 = 1.0, the rest 0) that the caller sets once.  heads % 8 == 0,
+ * S % 64 == 0, M % S == 0, K % 96 == 0, K <= 1152, k_norm_w [72] required and 16-byte aligned; eps: LayerNorm, k_eps: the RMS norm;
+ * anything else VSYS_ERR_SHAPE / _ARG / _ALIGN.  Always the two-workgroup 16x16x32 tile kernel. */
+int vsys_gemm_bf16_ln_qkv_kv(const void* x, int64_t ldx, const void* wp, int64_t ldw, const void* cs, const void* cv, const void* stats,
+                             int64_t stats_ld, const void* k_norm_w, void* q, int64_t ldq, void* kp, void* vt, int64_t M, int64_t K,
+                             int64_t S, int64_t heads, float eps, float k_eps, void* stream);
+/* 1 when vsys_gemm_bf16_ln at [M, K] x [N, K] runs on that same kernel (so that the fused form replaces a launch of it and not of
+ * another tile shape the dispatch prefers there), else 0.  Host-side, no launch; no reference counterpart. */
+int vsys_gemm_bf16_ln_qkv_kv_dispatched(int64_t M, int64_t N, int64_t K);
+
 /* vsys_gemm_bf16 with VSYS_EPI_GATE_RES (out = res + gate (x W^T + b): attentions.py:107 / :183 / timm Mlp fc2 + the residual adds
  * of open_sora_transformer_3d.py:228,240,284) that ALSO emits the LayerNorm partials of the rows it stores — what the next block's
  * norm1 / norm2 (open_sora_transformer_3d.py:116-117,196,260) would compute from them: float2 stats[b * stats_ld + m] = (mean, M2)
@@ -113,7 +131,8 @@ int vsys_gemm_bf16_gate_res_add(const void* x, int64_t ldx, const void* w, int64
  * table (t2i_modulate operands, open_sora_transformer_3d.py:177-179; valid when every sample of the batch shares the timestep, as
  * the CFG pair of scheduling_rflow_open_sora.py:239-244 does).  ``sites``: DEVICE array of nsites x 10 int64: W, bias, W', cs, cv
  * (addresses), shift_off, scale_off (element offsets into ``mod``), N, K, first block of the site; 4 weight rows per block,
- * nblocks = sum ceil(N / 4). */
+ * nblocks = sum ceil(N / 4).  N word: bits 0-31 = N; bits 32 and up = 0, or ``heads`` of a spatial qkv site (N = 216 heads) whose
+ * W', cs, cv are to be written in the K/V column order of vsys_gemm_bf16_ln_qkv_kv (row n at its column; same values). */
 int vsys_adaln_prescale(const void* sites, int64_t nsites, int64_t nblocks, const void* mod, void* stream);
 
 /* LayerNorm partials (format of vsys_gemm_bf16_ln) of a [rows, C] bf16 tensor no GEMM epilogue produced: the patch embedding
@@ -538,7 +557,8 @@ int vsys_softmax_rows(const void* s_f32, void* p, int64_t rows, int64_t n, int64
 #define VSYS_OP_SOFTMAX_ROWS                 54
 #define VSYS_OP_ATTN_PREP_KV_VARLEN          55
 #define VSYS_OP_FLASH_ATTN_D72_VARLEN        56
-#define VSYS_OP_COUNT 57
+#define VSYS_OP_GEMM_BF16_LN_QKV_KV          57
+#define VSYS_OP_COUNT 58
 /* <<< VSYS_OP codes */
 
 #define VSYS_CMD_MAX_INT 24

@@ -24,6 +24,9 @@ SIGNATURES = {
     "vsys_gemm_bf16": [_ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _ptr, _i64, _i64, _ptr, _i64,
                        _ptr, _i64, _ptr],
     "vsys_gemm_bf16_ln": [_ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _ptr, _i64, _f32, _ptr],
+    "vsys_gemm_bf16_ln_qkv_kv": [_ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _f32, _f32,
+                                 _ptr],
+    "vsys_gemm_bf16_ln_qkv_kv_dispatched": [_i64, _i64, _i64],   # host-side query (no stream)
     "vsys_gemm_bf16_stats": [_ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr],
     "vsys_gemm_bf16_gate_res_add": [_ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _i64, _i64, _ptr, _i64, _ptr, _ptr,
                                     _ptr, _ptr, _i64, _ptr],

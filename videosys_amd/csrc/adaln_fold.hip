@@ -21,7 +21,10 @@ namespace vsys {
 namespace {
 
 // one site = 10 int64: W, bias, Wp, cs, cv (device addresses), shift_off, scale_off (element offsets into the modulation
-// table handed to the launch), N, K, blk0 (first block of the site in the launch's 1-D grid; 4 rows per block)
+// table handed to the launch), N, K, blk0 (first block of the site in the launch's 1-D grid; 4 rows per block).
+// Column order: bits 32 and up of the N word hold ``heads`` of a spatial qkv site whose GEMM runs in the K/V column order
+// (vsys_internal.h qkv_kv_column; N = 216 heads): row n of W', cs[n], cv[n] are then written at position qkv_kv_column(n, heads) —
+// same values, other places.  0 = the checkpoint's order.
 constexpr int SITE_WORDS = 10;
 
 __global__ __launch_bounds__(256) void adaln_prescale_kernel(const int64_t* __restrict__ sites, int nsites,
@@ -41,11 +44,12 @@ __global__ __launch_bounds__(256) void adaln_prescale_kernel(const int64_t* __re
   float* cv = reinterpret_cast<float*>(s[4]);
   const bf16_t* shift = mod + s[5];
   const bf16_t* scale = mod + s[6];
-  const int N = (int)s[7], K = (int)s[8];
+  const int N = (int)(s[7] & 0xffffffff), kv_heads = (int)(s[7] >> 32), K = (int)s[8];
   const int n = ((int)blockIdx.x - (int)s[9]) * 4 + wave;
   if (n >= N) return;
+  const int nd = (kv_heads > 0 && N == 216 * kv_heads && kv_heads % 4 == 0) ? qkv_kv_column(n, kv_heads) : n;   // where this output feature sits among the GEMM's columns
   const bf16_t* wr = W + (int64_t)n * K;
-  bf16_t* wo = Wp + (int64_t)n * K;
+  bf16_t* wo = Wp + (int64_t)nd * K;
   float a_cs = 0.f, a_cv = 0.f;
   for (int c = lane; c < (K >> 3); c += 64) {
     float w[8], sc[8], sh[8], o[8];
@@ -67,8 +71,8 @@ __global__ __launch_bounds__(256) void adaln_prescale_kernel(const int64_t* __re
   a_cs = wave_sum(a_cs);
   a_cv = wave_sum(a_cv);
   if (lane == 0) {
-    cs[n] = a_cs;
-    cv[n] = a_cv + (bias != nullptr ? bf2f(bias[n]) : 0.f);
+    cs[nd] = a_cs;
+    cv[nd] = a_cv + (bias != nullptr ? bf2f(bias[n]) : 0.f);
   }
 }
 

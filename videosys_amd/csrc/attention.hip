@@ -89,23 +89,16 @@ __global__ __launch_bounds__(256) void attn_prep_kv_kernel(const bf16_t* __restr
 #pragma unroll
       for (int c = 0; c < 3; ++c) unpack8(*reinterpret_cast<const uint4*>(src + c * 8), x + c * 8);
     }
+    // (common.h KNorm72: the same three steps as the K/V epilogue of the spatial qkv GEMM.)  The softmax scale 72^-1/2 and log2(e)
+    // ride on K (one rounding, the one the reference's k also gets), so that the QK^T accumulators are exp2-ready and the flash
+    // kernel spends no VALU on scaling
+    float rstd = 0.f;
     if (k_norm_w != nullptr) {
-      float ss = 0.f;
-#pragma unroll
-      for (int e = 0; e < 24; ++e) ss += x[e] * x[e];
+      const float ss = KNorm72::sumsq(x);
       const int base = g * 3;
-      const float tot = __shfl(ss, base, 64) + __shfl(ss, base + 1, 64) + __shfl(ss, base + 2, 64);
-      const float rstd = rsqrtf(tot / (float)HD + eps);
-#pragma unroll
-      for (int e = 0; e < 24; ++e) {
-        const float nrm = bf2f(f2bf(x[e] * rstd));  // hidden_states.to(input_dtype) before the weight multiply
-        x[e] = nrm * bf2f(k_norm_w[part * 24 + e]);
-      }
+      rstd = KNorm72::rstd(__shfl(ss, base, 64), __shfl(ss, base + 1, 64), __shfl(ss, base + 2, 64), eps);
     }
-    // softmax scale 72^-1/2 and log2(e) ride on K (one rounding, the one the reference's k also gets), so that the
-    // QK^T accumulators are exp2-ready and the flash kernel spends no VALU on scaling
-#pragma unroll
-    for (int e = 0; e < 24; ++e) x[e] *= kscale;
+    KNorm72::apply(x, rstd, k_norm_w != nullptr ? k_norm_w + part * 24 : nullptr, kscale);
     if (active) {
       bf16_t* dst = kp + (((int64_t)bh * kv_pad) + s) * HD + part * 24;
 #pragma unroll

@@ -96,6 +96,26 @@ int vsys_gemm_bf16_ln(const void* x, int64_t ldx, const void* wp, int64_t ldw, c
   return launch_gemm(p, epilogue == VSYS_EPI_BIAS ? EPI_LN_BIAS : EPI_LN_GELU, S(stream));
 }
 
+int vsys_gemm_bf16_ln_qkv_kv(const void* x, int64_t ldx, const void* wp, int64_t ldw, const void* cs, const void* cv, const void* stats,
+                             int64_t stats_ld, const void* k_norm_w, void* q, int64_t ldq, void* kp, void* vt, int64_t M, int64_t K,
+                             int64_t S_, int64_t heads, float eps, float k_eps, void* stream) {
+  if (!x || !wp || !cs || !cv || !stats || !k_norm_w || !q || !kp || !vt) return VSYS_ERR_ARG;
+  if (!fits_int(M) || !fits_int(K) || !fits_int(S_) || heads <= 0 || heads > 4096) return VSYS_ERR_SHAPE;
+  if (K % LN_BLOCK != 0 || K / LN_BLOCK > 12) return VSYS_ERR_SHAPE;
+  GemmParams p;
+  p.A = B16(x); p.lda = ldx; p.W = B16(wp); p.ldw = ldw; p.bias = nullptr; p.out = B16(q); p.ldo = ldq;
+  p.M = (int)M; p.N = (int)(216 * heads); p.K = (int)K;
+  p.gate = nullptr; p.gate_stride = 0; p.res = nullptr; p.ldr = 0; p.aux = nullptr; p.ldaux = 0; p.rows_per_sample = 0;
+  p.seg_split = 0; p.gate_alt = 0; p.ks = 0; p.out32 = nullptr; p.slab = 0; p.ldo32 = 0;
+  p.cs = reinterpret_cast<const float*>(cs); p.cv = reinterpret_cast<const float*>(cv);
+  p.ln_stats = reinterpret_cast<const float2*>(stats); p.ln_ld = stats_ld; p.ln_nb = (int)(K / LN_BLOCK); p.ln_eps = eps;
+  p.kp = B16(kp); p.vt = B16(vt); p.k_norm_w = B16(k_norm_w); p.kv_S = (int)S_; p.kv_heads = (int)heads; p.k_eps = k_eps;
+  p.kscale = 0.11785113019775793f * 1.4426950408889634f;   /* 72^-0.5 * log2(e), as launch_attn_prep_kv */
+  return launch_gemm_qkv_kv(p, S(stream));
+}
+
+int vsys_gemm_bf16_ln_qkv_kv_dispatched(int64_t M, int64_t N, int64_t K) { return gemm_ln_qkv_kv_dispatched(M, N, K) ? 1 : 0; }
+
 int vsys_gemm_bf16_stats(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* out, int64_t ldo, int64_t M,
                          int64_t N, int64_t K, const void* gate, int64_t gate_sample_stride, int64_t rows_per_sample, const void* res,
                          int64_t ldr, void* stats, int64_t stats_ld, void* stream) {

@@ -53,6 +53,35 @@ __device__ __forceinline__ float gelu_tanh(float x) {
 }
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + __expf(-x)); }
 
+// ---- k half of the qk-norm of a 72-wide head (LlamaRMSNorm, normalization.py:28-33) + the softmax scale that rides on K, in
+// thirds of 24 dims: sumsq() of each third, rstd() of the three sums in the order 0, 1, 2, apply() on each third.  attn_prep_kv_kernel
+// (three lanes per row, the sums meet by shuffle) and the K/V epilogue of gemm2_kernel (one lane per row, the thirds in turn) both go
+// through these three steps and nothing else, so both contract and round alike: the same k row gives the same Kp bits from either.
+struct KNorm72 {
+  static __device__ __forceinline__ float sumsq(const float* x) {
+    float ss = 0.f;
+#pragma unroll
+    for (int e = 0; e < 24; ++e) ss += x[e] * x[e];
+    return ss;
+  }
+  static __device__ __forceinline__ float rstd(float ss0, float ss1, float ss2, float eps) {
+    const float tot = ss0 + ss1 + ss2;
+    return rsqrtf(tot / 72.0f + eps);
+  }
+  // w24: the 24 norm weights of this third (null = no norm: the scale alone)
+  static __device__ __forceinline__ void apply(float* x, float rstd_, const bf16_t* w24, float kscale) {
+    if (w24 != nullptr) {
+#pragma unroll
+      for (int e = 0; e < 24; ++e) {
+        const float nrm = bf2f(f2bf(x[e] * rstd_));  // hidden_states.to(input_dtype) before the weight multiply
+        x[e] = nrm * bf2f(w24[e]);
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 24; ++e) x[e] *= kscale;
+  }
+};
+
 // ---- AdaLN fold: LayerNorm statistics as per-96-column partials (mean_b, M2_b) at st[b * ld + row] (vsys_internal.h GemmParams).
 // (mu, rstd) of one row from its nb <= 12 partials.  Chan's combination around the first block's mean: no E[x^2] - mu^2 form
 // anywhere, so a row mean that is many sigma away from zero costs nothing.

@@ -43,6 +43,8 @@ struct G2 {
   static constexpr int LDS_BYTES = STAGING > NW * OUT_WAVE_BYTES ? STAGING : NW * OUT_WAVE_BYTES;  // 73728 or 106496
   // EPI_LN_*: (mu, rstd) of the tile's 256 rows + (cs, cv) of its columns behind the staging area (common.h ln_stage_tile)
   static constexpr int LN_BYTES = (BM + BN) * 8;
+  // EPI_LN_QKV_KV: the 72 k-norm weights behind that
+  static constexpr int KW_BYTES = 160;
 };
 
 // STAMP = 1 (lab, variant 31): s_memtime stamps around the four phases of every stage (fragment reads landed / MFMA block issued /
@@ -66,6 +68,7 @@ __global__ __launch_bounds__(G2<NWN>::NT, 2) void gemm2_kernel(GemmParams p) {
   const int l31 = lane & 31, hi = lane >> 5;
   const int l15 = lane & 15, lq = lane >> 4;   // MF = 1: fragment row / 16-byte k-chunk, accumulator token / column quad
   static_assert(!MF || (EPI != EPI_F32_SLICES && !STAMP), "the 16x16x32 form covers the token-row epilogues only");
+  static_assert(EPI != EPI_LN_QKV_KV || (MF && NWN == 2), "the K/V epilogue exists on the 256 x 192 tile of the 16x16x32 form only");
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   // tile order: same W-resident raster as gemm_bf16.hip (column groups of 6 inside 8 row-panel groups)
   const int nbn = p.N / BN;
@@ -136,7 +139,7 @@ __global__ __launch_bounds__(G2<NWN>::NT, 2) void gemm2_kernel(GemmParams p) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc16[i][j][r] = 0.f;
 
-  constexpr bool LN = EPI == EPI_LN_BIAS || EPI == EPI_LN_GELU;
+  constexpr bool LN = EPI == EPI_LN_BIAS || EPI == EPI_LN_GELU || EPI == EPI_LN_QKV_KV;
   float2* ln_lds = reinterpret_cast<float2*>(smem + G::LDS_BYTES);
   // (slices: the last one may be shorter — K need not divide evenly)
   const int nt = (EPI == EPI_F32_SLICES ? (p.ks < p.K - kslice * p.ks ? p.ks : p.K - kslice * p.ks) : p.K) / BK;
@@ -157,6 +160,9 @@ __global__ __launch_bounds__(G2<NWN>::NT, 2) void gemm2_kernel(GemmParams p) {
   if constexpr (LN) {
     __builtin_amdgcn_sched_barrier(0);
     ln_stage_tile(ln_lds, p.ln_stats, p.ln_ld, p.ln_nb, p.ln_eps, p.M, row0, BM, p.cs, p.cv, col0, BN, tid, G::NT);
+    if constexpr (EPI == EPI_LN_QKV_KV) {   // the k-norm weights ride along (nine 16-byte units)
+      if (tid < 9) *reinterpret_cast<uint4*>(smem + G::LDS_BYTES + G::LN_BYTES + tid * 16) = *reinterpret_cast<const uint4*>(p.k_norm_w + tid * 8);
+    }
     __builtin_amdgcn_sched_barrier(0);
   }
   if (nt > 1) {
@@ -358,7 +364,7 @@ __global__ __launch_bounds__(G2<NWN>::NT, 2) void gemm2_kernel(GemmParams p) {
   for (int j = 0; j < 3; ++j)
 #pragma unroll
     for (int g = 0; g < 4; ++g) bb[j][g] = make_uint2(0, 0);
-  if (p.bias != nullptr && EPI != EPI_LN_BIAS && EPI != EPI_LN_GELU && !MF) {
+  if (p.bias != nullptr && !LN && !MF) {
 #pragma unroll
     for (int j = 0; j < 3; ++j)
 #pragma unroll
@@ -367,7 +373,7 @@ __global__ __launch_bounds__(G2<NWN>::NT, 2) void gemm2_kernel(GemmParams p) {
   uint2 bb16[6];   // MF: bias of this lane's column quads 16 j + 4 lq ..
 #pragma unroll
   for (int j = 0; j < 6; ++j) bb16[j] = make_uint2(0, 0);
-  if (MF && p.bias != nullptr && EPI != EPI_LN_BIAS && EPI != EPI_LN_GELU) {
+  if (MF && p.bias != nullptr && !LN) {
 #pragma unroll
     for (int j = 0; j < 6; ++j) bb16[j] = *reinterpret_cast<const uint2*>(p.bias + ncol0 + j * 16 + 4 * lq);
   }
@@ -607,6 +613,103 @@ __global__ __launch_bounds__(G2<NWN>::NT, 2) void gemm2_kernel(GemmParams p) {
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
+    if constexpr (EPI == EPI_LN_QKV_KV) {
+      // ---- K/V column order (vsys_internal.h qkv_kv_column): what this wave's 96-column window holds is wave-uniform.  Q windows
+      // take the store phase below; a K window leaves as Kp rows + 24 Vt row pieces, a V window as 96 Vt row pieces — what
+      // attn_prep_kv would make of these 64 rows (M % 64 == 0 and kv_S % 64 == 0: a pass is whole or absent, and inside one sample).
+      const int H = p.kv_heads, nq = (H * 3) >> 2;
+      const int win = __builtin_amdgcn_readfirstlane(ncol0 / 96);
+      if (win >= nq) {
+        if (wrow0 < p.M) {
+          const int bt = __builtin_amdgcn_readfirstlane(wrow0 / p.kv_S), key0 = __builtin_amdgcn_readfirstlane(wrow0 - bt * p.kv_S);
+          int vf0 = 24 * H + 96 * (win - nq - H);   // flat V feature (h_v * 72 + d) of the first V column of the image
+          if (win < nq + H) {
+            const int h = win - nq;
+            vf0 = 24 * h;
+            // the k half of the qk-norm in place: lane = row, the three thirds of its head in turn (common.h KNorm72)
+            char* rowp = st + lane * OUT_ROW_BYTES;
+            const uint4* wl = reinterpret_cast<const uint4*>(smem + G::LDS_BYTES + G::LN_BYTES);
+            uint4 kk[9];
+#pragma unroll
+            for (int c = 0; c < 9; ++c) kk[c] = *reinterpret_cast<const uint4*>(rowp + c * 16);
+            float ss[3];
+#pragma unroll
+            for (int part = 0; part < 3; ++part) {
+              float x[24];
+#pragma unroll
+              for (int c = 0; c < 3; ++c) unpack8(kk[part * 3 + c], x + c * 8);
+              ss[part] = KNorm72::sumsq(x);
+            }
+            const float rstd = KNorm72::rstd(ss[0], ss[1], ss[2], p.k_eps);
+#pragma unroll
+            for (int part = 0; part < 3; ++part) {
+              float x[24];
+              union { uint4 u[3]; bf16_t w[24]; } kw;
+#pragma unroll
+              for (int c = 0; c < 3; ++c) {
+                unpack8(kk[part * 3 + c], x + c * 8);
+                kw.u[c] = wl[part * 3 + c];
+              }
+              KNorm72::apply(x, rstd, kw.w, p.kscale);
+#pragma unroll
+              for (int c = 0; c < 3; ++c) *reinterpret_cast<uint4*>(rowp + (part * 3 + c) * 16) = pack8(x + c * 8);
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+            // 64 Kp rows of 144 bytes are one contiguous run of 9216 bytes
+            bf16_t* kdst = p.kp + (((int64_t)bt * H + h) * p.kv_S + key0) * 72;
+            uint4 kq[9];
+#pragma unroll
+            for (int it = 0; it < 9; ++it) {
+              const int q = lane + 64 * it;
+              const int m_local = q / 9, c = q - m_local * 9;
+              kq[it] = *reinterpret_cast<const uint4*>(st + m_local * OUT_ROW_BYTES + c * 16);
+            }
+#pragma unroll
+            for (int it = 0; it < 9; ++it) *reinterpret_cast<uint4*>(kdst + (lane + 64 * it) * 8) = kq[it];
+          }
+          // V columns, read down the image: a unit = 8 keys of one column = 16 bytes of a Vt row.  K window: 24 columns x 8 units;
+          // V window: per round 32 columns x 2 units, which meets every LDS bank once (row stride 52 words)
+          const bool kwin = win < nq + H;
+          bf16_t* vdst = p.vt + (int64_t)bt * H * 96 * p.kv_S + key0;
+#pragma unroll
+          for (int g = 0; g < 3; ++g) {
+            uint4 o[4];
+            int64_t off[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              const int it = g * 4 + k;
+              if (kwin && it >= 3) continue;   // (a K window has 3 rounds: 24 columns x 8 units)
+              int col, c;
+              if (kwin) {
+                const int q = lane + 64 * it;
+                c = q / 24;
+                col = q - c * 24;
+              } else {
+                col = (it >> 2) * 32 + (lane & 31);
+                c = 2 * (it & 3) + (lane >> 5);
+              }
+              const int f = vf0 + col, hv = f / 72, d = f - hv * 72;
+              off[k] = ((int64_t)hv * 96 + d) * p.kv_S + c * 8;
+              const char* src = st + (c * 8) * OUT_ROW_BYTES + ((kwin ? 72 : 0) + col) * 2;
+              uint32_t w[4];
+#pragma unroll
+              for (int e = 0; e < 4; ++e)
+                w[e] = (uint32_t)*reinterpret_cast<const uint16_t*>(src + (2 * e) * OUT_ROW_BYTES) |
+                       ((uint32_t)*reinterpret_cast<const uint16_t*>(src + (2 * e + 1) * OUT_ROW_BYTES) << 16);
+              o[k] = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              if (!(kwin && g * 4 + k >= 3)) *reinterpret_cast<uint4*>(vdst + off[k]) = o[k];
+            if (kwin) break;
+          }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // image reads done before the next pass overwrites it
+        __builtin_amdgcn_wave_barrier();
+        continue;
+      }
+    }
     uint4 val[12];
 #pragma unroll
     for (int it = 0; it < 12; ++it) {
@@ -683,6 +786,28 @@ static int launch_gemm2_t(const GemmParams& p, int epi, hipStream_t stream) {
       return VSYS_ERR_ARG;
     default: return VSYS_ERR_ARG;
   }
+  return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
+}
+
+// The spatial qkv site with the K/V prep in the epilogue (EPI_LN_QKV_KV; vsys_gemm_bf16_ln_qkv_kv).  Always this kernel: the window
+// arithmetic of the epilogue is the 256 x 192 tile's (two 96-column wave windows per tile).
+int launch_gemm2_qkv_kv(const GemmParams& p_, hipStream_t stream) {
+  using G = G2<2>;
+  if (p_.M <= 0) return 0;
+  GemmParams p = p_;
+  const int H = p.kv_heads;
+  if (H <= 0 || H % 8 != 0 || p.N != 216 * H || p.kv_S <= 0 || p.kv_S % 64 != 0 || p.M % p.kv_S != 0 || p.K <= 0 || p.K % BK != 0)
+    return VSYS_ERR_SHAPE;
+  if (!p.cs || !p.cv || !p.ln_stats || p.ln_nb < 1 || p.ln_nb > 12 || p.ln_nb * LN_BLOCK != p.K || p.ln_ld < p.M) return VSYS_ERR_SHAPE;
+  if (!p.out || !p.kp || !p.vt || !p.k_norm_w || p.ldo < 72 * H) return VSYS_ERR_ARG;
+  if ((p.lda % 8) || (p.ldw % 8) || (p.ldo % 8) || ((uintptr_t)p.kp % 16) || ((uintptr_t)p.vt % 16) || ((uintptr_t)p.k_norm_w % 16)) return VSYS_ERR_ALIGN;
+  if (p.lda * 512 + (int64_t)p.K * 2 >= 0x7fffffff || p.ldw * 384 + (int64_t)p.K * 2 >= 0x7fffffff) return VSYS_ERR_SHAPE;
+  constexpr int LDS = G::LDS_BYTES + G::LN_BYTES + G::KW_BYTES;
+  static std::atomic<unsigned long long> attr_seen{0};
+  for (DeviceOnce once(attr_seen); once.todo(); once.done())
+    (void)hipFuncSetAttribute((const void*)gemm2_kernel<EPI_LN_QKV_KV, 2, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+  const int grid = ((p.M + BM - 1) / BM) * (p.N / G::BN);
+  hipLaunchKernelGGL((gemm2_kernel<EPI_LN_QKV_KV, 2, 0, 1>), dim3(grid), dim3(G::NT), LDS, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
 }
 

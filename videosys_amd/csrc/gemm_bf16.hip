@@ -1259,6 +1259,23 @@ static int launch_sched8(const GemmParams& p, int epi, hipStream_t stream) {
   return mf16_default() ? launch_gemm_t<8, 256, 1, 0, 1>(p, epi, stream) : launch_gemm_t<8, 256>(p, epi, stream);
 }
 
+// the folded-LayerNorm epilogues at this shape run on gemm2_kernel (256 x 192 tile, two workgroups per CU): many tiles, short K loop
+static bool ln_on_two_workgroup_tile(int64_t M, int64_t N, int64_t K) {
+  return (int64_t)((M + 255) / 256) * (N / BN) >= 400 && K <= 1536 && N >= 2304 && g_gemm_variant_a.load(std::memory_order_relaxed) != 8;
+}
+// ... and on its 16x16x32 form, the one that has the K/V epilogue (vsys_gemm_bf16_ln_qkv_kv_dispatched)
+bool gemm_ln_qkv_kv_dispatched(int64_t M, int64_t N, int64_t K) {
+  return N > 0 && N % BN == 0 && K > 0 && K % BK == 0 && ln_on_two_workgroup_tile(M, N, K) && mf16_default();
+}
+// EPI_LN_QKV_KV: gemm2_kernel whatever the shape, with the tile raster every other launch gets
+int launch_gemm_qkv_kv(const GemmParams& p_, hipStream_t stream) {
+  GemmParams p = p_;
+  const int ras = g_gemm_raster_a.load(std::memory_order_relaxed);
+  p.raster_gw = ras / 100;
+  p.raster_ph = ras % 100;
+  return launch_gemm2_qkv_kv(p, stream);
+}
+
 int launch_gemm(const GemmParams& p_, int epi, hipStream_t stream) {
   if (p_.M <= 0) return 0;
   GemmParams p = p_;
@@ -1289,7 +1306,7 @@ int launch_gemm(const GemmParams& p_, int epi, hipStream_t stream) {
   }
   if (ln) {   // same shape dispatch as the store-only epilogues below
     if ((int64_t)((p.M + 255) / 256) * (p.N / BN) < 400) return launch_rows128(p, epi, stream, g_gemm_variant_a.load(std::memory_order_relaxed) == 123);
-    if (p.K <= 1536 && p.N >= 2304 && g_gemm_variant_a.load(std::memory_order_relaxed) != 8) return launch_gemm2(p, epi, mf16_default() ? 2 : 0, stream);
+    if (ln_on_two_workgroup_tile(p.M, p.N, p.K)) return launch_gemm2(p, epi, mf16_default() ? 2 : 0, stream);
     return g_gemm_variant_a.load(std::memory_order_relaxed) == 8 ? launch_gemm_t<8, 256>(p, epi, stream) : launch_sched8(p, epi, stream);
   }
   const int g_gemm_variant = g_gemm_variant_a.load(std::memory_order_relaxed);

@@ -54,6 +54,9 @@ enum { EPI_BIAS = VSYS_EPI_BIAS, EPI_BIAS_GELU = VSYS_EPI_BIAS_GELU, EPI_GATE_RE
        EPI_LN_BIAS = 3, EPI_LN_GELU = 4,
        // EPI_GATE_RES that also emits the LayerNorm partials of the rows it stores (vsys_gemm_bf16_stats); no aux
        EPI_GATE_RES_STATS = 5,
+       // EPI_LN_BIAS of the spatial qkv site in the K/V column order (vsys_gemm_bf16_ln_qkv_kv, gemm2_bf16.hip): Q windows are stored
+       // as rows, K windows leave as Kp (RMS norm + softmax scale), V columns as Vt — the attn_prep_kv pass without its launch
+       EPI_LN_QKV_KV = 6,
        EPI_F32_SLICES = 100 /* internal (gemm2_bf16.hip): fp32 K-slice partials, see launch_gemm2_slices */ };
 constexpr int LN_BLOCK = 96;   // columns per LayerNorm partial (= the column width of a GEMM wave tile)
 enum { ACT_NONE = VSYS_ACT_NONE, ACT_SILU = VSYS_ACT_SILU, ACT_GELU_TANH = VSYS_ACT_GELU_TANH };
@@ -91,7 +94,24 @@ struct GemmParams {
   // two-way split K of the 128-row geometry (gemm_bf16.hip KS): fp32 partial sums [tile][wave][24][64 lanes] float4 and one flag per
   // (tile, wave), both owned by the library (one workspace per stream); filled in by launch_gemm
   float* sk_ws = nullptr; int* sk_flags = nullptr;
+  // EPI_LN_QKV_KV only.  N = 216 kv_heads output columns in 96-column windows (qkv_kv_column below): out / ldo take the Q windows;
+  // row m is key m % kv_S of sample m / kv_S in kp [M / kv_S][kv_heads][kv_S][72] and vt [M / kv_S][kv_heads][96][kv_S] (the
+  // attn_prep_kv layouts at kv_len = kv_pad = kv_S; vt rows 72-95 are the caller's constants).  kv_S % 64 == 0, M % kv_S == 0.
+  bf16_t* kp = nullptr; bf16_t* vt = nullptr; const bf16_t* k_norm_w = nullptr;
+  int kv_S = 0, kv_heads = 0; float k_eps = 0.f, kscale = 0.f;
 };
+
+// Column order of the spatial qkv site under EPI_LN_QKV_KV: where output feature n (0 .. 216 heads - 1: q | k | v as the checkpoint
+// has them, a head = 72 features) sits among the GEMM's columns.  Windows of 96 columns = one wave's column window: 3 heads / 4
+// windows of Q in place, then one window per head h = its 72 K features + V features 24 h .. 24 h + 23, then the remaining V features
+// 96 to a window.  adaln_prescale_kernel writes W', cs, cv through it; the epilogue reads window kinds back from the column offset.
+__host__ __device__ inline int qkv_kv_column(int n, int heads) {
+  const int C = 72 * heads, nq = C / 96;
+  if (n < C) return n;
+  if (n < 2 * C) return (nq + (n - C) / 72) * 96 + (n - C) % 72;
+  const int f = n - 2 * C;
+  return f < 24 * heads ? (nq + f / 24) * 96 + 72 + f % 24 : (nq + heads) * 96 + (f - 24 * heads);
+}
 
 // implicit-GEMM convolution / 128-column GEMM (conv_bf16.hip).  A points at the row that tap (0,0,0) reads for output row 0.
 struct ConvParams {
@@ -146,6 +166,9 @@ int launch_t5_attention_mfma(const bf16_t* qkv, int64_t row_stride, int inner, c
 
 int launch_gemm(const GemmParams& p, int epi, hipStream_t stream);
 int launch_gemm2(const GemmParams& p, int epi, int wide, hipStream_t stream);
+int launch_gemm2_qkv_kv(const GemmParams& p, hipStream_t stream);   // EPI_LN_QKV_KV (gemm2_bf16.hip); raster fields as given
+int launch_gemm_qkv_kv(const GemmParams& p, hipStream_t stream);    // ... with the library's tile raster (gemm_bf16.hip)
+bool gemm_ln_qkv_kv_dispatched(int64_t M, int64_t N, int64_t K);    // launch_gemm would run EPI_LN_BIAS at this shape on that kernel
 int launch_gemm2_slices(const GemmParams& p, int slices, hipStream_t stream);
 int launch_gemm3(const GemmParams& p, int epi, hipStream_t stream);
 // ping-pong wave groups (gemm4_bf16.hip); persistent = 1: one workgroup per CU walks the tiles, 2: + stream-K tail

@@ -175,7 +175,8 @@ def gemm_gate_res_add(x, w, bias, *, res, gate=None, gate_stride=0, rows_per_sam
 
 
 def adaln_prescale(sites, nblocks, mod):
-    """sites: int64 device tensor [nsites, 10] (include/videosys_amd.h, vsys_adaln_prescale); mod: the step's modulation table."""
+    """sites: int64 device tensor [nsites, 10] (include/videosys_amd.h, vsys_adaln_prescale); mod: the step's modulation table.  A site
+    whose N word is ``N | heads << 32`` gets its W', cs, cv in the K/V column order (qkv_kv_column_order)."""
     _chk(sites, mod)
     _bf16(mod)
     assert sites.dtype == torch.int64 and sites.is_contiguous() and sites.shape[1] == 10 and mod.is_contiguous()
@@ -383,6 +384,61 @@ def alloc_kv_buffers(batch, heads, kv_len, device):
     # 73..75 and 77..95 are never written by it, so they must be zero on entry: this zero fill is part of the contract
     vt = torch.zeros(batch, heads, VT_ROWS, kv_pad, dtype=torch.bfloat16, device=device)
     return kp, vt
+
+
+# ---- spatial K/V prep in the qkv GEMM's epilogue (include/videosys_amd.h, vsys_gemm_bf16_ln_qkv_kv)
+def _fused_kv_default() -> bool:
+    import os
+
+    return os.environ.get("VSYS_FUSED_KV", "1") != "0"
+
+
+FUSED_KV = _fused_kv_default()   # VSYS_FUSED_KV=0 (read once): models keep the gemm_ln + attn_prep_kv pair
+
+
+def qkv_kv_column_order(heads: int) -> torch.Tensor:
+    """int64 [216 heads]: the GEMM column that output feature n (q | k | v in the checkpoint's order) takes in the K/V column order
+    (csrc/vsys_internal.h qkv_kv_column — this is its host mirror): windows of 96 columns, Q in place, then one window per head with
+    its 72 K features + 24 V features, then the remaining V features."""
+    assert heads > 0 and heads % 4 == 0
+    C, nq = 72 * heads, 72 * heads // 96
+    n = torch.arange(3 * C, dtype=torch.int64)
+    k, f = n - C, n - 2 * C
+    kcol = (nq + k // 72) * 96 + k % 72
+    vcol = torch.where(f < 24 * heads, (nq + f // 24) * 96 + 72 + f % 24, (nq + heads) * 96 + (f - 24 * heads))
+    return torch.where(n < C, n, torch.where(n < 2 * C, kcol, vcol))
+
+
+def gemm_ln_qkv_kv_dispatched(M: int, N: int, K: int) -> bool:
+    """True when gemm_ln at this shape runs on the kernel that has the K/V epilogue (the fused form then replaces that launch)."""
+    return bool(_lib.load().vsys_gemm_bf16_ln_qkv_kv_dispatched(M, N, K))
+
+
+def kv_set_constant_rows(vt):
+    """The Vt rows no per-step launch has to write when every key of the buffer is valid (kv_len == kv_pad): rows 72 and 76 = 1.0 (the
+    softmax denominator rides on the PV MFMA), 73-75 and 77-95 = 0.  attn_prep_kv writes the same values into rows 72 / 76 there."""
+    assert vt.shape[2] == VT_ROWS
+    vt[:, :, HEAD_DIM:] = 0
+    vt[:, :, HEAD_DIM] = 1.0
+    vt[:, :, HEAD_DIM + 4] = 1.0
+
+
+def gemm_ln_qkv_kv(x, wp, cs, cv, stats, k_norm_w, q, kp, vt, S, heads, eps=1e-6, k_eps=1e-6):
+    """gemm_ln of the spatial qkv site + attn_prep_kv in one launch.  wp / cs / cv are in the K/V column order (adaln_prescale writes
+    them so for a site whose N word carries ``heads``); row m of x is key m % S of sample m // S.  q [M, >= 72 heads] (row-strided)
+    gets what gemm_ln's first third would hold, kp / vt (alloc_kv_buffers(M // S, heads, S) + kv_set_constant_rows) the attn_prep_kv
+    layouts.  Shapes the entry does not take (S % 64, heads % 8) raise: there is no fallback here."""
+    _chk(x, wp, cs, cv, stats, k_norm_w, q, kp, vt)
+    _bf16(x, wp, k_norm_w, q, kp, vt)
+    assert x.dim() == 2 and x.stride(1) == 1 and wp.stride(1) == 1 and q.stride(1) == 1 and cs.dtype == torch.float32 and cv.dtype == torch.float32
+    M, K = x.shape
+    assert wp.shape == (216 * heads, K) and cs.numel() == cv.numel() == 216 * heads and k_norm_w.numel() == HEAD_DIM and k_norm_w.is_contiguous()
+    assert S > 0 and M % S == 0 and q.shape[0] == M and q.shape[1] >= HEAD_DIM * heads and kp.is_contiguous() and vt.is_contiguous()
+    assert tuple(kp.shape) == (M // S, heads, S, HEAD_DIM) and tuple(vt.shape) == (M // S, heads, VT_ROWS, S)
+    ld = _stats_ld(stats, M, K // LN_BLOCK)
+    _call("vsys_gemm_bf16_ln_qkv_kv", _p(x), x.stride(0), _p(wp), wp.stride(0), _p(cs), _p(cv), _p(stats), ld, _p(k_norm_w), _p(q),
+          q.stride(0), _p(kp), _p(vt), M, K, S, heads, float(eps), float(k_eps))
+    return q
 
 
 def attn_prep_kv(k, v, k_norm_w, kp, vt, batch, heads, kv_len, eps=1e-6):

@@ -206,7 +206,10 @@ class STDiT3:
         self.adaln_fold = os.environ.get("VSYS_ADALN_FOLD", "1") != "0"
         self.fold_spatial_qkv = True   # test hook: False = the spatial qkv site keeps the separate AdaLN pass on one GPU too (what a
         #                                sequence-parallel rank whose modulated activations travel computes, bit for bit)
-        self._fold = None          # per-B site table + the W' / cs / cv buffers (built on first use)
+        # spatial K/V prep in the qkv GEMM's epilogue (ops.gemm_ln_qkv_kv) where the folded spatial qkv site runs on the kernel that has
+        # it; VSYS_FUSED_KV=0 (or this attribute) keeps the gemm_ln + attn_prep_kv pair — same bits either way
+        self.fused_kv = ops.FUSED_KV
+        self._fold = None          # per-(B, column order) site table + the W' / cs / cv buffers (built on first use)
         self._stats_fresh = False  # "the statistics buffer describes the current x" (within one step)
         self._programs = {}
         self.program_stats = dict(recorded=0, replayed=0, eager=0)
@@ -439,11 +442,20 @@ class STDiT3:
         return (self.adaln_fold and x_mask is None and C % ops.LN_BLOCK == 0 and C // ops.LN_BLOCK <= 12
                 and bool((ts_host == ts_host[0]).all()) and len(set(fkey[:-1])) == 1)
 
-    def _fold_tables(self, B):
+    def _fused_kv_ok(self, N, S):
+        """The spatial qkv site of a step with N token rows, S per frame, takes the fused GEMM + K/V prep: one GPU, the site folded,
+        a shape the entry supports (whole 64-row passes inside one frame) and the shape dispatch already runs on its kernel."""
+        C, H = self.hidden_size, self.num_heads
+        return bool(self.fused_kv and self._sp is None and self.fold_spatial_qkv and C == 72 * H and H % 8 == 0 and S % 64 == 0
+                    and ops.gemm_ln_qkv_kv_dispatched(N, 3 * C, C))
+
+    def _fold_tables(self, B, fused_kv=False):
         """Site table of vsys_adaln_prescale for a modulation table laid out [2*depth, B, 6C] (sample-0 rows) and the per-site
-        W' / cs / cv buffers (allocated once: 2 x the qkv + fc1 weight bytes)."""
+        W' / cs / cv buffers (allocated once: 2 x the qkv + fc1 weight bytes).  ``fused_kv``: the spatial qkv sites are written in
+        the K/V column order (ops.qkv_kv_column_order) that ops.gemm_ln_qkv_kv reads — the buffers are the same, a step writes all
+        of them before it reads any, so steps of either order may alternate."""
         f = self._fold or None     # (HostOffload empties it when the weights leave the device: their addresses are in the table)
-        if f is not None and f["B"] == B:
+        if f is not None and f["B"] == B and f["fused_kv"] == fused_kv:
             return f
         w, C, dev = self.w, self.hidden_size, self.device
         bufs = f["bufs"] if f is not None else {}
@@ -458,10 +470,11 @@ class STDiT3:
                                   torch.empty(N, dtype=torch.float32, device=dev))
                 Wp, cs, cv = bufs[name]
                 base = i * B * 6 * C
+                order = self.num_heads << 32 if (fused_kv and i % 2 == 0 and s_sh == 0) else 0   # spatial qkv: K/V column order
                 rows.append([W.data_ptr(), b.data_ptr(), Wp.data_ptr(), cs.data_ptr(), cv.data_ptr(), base + s_sh, base + s_sc,
-                             N, K, blk])
+                             N | order, K, blk])
                 blk += -(-N // 4)
-        self._fold = dict(B=B, bufs=bufs, sites=torch.tensor(rows, dtype=torch.int64).to(dev), nblocks=blk)
+        self._fold = dict(B=B, fused_kv=fused_kv, bufs=bufs, sites=torch.tensor(rows, dtype=torch.int64).to(dev), nblocks=blk)
         return self._fold
 
     def _ln_stats(self, N):
@@ -547,7 +560,7 @@ class STDiT3:
             out = self._forward_device(xz, ts_host.to(dev), static, plan, timestep_int, valid_depth, cp, x_mask, fold=fold)
         else:
             sp = self._sp
-            key = (B, Tx, Hx, Wx, float(height[0]), float(width[0]), fkey, valid_depth, cp, fold, self.fold_spatial_qkv,
+            key = (B, Tx, Hx, Wx, float(height[0]), float(width[0]), fkey, valid_depth, cp, fold, self.fold_spatial_qkv, self.fused_kv,
                    None if plan is None else tuple(d[:2] + d[5:7] for d in plan),
                    None if static[0]["varlen"] is None else static[0]["varlen"].lens,   # a ragged batch: its per-sample text lengths
                    None if sp is None else (sp.P, sp.rank, self._scatter, self._switch, self._overlap))
@@ -655,7 +668,7 @@ class STDiT3:
         mod = ops.mod_table(w["_all_tables"], t_mlp)  # [2*depth, B, 6C]  (x_mask: [2*depth, B*T, 6C])
         ftab = None
         if fold:   # W' = bf16(W (1 + scale)), cs, cv of all 2 x 2 x depth sites of this step: one launch
-            ftab = self._fold_tables(B)
+            ftab = self._fold_tables(B, self._fused_kv_ok(B * T * S, S))
             ops.adaln_prescale(ftab["sites"], ftab["nblocks"], mod)
         self._stats_fresh = False
 
@@ -807,7 +820,18 @@ class STDiT3:
                 self._stats_fresh = False
         else:
             xm = None
-            if fold_attn and sp_order is None:
+            fused_kv = fold_attn and not temporal and sp is None and ftab["fused_kv"]
+            if fused_kv:
+                # qkv GEMM + K/V prep in one launch: W' / cs / cv of this site are in the K/V column order, q lands in the front of the
+                # qkv buffer as [N, C] rows, Kp / Vt leave the epilogue; the K and V thirds are never written as rows
+                if not self._stats_fresh:
+                    ops.ln_row_stats(x, stats)
+                    self._stats_fresh = True
+                Wp_, cs_, cv_ = ftab["bufs"][p + ".attn.qkv"]
+                kp, vt = self._kv_spatial(B * T, S, constant_rows=True)
+                q = _buf("qkv", (N, 3 * C)).view(-1)[:N * C].view(N, C)
+                ops.gemm_ln_qkv_kv(x, Wp_, cs_, cv_, stats, w[p + ".attn.k_norm.weight"], q, kp, vt, S, H)
+            elif fold_attn and sp_order is None:
                 qkv = folded(p + ".attn.qkv", False, _buf("qkv", (N, 3 * C)))
             elif not fold_attn:
                 xm = ops.adaln_modulate(x, shift_msa, scale_msa, rps, C6, out=_buf("xm", (N, C)))
@@ -821,6 +845,9 @@ class STDiT3:
                 ao = _buf("attn_out", (N, C))
                 cos, sin = self._rope(T)
                 ops.attn_temporal(qkv, C, w[p + ".attn.q_norm.weight"], w[p + ".attn.k_norm.weight"], cos, sin, ao, B, T, S, H)
+            elif fused_kv:
+                ao = _buf("attn_out", (N, C))
+                ops.flash_attn(q, w[p + ".attn.q_norm.weight"], kp, vt, ao, B * T, H, S, S, k_norm_bound=self._kbound(p))
             elif sp is None:
                 if not fold_attn:
                     qkv = ops.gemm(xm, w[p + ".attn.qkv.weight"], w[p + ".attn.qkv.bias"], out=_buf("qkv", (N, 3 * C)))
@@ -986,10 +1013,19 @@ class STDiT3:
             self._kbounds[p] = kb
         return kb
 
-    def _kv_spatial(self, batch, kv_len):
+    def _kv_spatial(self, batch, kv_len, constant_rows=False):
+        """The Kp / Vt buffers all spatial blocks share.  ``constant_rows`` (the fused qkv + K/V launch, which leaves Vt rows 72-95
+        alone; kv_len is then a multiple of 64, every key valid): those rows are set once here.  The buffers may be handed to
+        attn_prep_kv by another path of the same process (the switch off, an unfolded step): it writes rows 72 / 76 itself, with the
+        same 1.0 over all kv_len = kv_pad keys, and never touches 73-75 / 77-95 — both writers leave the same constants, which is
+        what makes sharing safe."""
         key = ("kv_spatial", batch, kv_len)
         if key not in self._ws:
             self._ws[key] = ops.alloc_kv_buffers(batch, self.num_heads, kv_len, self.device)
+        if constant_rows and key + ("const",) not in self._ws:
+            assert kv_len % 64 == 0
+            ops.kv_set_constant_rows(self._ws[key][1])
+            self._ws[key + ("const",)] = True
         return self._ws[key]
 
     def _mlp_slab(self, like):
