@@ -221,7 +221,12 @@ int vsys_attn_prep_kv(const void* k, int64_t k_stride, const void* v, int64_t v_
 
 /* softmax(q k^T / sqrt(72)) v for head_dim 72, non-causal, keys >= kv_len masked; optional q RMS-norm.
  * Spatial self-attention (attentions.py:75,100) and cross-attention (attentions.py:259-270).
- * q(b,s,h) at q + (b*q_len + s)*q_stride + h*72; out likewise with out_stride. */
+ * q(b,s,h) at q + (b*q_len + s)*q_stride + h*72; out likewise with out_stride.
+ * Padding: the kernels read the Kp rows and Vt columns of keys kv_len .. 64 ceil(kv_len / 64) - 1 and give them the weight 0 by
+ * masking, not by skipping: both MUST BE FINITE there (0 x NaN is NaN: with NaN in the Kp pad rows alone, or in the Vt pad columns
+ * alone, every output element is NaN; any finite value gives the bits of zeros).  vsys_attn_prep_kv writes zeros there; a kv_len
+ * shorter than the one the buffers were prepared for (Latte's per-sample text lengths) leaves real K / V values, which is fine.
+ * The same holds for vsys_flash_attn_d72_kb. */
 int vsys_flash_attn_d72(const void* q, int64_t q_stride, const void* q_norm_w, const void* kp, const void* vt, void* out,
                         int64_t out_stride, int64_t batch, int64_t heads, int64_t q_len, int64_t kv_len, int64_t kv_pad,
                         float eps, void* stream);

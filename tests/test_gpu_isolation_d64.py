@@ -1,0 +1,20 @@
+"""-m gpu: guard-band tests (tests/isolation.py) of the 'd64' family — every row of tests/isolation_cases.py with that family
+name, under both guard fills and every kernel variant the row lists.  Exact assertions only: same bits as the call on tight operands,
+every guard byte untouched, every input unchanged."""
+import pytest
+
+import isolation_run as run
+from isolation_cases import family
+
+pytestmark = pytest.mark.gpu
+ROWS = family("d64")
+
+
+@pytest.mark.parametrize("row", ROWS, ids=[c.name for c in ROWS])
+def test_isolation_d64(row):
+    run.run_case(row)
+
+
+def test_isolation_d64_variant_runs():
+    """Runs after the rows above (file order): what executed, per kernel variant."""
+    run.check_counts("d64", ROWS)

@@ -457,7 +457,10 @@ def flash_attn(q, q_norm_w, kp, vt, out, batch, heads, q_len, kv_len, eps=1e-6, 
     """q/out: 2-D row-strided views [batch*q_len, >= heads*72].  ``k_norm_bound``: the caller's promise about the norms of the Kp
     rows (include/videosys_amd.h, vsys_flash_attn_d72_kb; see rms_key_bound); None = no promise.  ``keys_exact``: the caller's promise
     that (kp, vt) were prepared by attn_prep_kv for exactly ``kv_len`` on zeroed buffers (vsys_flash_attn_d72_exact: no mask on the
-    ragged last tile) — never with a kv_len shorter than the buffers were prepared for."""
+    ragged last tile) — never with a kv_len shorter than the buffers were prepared for.  The masked forms (default, k_norm_bound) READ the
+    Kp rows and Vt columns behind kv_len up to the end of the last 64-key tile and give them the weight 0 by masking, not by
+    skipping: both must hold FINITE values (NaN in either makes every output element NaN; include/videosys_amd.h).  attn_prep_kv
+    leaves zeros there, a shorter kv_len inside a longer prepared buffer real K / V values."""
     _chk(q, q_norm_w, kp, vt, out)
     _bf16(q, q_norm_w, kp, vt, out)
     assert q.stride(1) == 1 and out.stride(1) == 1
