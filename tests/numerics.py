@@ -92,3 +92,108 @@ class Bound:
 def check_elementwise(out, ref, bound, what: str) -> None:
     """One-shot form of Bound for outputs small enough to compare at once (any shape; rows = the first dimension)."""
     Bound(what).add(out, ref, bound).check()
+
+
+# ------------------------------------------------------------------------------------------------ softmax attention
+U_EXP = 2.0**-21   # relative accuracy assumed for v_exp_f32: the kernel guides give no figure, so 2^-21 (about 1 ulp of fp32 with room for
+U_RCP = 2.0**-21   # the range reduction) is used for it and for the reciprocal / division of the row sum; both vanish next to 2^-8
+
+
+class AttnRef:
+    """Result of ``attention_ref``: ``out`` and ``bound`` [Lq, Dv] float64, ``weight`` [Lq] = the reference's softmax weight on the keys
+    named by ``targets`` (None without targets), ``logits`` [Lq, Lk] (exp2 domain, float64), ``ds_max`` [Lq] = the largest logit error
+    bound of the row, ``vacuous`` = the number of rows whose P error bound reaches 1 (their elements get an INFINITE bound: the
+    quotient form has broken down there, and a test must hold such rows by other means and say so)."""
+
+    def __init__(self, out, bound, weight, logits, ds_max, vacuous):
+        self.out, self.bound, self.weight, self.logits, self.ds_max, self.vacuous = out, bound, weight, logits, ds_max, vacuous
+
+
+def attention_ref(q, kp, v, *, eq=None, ek=None, bias=None, log2_scale=1.0, m_extra=None, denominator="rounded", targets=None,
+                  tile=64, budget=1 << 25) -> AttnRef:
+    """softmax attention of one (batch, head) slice — or a stack of slices of one shape: any leading dimensions, shared by all
+    arguments — in float64 and its per-element bound, chunked over query rows.
+
+    ``q`` [Lq, D], ``kp`` [Lk, D], ``v`` [Lk, Dv]: the operands the two matrix products see, as float64 (exactly the bf16 values where
+    the kernel's operand is a stored tensor; where the kernel derives the operand — a normed q — the float64 value of the contract and
+    ``eq`` / ``ek`` [same shape] its worst-case error, None = exact).  Logits s = log2_scale q kp^T (+ ``bias`` [Lq, Lk], float64, in
+    the same exp2 domain): the d72 / d64 kernels carry scale log2(e) on Kp (log2_scale = 1), the temporal and T5 kernels multiply
+    natural-domain logits by log2(e).  Only valid keys are passed (the caller slices at kv_len).
+
+    Bound, term by term (no global factor):
+      logits   ds_j = log2_scale (eq |kp_j| + |q| ek_j + eq ek_j) + acc(D + 10, log2_scale sum_d |q_d kp_jd| + |bias| + M): D + 8 products
+               (the head dim padded to whole MFMA chunks) + the subtracted maximum entering the accumulator + the bias add; M is the
+               magnitude of what is subtracted: max_j |s_j|, raised to ``m_extra`` [Lq] (|q| k_bound of the kernels without a running max);
+      P        p_j = 2^(s_j - m) -> bf16: relative error e_j = 2^-8 + U_EXP + (2^ds_j - 1);
+      output   denominator == "rounded": the row sum is the sum of the SAME rounded p_j (the d72 flash kernels: the ones rows of Vt ride
+               on the PV MFMA), so numerator and denominator err together and
+               o~ - o = sum_j p_j e_j (v_j - o) / sum_j p_j (1 + e_j):  sum_j p_j e_j |v_jd - o_d| / (l (1 - max e)) (infinite from max e = 1 on, see AttnRef.vacuous);  a peaked row
+               collapses to rnd(o).  denominator == "fp32": p_j / l is formed in fp32 from the unrounded p_j and THEN rounded to bf16
+               (the temporal kernels, as the reference's attn.to(dtype) does), or the rounded p_j feed the PV product while the row sum adds
+               up the UNROUNDED fp32 p_j (the 32-row d64 kernel, attention64.hip: lsum += pv before the cast, also under T5's bias hook; the
+               d64 w64 stream takes the sum from the rounded P like d72): each weight errs on its own,
+               sum_j p_j e'_j |v_jd| / (l (1 - max e')), e' = e + U_RCP + acc(Lk, 1) + (2^max ds - 1) (the sum's own error);
+      PV       acc(Lk + 2 ntiles, sum_j p_j |v_jd| / l + |o_d|): Lk products and one rescale of numerator and denominator per tile (the
+               rescale factor itself cancels in the quotient);  U_RCP |o_d| for the final division;  rnd(o_d) for the bf16 store.
+    """
+    assert denominator in ("rounded", "fp32")
+    Lq, D = q.shape[-2:]
+    Lk, Dv = v.shape[-2:]
+    assert kp.shape[-2:] == (Lk, D) and Lk > 0
+    ntiles = -(-Lk // tile)
+    T = lambda x: x.transpose(-1, -2)
+    rows = lambda x, r0, r1: x[..., r0:r1, :]
+    ka, va = kp.abs(), v.abs()
+    outs, bounds, weights, logits, dsmax = [], [], [], [], []
+    vacuous = 0
+    nb = max(1, q.numel() // (Lq * D))
+    # the largest temporary per query row: [Lk, Dv] for the |v - o| weighting, [Lk] otherwise
+    chunk = max(1, min(Lq, budget // (nb * Lk * (Dv if denominator == "rounded" else 1))))
+    for r0, r1 in row_chunks(Lq, chunk):
+        qc = rows(q, r0, r1)
+        s = log2_scale * (qc @ T(kp))
+        sabs = log2_scale * (qc.abs() @ T(ka))
+        ds = torch.zeros_like(s)
+        if eq is not None:
+            ds = ds + log2_scale * (rows(eq, r0, r1) @ T(ka))
+        if ek is not None:
+            ds = ds + log2_scale * ((qc.abs() + (rows(eq, r0, r1) if eq is not None else 0)) @ T(ek))
+        if bias is not None:
+            s = s + rows(bias, r0, r1)
+            sabs = sabs + rows(bias, r0, r1).abs()
+        M = s.abs().amax(dim=-1, keepdim=True)
+        if m_extra is not None:
+            M = torch.maximum(M, m_extra[..., r0:r1, None].abs())
+        ds = ds + acc(D + 10, sabs + M)
+        e = U_BF16 + U_EXP + (torch.exp2(ds) - 1)
+        p = torch.exp2(s - s.amax(dim=-1, keepdim=True))
+        l = p.sum(dim=-1, keepdim=True)
+        o = (p @ v) / l
+        pv_abs = (p @ va) / l
+        if denominator == "rounded":
+            first = torch.einsum("...qk,...qkd->...qd", p * e, (v[..., None, :, :] - o[..., :, None, :]).abs())
+        else:
+            e = e + U_RCP + acc(Lk, 1.0) + (torch.exp2(ds.amax(dim=-1, keepdim=True)) - 1)
+            first = (p * e) @ va
+        emax = e.amax(dim=-1, keepdim=True)
+        broken = emax >= 1.0        # (the quotient form holds for every max e < 1 and grows without limit towards it on its own)
+        vacuous += int(broken.sum())
+        first = torch.where(broken, torch.full_like(first, float("inf")), first / (l * (1 - emax).clamp_min(FLOOR)))
+        dsmax.append(ds.amax(dim=-1))
+        bounds.append(first + acc(Lk + 2 * ntiles, pv_abs + o.abs()) + U_RCP * o.abs() + rnd(o))
+        outs.append(o)
+        logits.append(s)
+        if targets is not None:
+            weights.append(torch.gather(p, -1, rows(targets, r0, r1)).sum(dim=-1) / l[..., 0])
+    return AttnRef(torch.cat(outs, dim=-2), torch.cat(bounds, dim=-2), torch.cat(weights, dim=-1) if targets is not None else None,
+                   torch.cat(logits, dim=-2), torch.cat(dsmax, dim=-1), vacuous)
+
+
+def rms_q_chain(q, w, eps=1e-6):
+    """(q^, eq) of the d72 flash kernels' query chain (attention.hip finish_q): q^ = bf16(bf16(q rstd) w), rstd = rsqrt(mean(q^2) + eps)
+    over the head's 72 values in fp32.  eq = (rnd(q rstd) + acc(72, |q rstd|)) |w| + rnd(q^).  ``w`` None: q is the operand bit for bit."""
+    if w is None:
+        return q, None
+    n = q * torch.rsqrt((q * q).mean(dim=-1, keepdim=True) + eps)
+    qh = n * w
+    return qh, (rnd(n) + acc(q.shape[-1], n.abs())) * w.abs() + rnd(qh)

@@ -1,8 +1,10 @@
 """The element-wise bound of tests/numerics.py on synthetic data (no GPU): a correctly rounded result and a result with one
-rounding fewer than the contract pass; each of four planted defects fails, and the failure names the tile."""
+rounding fewer than the contract pass; each of four planted GEMM defects fails, and the failure names the tile.  Second half: the
+softmax-attention bound (numerics.attention_ref) against a CPU emulation of the d72 flash contract and its planted defects."""
 import pytest
 import torch
 
+import attn_families as fam
 import numerics as nm
 
 M, N, K = 1024, 384, 1024
@@ -110,3 +112,139 @@ def test_gate_residual_chain_accepts_one_rounding_fewer():
     bad[256:384] = (x[256:384].float() + (gate2.float() * acc32[256:384]).to(torch.bfloat16).float()).to(torch.bfloat16)
     with pytest.raises(AssertionError, match=r"128-row tile 2,"):
         _check(bad, ref, bound, "gate + residual")
+
+
+# ------------------------------------------------------------------------------------------------ softmax attention
+
+
+def emulate_d72(qh, kp, v, kv_len, *, static_m=None, defect=None):
+    """The d72 flash contract in fp32 / bf16 on the CPU (attention.hip): 64-key tiles, online softmax in the exp2 domain, P rounded to
+    bf16, the row sum taken from the rounded P, O and the row sum rescaled only when some row of a 32-row group sees a tile maximum
+    more than 8 above the adopted one (the first tile adopts its maximum, signed), one final division, bf16 output.  ``static_m``
+    [Lq]: the form without a running maximum (subtract |q^| k_bound, never rescale).  kp / v [kv_pad, 72] hold what lies behind kv_len
+    (zeros after attn_prep_kv).  ``defect`` plants one of the errors the bound must catch."""
+    Lq, kv_pad = qh.shape[0], kp.shape[0]
+    q32, k32, v32 = qh.float(), kp.float(), v.float()
+    limit = kv_pad if defect == "mask_at_kv_pad" else kv_len - 1 if defect == "drop_last_key" else kv_len
+    m = torch.zeros(Lq, 1) if static_m is None else static_m.float()[:, None]
+    o, l = torch.zeros(Lq, v.shape[1]), torch.zeros(Lq, 1)
+    for t in range(kv_pad // 64):
+        ks, vs = k32[64 * t:64 * t + 64], v32[64 * t:64 * t + 64]
+        s = q32 @ ks.t() - m
+        s[:, max(0, limit - 64 * t):] = -1e30
+        if static_m is None:
+            mx = s.amax(dim=1, keepdim=True)
+            for r0 in range(0, Lq, 32):
+                g = slice(r0, r0 + 32)
+                if t == 0 or bool((mx[g] > 8.0).any()):
+                    delta = mx[g] if t == 0 else mx[g].clamp_min(0.0)
+                    m[g] += delta
+                    s[g] -= delta
+                    stale = defect == "stale_scale" or (defect == "stale_scale_8_to_16" and bool(((delta > 8.0) & (delta <= 16.0)).any()))
+                    if t != 0 and not stale:
+                        o[g] *= torch.exp2(-delta)
+                        l[g] *= torch.exp2(-delta)
+        p = torch.exp2(s).to(torch.bfloat16)
+        if defect == "p_4_bits":
+            p = (p.view(torch.int16) & -16).view(torch.bfloat16)     # 7 stored significand bits -> 3 (+ the hidden one)
+        if defect == "swap_v_columns" and t == 1:
+            vs = vs.clone()
+            vs[[3, 17]] = vs[[17, 3]]
+        o += p.float() @ vs
+        if not (defect == "rowsum_tile0" and t > 0):
+            l += p.float().sum(dim=1, keepdim=True)
+    if defect == "rowsum_tile0":
+        l = l * (kv_pad // 64)     # (scaled so that the defect is not a trivial factor: still the wrong sum)
+    out = (o / l).to(torch.bfloat16)
+    if defect == "row_xor_32":
+        idx = torch.arange(Lq) ^ 32
+        out = out[torch.where(idx < Lq, idx, torch.arange(Lq))]
+    return out
+
+
+ATTN_LQ = 128
+DEFECTS = ("drop_last_key", "swap_v_columns", "stale_scale", "stale_scale_8_to_16", "rowsum_tile0", "p_4_bits", "row_xor_32", "mask_at_kv_pad")
+
+
+@pytest.fixture(scope="module")
+def attn_cases():
+    """(family, kv_len) -> operands, float64 reference and bound; computed once, never modified."""
+    cases = {}
+    for kv_len in (1024, 65, 321):
+        for name, build in fam.FAMILIES.items():
+            if (name == "ramps" and kv_len < 320) or (name == "two_key" and kv_len % 64 == 0):
+                continue
+            c = build(ATTN_LQ, kv_len, 100 + kv_len)
+            kv_pad = -(-kv_len // 64) * 64
+            kp = torch.zeros(kv_pad, fam.HD, dtype=torch.bfloat16)
+            vp = torch.zeros(kv_pad, fam.HD, dtype=torch.bfloat16)
+            kp[:kv_len], vp[:kv_len] = fam.prep_k(c["k"]), c["v"]
+            # what a buffer prepared for a longer text holds behind kv_len: finite, non-zero (only the kv_pad mask defect reads it)
+            g = torch.Generator().manual_seed(kv_len)
+            kp_dirty, vp_dirty = kp.clone(), vp.clone()
+            kp_dirty[kv_len:] = (0.2 * torch.randn(kv_pad - kv_len, fam.HD, generator=g)).to(torch.bfloat16)
+            vp_dirty[kv_len:] = torch.randn(kv_pad - kv_len, fam.HD, generator=g).to(torch.bfloat16)
+            ref = nm.attention_ref(c["q"].double(), kp[:kv_len].double(), vp[:kv_len].double(), targets=c["targets"])
+            assert ref.vacuous == 0
+            if c["targets"] is not None:
+                fam.check_targets(ref, c, f"{name} kv_len={kv_len}")
+            if name == "ramps":
+                fam.check_ladders(ref.logits, c["levels"], f"ramps kv_len={kv_len}")
+            cases[name, kv_len] = dict(c, kp=kp_dirty, vp=vp_dirty, ref=ref, kv_len=kv_len)
+    return cases
+
+
+def _passes(out, case):
+    rep = nm.Bound("attention").add(out, case["ref"].out, case["ref"].bound)
+    return rep.bad == 0
+
+
+def test_attention_emulation_passes_on_every_family(attn_cases):
+    for (name, kv_len), c in attn_cases.items():
+        out = emulate_d72(c["q"], c["kp"], c["vp"], kv_len)
+        nm.Bound(f"d72 emulation, {name}, kv_len={kv_len}").add(out, c["ref"].out, c["ref"].bound).check()
+        if c["expect"] is not None:     # retrieval / two-key: v of the targets to about one bf16 ulp
+            assert ((out.double() - c["expect"]).abs() <= 2.0**-7 * c["expect"].abs() + 2.0**-9).all()
+
+
+def test_attention_emulation_without_running_max_passes(attn_cases):
+    """Subtract |q^| k_bound (k_bound = the largest Kp row norm) instead of a running maximum: same softmax, same bound with M raised."""
+    for (name, kv_len), c in attn_cases.items():
+        kb = c["kp"][:kv_len].float().norm(dim=1).max()
+        m = c["q"].float().norm(dim=1) * kb
+        if float(m.max()) > 120.0:      # (far outside the kernels' promise |q| k_bound <= 60: P would leave fp32's range)
+            continue
+        out = emulate_d72(c["q"], c["kp"], c["vp"], kv_len, static_m=m)
+        ref = nm.attention_ref(c["q"].double(), c["kp"][:kv_len].double(), c["vp"][:kv_len].double(), m_extra=m.double())
+        nm.Bound(f"d72 emulation without running max, {name}, kv_len={kv_len}").add(out, ref.out, ref.bound).check()
+
+
+# which families must catch which planted defect (at least these; the test also requires that NOTHING passes everywhere)
+CAUGHT_BY = {
+    ("drop_last_key", 1024): ("retrieval",), ("drop_last_key", 65): ("retrieval", "two_key"),
+    ("swap_v_columns", 1024): ("retrieval",), ("stale_scale", 1024): ("ramps",), ("stale_scale_8_to_16", 1024): ("ramps",), ("rowsum_tile0", 1024): ("diffuse", "retrieval"),
+    ("p_4_bits", 1024): ("diffuse",), ("row_xor_32", 1024): ("diffuse", "retrieval"), ("mask_at_kv_pad", 65): ("diffuse",),
+    ("mask_at_kv_pad", 321): ("diffuse", "ramps"),
+}
+
+
+@pytest.mark.parametrize("defect,kv_len", sorted(CAUGHT_BY))
+def test_attention_planted_defect_fails(attn_cases, defect, kv_len):
+    caught = {name for (name, n), c in attn_cases.items() if n == kv_len and not _passes(emulate_d72(c["q"], c["kp"], c["vp"], kv_len, defect=defect), c)}
+    print(f"{defect} at kv_len={kv_len}: caught by {sorted(caught)}")
+    assert set(CAUGHT_BY[defect, kv_len]) <= caught, f"{defect} at kv_len={kv_len} is caught only by {sorted(caught)}"
+
+
+def test_attention_bound_fp32_denominator_form():
+    """The temporal contract (weights normalised in fp32, THEN rounded to bf16) passes the "fp32" form; on a two-key row (weights 1/2)
+    it also passes the "rounded" form, but on diffuse rows it must not be held to it: the rounded weights no longer sum to 1."""
+    c = fam.diffuse(64, 40, 5)
+    q, k, v = c["q"].double() * fam.HD**-0.5, c["k"].double(), c["v"].double()
+    s = (q @ k.t()).float()
+    w = torch.softmax(s, dim=1).to(torch.bfloat16)
+    out = (w.float() @ v.float()).to(torch.bfloat16)
+    ref = nm.attention_ref(q, k, v, log2_scale=1.4426950408889634, denominator="fp32")
+    nm.check_elementwise(out, ref.out, ref.bound, "fp32-denominator emulation")
+    out_bad = (w.float() @ v.float().roll(1, 0)).to(torch.bfloat16)
+    with pytest.raises(AssertionError, match="outside the bound"):
+        nm.check_elementwise(out_bad, ref.out, ref.bound, "fp32-denominator emulation, v shifted by one key")

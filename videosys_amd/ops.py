@@ -460,7 +460,11 @@ def flash_attn(q, q_norm_w, kp, vt, out, batch, heads, q_len, kv_len, eps=1e-6, 
     ragged last tile) — never with a kv_len shorter than the buffers were prepared for.  The masked forms (default, k_norm_bound) READ the
     Kp rows and Vt columns behind kv_len up to the end of the last 64-key tile and give them the weight 0 by masking, not by
     skipping: both must hold FINITE values (NaN in either makes every output element NaN; include/videosys_amd.h).  attn_prep_kv
-    leaves zeros there, a shorter kv_len inside a longer prepared buffer real K / V values."""
+    leaves zeros there, a shorter kv_len inside a longer prepared buffer real K / V values.
+    Rounding contract (held element-wise by tests/test_gpu_numerics_attention.py): q^ = bf16(bf16(q rstd) w) (q bit for bit without
+    q_norm_w), logits q^ . Kp accumulated in fp32 in the exp2 domain, P = 2^(s - m) rounded to bf16, the row sum taken from the same
+    rounded P (the ones rows of Vt ride on the PV product), O and the sum rescaled only when a tile's maximum exceeds the adopted one by
+    more than 8 (never with k_norm_bound: m = |q^| k_norm_bound), one division and one rounding of the output to bf16."""
     _chk(q, q_norm_w, kp, vt, out)
     _bf16(q, q_norm_w, kp, vt, out)
     assert q.stride(1) == 1 and out.stride(1) == 1
@@ -542,7 +546,11 @@ def rms_key_bound(q_norm_w, k_norm_w, head_dim=HEAD_DIM):
 
 
 def attn_temporal(qkv, C, q_norm_w, k_norm_w, rope_cos, rope_sin, out, B, T, S, heads, eps=1e-6):
-    """qkv [B*T*S, 3C] rows ordered (b,t,s); out [B*T*S, C]."""
+    """qkv [B*T*S, 3C] rows ordered (b,t,s); out [B*T*S, C].
+    Rounding contract (tests/test_gpu_numerics_attention.py): q^ and k^ carry at most the reference's roundings (x rstd, * w, rotation,
+    q * 72^-1/2, each to bf16; the default kernels round once), logits and softmax in fp32 with the row sum of the UNROUNDED
+    probabilities, the normalised weights p / l rounded to bf16 before the PV product (no running maximum: all T keys at once), fp32
+    accumulation, one rounding of the output."""
     _chk(qkv, q_norm_w, k_norm_w, rope_cos, rope_sin, out)
     _bf16(qkv, q_norm_w, k_norm_w, out)
     assert qkv.stride(1) == 1 and out.stride(1) == 1
@@ -636,7 +644,11 @@ def attn_prep_kv64(k, v, ln_w, ln_b, rope_cos, rope_sin, rope_start, kp, vt, bat
 
 
 def flash_attn64(q, ln_w, ln_b, rope_cos, rope_sin, rope_start, kp, vt, out, batch, heads, q_len, kv_len, eps=1e-6, k_norm_bound=None):
-    """``k_norm_bound``: the promise about the Kp row norms (vsys_flash_attn_d64_kb; ln_key_bound); None = none."""
+    """``k_norm_bound``: the promise about the Kp row norms (vsys_flash_attn_d64_kb; ln_key_bound); None = none.
+    Rounding contract (held element-wise by tests/test_gpu_numerics_attention.py): as flash_attn with
+    q^ = bf16(rope(bf16(LN(q) w + b))); P = 2^(s - m) rounded to bf16 feeds the PV product; the row sum is added up on the VALU from
+    the fp32 P BEFORE that rounding (the 32-row kernel, attention64.hip) or comes from the rounded P on the matrix pipe (the w64
+    stream, attention64_w64.hip: from 2048 keys); the same deferred rescale (threshold 8, exp2 domain), one division, bf16 output."""
     _chk(q, ln_w, ln_b, rope_cos, rope_sin, kp, vt, out)
     _bf16(q, ln_w, ln_b, kp, vt, out)
     assert q.stride(1) == 1 and out.stride(1) == 1
