@@ -352,6 +352,24 @@ int vsys_attn_temporal_d72(const void* qkv, int64_t row_stride, int64_t C, const
                            const void* rope_cos_f32, const void* rope_sin_f32, void* out, int64_t out_stride, int64_t B,
                            int64_t T, int64_t S, int64_t heads, float eps, void* stream);
 
+/* Temporal self-attention of Vchitect-2.0 at head dim 64 (VchitectAttnProcessor.temporal_attention, attentions.py:705-764, without
+ * the projections): every token (b, s'), s' in [0, S + L), attends over its own T frames; the L text tokens of a frame follow its S
+ * video tokens.  Video rows ordered (b, t, s) in q_vid / k_vid / v_vid / out_vid, text rows ordered (b, t, l) in q_txt / k_txt /
+ * v_txt / out_txt, every tensor with its own row stride (elements, % 8 == 0, >= heads * 64; pointers 16-byte aligned), head h at
+ * column 64 h.  No qk-norm.  RoPE as apply_rotary_emb (:654-665): the interleaved pair (2i, 2i + 1) of frame t times
+ * (cos, sin)[t][i] in fp32, cast back to bf16 (cos / sin fp32 [T, 32]; both NULL = none).  fp32 softmax, scale 1/8.  Any T >= 1,
+ * heads >= 1, S + L >= 1 (S == 0 or L == 0: that side's pointers are not read). */
+int vsys_attn_temporal_d64(const void* q_vid, int64_t q_vid_stride, const void* k_vid, int64_t k_vid_stride, const void* v_vid,
+                           int64_t v_vid_stride, const void* q_txt, int64_t q_txt_stride, const void* k_txt, int64_t k_txt_stride,
+                           const void* v_txt, int64_t v_txt_stride, const void* rope_cos_f32, const void* rope_sin_f32, void* out_vid,
+                           int64_t out_vid_stride, void* out_txt, int64_t out_txt_stride, int64_t B, int64_t T, int64_t S, int64_t L,
+                           int64_t heads, void* stream);
+
+/* out[r] = bf16(bf16(a[r] * scale) + b[r]) over rows of C bf16 (C % 8 == 0; strides in elements, % 8 == 0), out may be a or b:
+ * `hidden_states * 1.1 + cross_output` of VchitectAttnProcessor (attentions.py:899) with the reference's two roundings. */
+int vsys_scale_add_rows(const void* a, int64_t a_stride, const void* b, int64_t b_stride, void* out, int64_t out_stride, int64_t rows,
+                        int64_t C, float scale, void* stream);
+
 /* Up to 16 vsys_copy_4d problems over one (src, dst) pair in a single launch: the per-peer pack (or unpack) pieces of a DSP /
  * Ulysses all-to-all (comm.py:104-108,282-304; cogvideox_transformer_3d.py:45-86).  desc (HOST) holds nops x 14 int64:
  * src_off, dst_off, n0, n1, n2, run, ss0, ss1, ss2, ds0, ds1, ds2, n1_valid, n2_valid (elements; run % 8 == 0). */
@@ -563,7 +581,9 @@ int vsys_softmax_rows(const void* s_f32, void* p, int64_t rows, int64_t n, int64
 #define VSYS_OP_ATTN_PREP_KV_VARLEN          55
 #define VSYS_OP_FLASH_ATTN_D72_VARLEN        56
 #define VSYS_OP_GEMM_BF16_LN_QKV_KV          57
-#define VSYS_OP_COUNT 58
+#define VSYS_OP_ATTN_TEMPORAL_D64            58
+#define VSYS_OP_SCALE_ADD_ROWS               59
+#define VSYS_OP_COUNT 60
 /* <<< VSYS_OP codes */
 
 #define VSYS_CMD_MAX_INT 24

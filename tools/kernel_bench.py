@@ -186,6 +186,18 @@ def main():
             ms = timeit(lambda: ops.attn_temporal(qkv, C, qw, qw, cos, sin, ao, 2, 19, 1024, H), args.reps)
             res.setdefault("attn_temporal" + (f"_v{fv}" if fv else ""), []).append((ms, (269.0 + 89.7) / ms))  # GB/s
     lib.vsys_tune_flash_variant(0)
+    # Vchitect-2B temporal attention (24 heads x 64 = 1536 wide, 24 layers) at the pipeline's defaults: 288 x 480, 40 frames -> latent
+    # 36 x 60, patch 2 -> S = 18 x 30 = 540 video tokens; L = 77 CLIP + 256 T5 text tokens per frame; one sample (as the pipeline calls it)
+    from videosys_amd import vchitect_ops as vops
+    vT, vS, vL, vH = 40, 18 * 30, 333, 24
+    vqkv, vtxt = rnd(vT * vS, 3 * vH * 64), [rnd(vT * vL, vH * 64) for _ in range(3)]
+    vo, vot = torch.empty(vT * vS, vH * 64, dtype=torch.bfloat16, device=dev), torch.empty(vT * vL, vH * 64, dtype=torch.bfloat16, device=dev)
+    ang = torch.outer(torch.arange(vT, dtype=torch.float32), 1.0 / (1e6 ** (torch.arange(0, 64, 2).float() / 64)))
+    vcos, vsin = ang.cos().to(dev), ang.sin().to(dev)
+    vq, vk, vv = (vqkv[:, i * vH * 64:(i + 1) * vH * 64] for i in range(3))
+    ms = timeit(lambda: vops.attn_temporal64(vq, vk, vv, *vtxt, vcos, vsin, vo, vot, 1, vT, vS, vL, vH), args.reps)
+    res["attn_temporal64_vchitect2b"] = [(ms, 4 * vT * (vS + vL) * vH * 64 * 2 / 1e6 / ms)]  # GB/s of q + k + v + out (x 24 layers per step)
+    del vqkv, vtxt, vo, vot
     ms = timeit(lambda: ops.adaln_modulate(x, mod[0, :C], mod[0, C:2 * C], N // 2, 6 * C, out=ao), args.reps)
     res["adaln_modulate"] = [(ms, 179.3 / ms)]  # GB/s
     ms = timeit(lambda: ops.add_rows(ao, x), args.reps)

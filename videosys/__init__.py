@@ -36,6 +36,7 @@ _MODULES = {
     "models.transformers.open_sora_transformer_3d": "stdit3",       # STDiT3, STDiT3Config, STDiT3_XL_2
     "models.transformers.latte_transformer_3d": "latte",            # LatteT2V
     "models.transformers.cogvideox_transformer_3d": "cogvideox",    # CogVideoXTransformer3DModel
+    "models.transformers.vchitect_transformer_3d": "vchitect",      # VchitectXLTransformerModel, JointTransformerBlock
     "models.autoencoders.autoencoder_kl_open_sora": "vae_open_sora",    # OpenSoraVAE_V1_2
     "models.autoencoders.autoencoder_kl_cogvideox": "vae_cogvideox",    # AutoencoderKLCogVideoX
     "pipelines.open_sora": "pipeline_open_sora",              # OpenSoraConfig, OpenSoraPABConfig, OpenSoraPipeline

@@ -545,6 +545,23 @@ __global__ void add_rows_kernel(bf16_t* __restrict__ x, const bf16_t* __restrict
   }
 }
 
+// out = bf16(bf16(a * scale) + b), row by row (each operand with its own row stride): `hidden_states * 1.1 + cross_output` of
+// VchitectAttnProcessor (attentions.py:899) with the two bf16 roundings of the reference's two tensor ops.
+__global__ void scale_add_rows_kernel(const bf16_t* __restrict__ a, int64_t lda, const bf16_t* __restrict__ b, int64_t ldb,
+                                      bf16_t* __restrict__ out, int64_t ldo, int64_t rows, int C8, float scale) {
+  const int64_t total = rows * C8;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / C8;
+    const int c = (int)(i - r * C8) * 8;
+    float x[8], y[8];
+    unpack8(*reinterpret_cast<const uint4*>(a + r * lda + c), x);
+    unpack8(*reinterpret_cast<const uint4*>(b + r * ldb + c), y);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[e] = bf2f(f2bf(x[e] * scale)) + y[e];
+    *reinterpret_cast<uint4*>(out + r * ldo + c) = pack8(x);
+  }
+}
+
 // Generic 4-D strided copy of rows of C bf16 (C % 8 == 0): dst[i0][i1][i2][:] = src[i0][i1][i2][:] or zero when
 // (i1 >= n1_valid || i2 >= n2_valid) — the zero-pad of all_to_all_with_pad.  Strides in elements.
 __global__ void copy_4d_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst, int n0, int n1, int n2, int C,
@@ -778,6 +795,20 @@ int launch_add_rows(bf16_t* x, const bf16_t* y, int64_t n, hipStream_t stream) {
   int64_t grid = (n8 + 255) / 256;
   if (grid > 2048 * 4) grid = 2048 * 4;
   hipLaunchKernelGGL(add_rows_kernel, dim3((unsigned)grid), dim3(256), 0, stream, x, y, n8);
+  return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
+}
+
+int launch_scale_add_rows(const bf16_t* a, int64_t lda, const bf16_t* b, int64_t ldb, bf16_t* out, int64_t ldo, int64_t rows, int C,
+                          float scale, hipStream_t stream) {
+  if (rows < 0 || C < 0) return VSYS_ERR_SHAPE;
+  if (rows == 0 || C == 0) return 0;
+  if (C % 8 || lda < C || ldb < C || ldo < C) return VSYS_ERR_SHAPE;
+  if ((lda % 8) || (ldb % 8) || (ldo % 8) || reinterpret_cast<uintptr_t>(a) % 16 || reinterpret_cast<uintptr_t>(b) % 16 ||
+      reinterpret_cast<uintptr_t>(out) % 16)
+    return VSYS_ERR_ALIGN;
+  int64_t grid = (rows * (C / 8) + 255) / 256;
+  if (grid > 2048 * 4) grid = 2048 * 4;
+  hipLaunchKernelGGL(scale_add_rows_kernel, dim3((unsigned)grid), dim3(256), 0, stream, a, lda, b, ldb, out, ldo, rows, C / 8, scale);
   return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
 }
 

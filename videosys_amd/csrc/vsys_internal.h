@@ -271,4 +271,13 @@ int launch_attn_temporal_d72(const bf16_t* qkv, int64_t row_stride, int C, const
                              const float* rope_cos, const float* rope_sin, bf16_t* out, int64_t out_stride, int B, int T,
                              int S, int heads, float eps, hipStream_t stream);
 
+// Vchitect-2.0: temporal attention at head dim 64 over separate video / text row tensors (attention_t64.hip)
+int launch_attn_temporal_d64(const bf16_t* q_vid, int64_t q_vid_ld, const bf16_t* k_vid, int64_t k_vid_ld, const bf16_t* v_vid,
+                             int64_t v_vid_ld, const bf16_t* q_txt, int64_t q_txt_ld, const bf16_t* k_txt, int64_t k_txt_ld,
+                             const bf16_t* v_txt, int64_t v_txt_ld, const float* rope_cos, const float* rope_sin, bf16_t* out_vid,
+                             int64_t out_vid_ld, bf16_t* out_txt, int64_t out_txt_ld, int B, int T, int S, int L, int heads,
+                             hipStream_t stream);
+int launch_scale_add_rows(const bf16_t* a, int64_t lda, const bf16_t* b, int64_t ldb, bf16_t* out, int64_t ldo, int64_t rows, int C,
+                          float scale, hipStream_t stream);
+
 }  // namespace vsys
