@@ -507,6 +507,20 @@ int vsys_vae_first_im2col(const void* z, int64_t F, int64_t H, int64_t W, int64_
  * below tskip dropped (VAE_Temporal.decode's x[:, :, time_padding:], autoencoder_kl_open_sora.py:461). */
 int vsys_extract_planar(const void* x, const int64_t* grid, int64_t N, int64_t ldx, int64_t nc, int64_t tskip, void* out,
                         int64_t Ftot, int64_t f0, void* stream);
+/* First layer of the SD3 VAE decode of the Vchitect-2.0 pipeline (pipeline_vchitect.py:980-983: `latents / scaling_factor +
+ * shift_factor` on the bf16 latents, then AutoencoderKL.decode -> Decoder.conv_in; the SD3 VAE has 16 latent channels and no
+ * post_quant_conv): fp32 latents z[F][Cz][H][W] (1 <= Cz <= 32; `latents[0]` of the pipeline's [1, F, Cz, h, w] tensor as it is) ->
+ * bf16 im2col rows [F*H*W, kcols] of the 3 x 3 conv (kcols % 32 == 0, kcols >= 9 Cz; column = tap * Cz + channel, tap = 3 dy + dx;
+ * zero outside the image and from column 9 Cz on).  Value: bf16(bf16(bf16(z) / scaling_factor) + shift_factor), the division a
+ * correctly rounded fp32 division.  No VSYS_OP code (the decode is not part of a recorded step). */
+int vsys_vae_first_im2col_nc(const void* z_f32, int64_t F, int64_t Cz, int64_t H, int64_t W, int64_t kcols, float scaling_factor,
+                             float shift_factor, void* out, void* stream);
+/* Last layer of the same decode (pipeline_vchitect.py:984, VaeImageProcessor.postprocess(image, "pil") of diffusers): the first 3
+ * channels of the interior rows [*, ldx] of a conv-output grid (grid descriptor and ldx as vsys_extract_planar; ldx % 4 == 0, x 8-byte
+ * aligned) -> uint8 out[Ftot][H][W][3], frames f0 .. f0 + N*T - 1 (f0 + N*T <= Ftot).  Value: d = clamp(bf16(bf16(x / 2) + 0.5), 0, 1),
+ * byte = round-half-even(float(d) * 255).  No VSYS_OP code. */
+int vsys_pixels_to_u8(const void* x, const int64_t* grid, int64_t N, int64_t ldx, void* out_u8, int64_t Ftot, int64_t f0,
+                      void* stream);
 /* row softmax over the first n of ld columns, fp32 [rows, ld] -> bf16 [rows, ld] with zeros in columns n..ld-1 (mid-block
  * attention of the 2-D VAE — diffusers Attention under VideoAutoencoderKL.decode / .encode, autoencoder_kl_open_sora.py:503-538 —
  * keys padded to the 128-column tile; n % 4 == 0, ld % 4 == 0, ld <= 8192). */

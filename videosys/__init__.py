@@ -45,6 +45,8 @@ _MODULES = {
     "pipelines.latte.pipeline_latte": "pipeline_latte",
     "pipelines.cogvideox": "pipeline_cogvideox",
     "pipelines.cogvideox.pipeline_cogvideox": "pipeline_cogvideox",
+    "pipelines.vchitect": "pipeline_vchitect",                # VchitectConfig, VchitectPABConfig, VchitectXLPipeline
+    "pipelines.vchitect.pipeline_vchitect": "pipeline_vchitect",
 }
 
 

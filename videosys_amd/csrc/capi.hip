@@ -707,6 +707,22 @@ int vsys_extract_planar(const void* x, const int64_t* grid, int64_t N, int64_t l
   return launch_extract_planar(B16(x), g, (int)N, (int)ldx, (int)nc, (int)tskip, B16(out), Ftot, (int)f0, S(stream));
 }
 
+int vsys_vae_first_im2col_nc(const void* z_f32, int64_t F, int64_t Cz, int64_t H, int64_t W, int64_t kcols, float scaling_factor,
+                             float shift_factor, void* out, void* stream) {
+  if (!z_f32 || !out) return VSYS_ERR_ARG;
+  if (!fits_int(F) || !fits_int(Cz) || !fits_int(H) || !fits_int(W) || !fits_int(kcols)) return VSYS_ERR_SHAPE;
+  return launch_vae_first_im2col_nc(reinterpret_cast<const float*>(z_f32), (int)F, (int)Cz, (int)H, (int)W, (int)kcols, scaling_factor,
+                                    shift_factor, B16(out), S(stream));
+}
+
+int vsys_pixels_to_u8(const void* x, const int64_t* grid, int64_t N, int64_t ldx, void* out_u8, int64_t Ftot, int64_t f0,
+                      void* stream) {
+  VaeGrid g;
+  if (!x || !out_u8 || !to_grid(grid, g)) return VSYS_ERR_ARG;
+  if (!fits_int(N) || !fits_int(ldx)) return VSYS_ERR_SHAPE;
+  return launch_pixels_to_u8(B16(x), g, (int)N, ldx, reinterpret_cast<uint8_t*>(out_u8), Ftot, f0, S(stream));
+}
+
 int vsys_softmax_rows(const void* s_f32, void* p, int64_t rows, int64_t n, int64_t ld, void* stream) {
   if (!s_f32 || !p) return VSYS_ERR_ARG;
   if (!fits_int(n) || !fits_int(ld)) return VSYS_ERR_SHAPE;

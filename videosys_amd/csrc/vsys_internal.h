@@ -150,6 +150,12 @@ int launch_extract_planar(const bf16_t* x, const VaeGrid& g, int N, int ldx, int
                           hipStream_t stream);
 int launch_softmax_rows(const float* s, bf16_t* p, int64_t rows, int n, int ld, hipStream_t stream);
 
+// SD3 VAE ends of the Vchitect-2.0 decode (vae_sd3.hip)
+int launch_vae_first_im2col_nc(const float* z, int F, int Cz, int H, int W, int kcols, float scaling, float shift, bf16_t* out,
+                               hipStream_t stream);
+int launch_pixels_to_u8(const bf16_t* x, const VaeGrid& g, int N, int64_t ldx, uint8_t* out, int64_t Ftot, int64_t f0,
+                        hipStream_t stream);
+
 // T5 encoder pieces (t5_ops.hip)
 int launch_gather_rows(const bf16_t* table, const int64_t* ids, bf16_t* out, int64_t n, int C, int64_t vocab, hipStream_t stream);
 int launch_rms_norm_rows(const bf16_t* x, const bf16_t* w, bf16_t* y, int64_t rows, int C, float eps, hipStream_t stream);

@@ -613,11 +613,13 @@ def im2col_patch(z_f32, B, p):
     return out
 
 
-def unpatchify_cvx(x, B, F, Hp, Wp, Cout, p):
-    _chk(x)
+def unpatchify_cvx(x, B, F, Hp, Wp, Cout, p, out=None):
+    _chk(x, out)
     _bf16(x)
     assert x.stride(1) == 1
-    out = torch.empty(B, F, Cout, Hp * p, Wp * p, dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty(B, F, Cout, Hp * p, Wp * p, dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * F * Cout * Hp * p * Wp * p
     lib = _lib.load()
     _call("vsys_unpatchify_cvx", _p(x), x.stride(0), _p(out), B, F, Hp, Wp, Cout, p)
     return out

@@ -7,7 +7,8 @@ vsys_flash_attn_d64 without norm / RoPE for the joint spatial and the cross atte
 (VchitectXLTransformerModel, JointTransformerBlock below) adds patch embed with the cropped 2-D sincos table, AdaLayerNormZero /
 AdaLayerNormContinuous (vsys_ln_modulate), FeedForward (bias + GELU and gate + residual GEMM epilogues), the time-text embedding
 (vsys_timestep_embedding, vsys_linear_small), proj_out and unpatchify, with the reference's constructor config and state-dict names.
-Not built: the Vchitect pipeline (CLIP / T5 encoders, SD3 VAE, scheduler) and sequence parallelism.
+The pipeline around it (flow-match sampler, T5, SD3 VAE decode) is pipeline_vchitect.py.  Not built: the two CLIP text encoders (they
+are injected objects there) and sequence parallelism.
 
 Every launch goes through ops._call and every buffer is resident, so a step can be recorded once (program.Recorder) and replayed.
 
@@ -297,6 +298,7 @@ class VchitectXLTransformerModel:
         self._ws = {}
         self._pos_crop = {}
         self.parallel_manager = None
+        self.use_programs = True     # samplers record a step once and replay it (pipeline_vchitect.py); False: eager issue
         self.pos_embed = sincos_2d(C, pos_embed_max_size, sample_size // patch_size)      # [max * max, C] fp32 (PatchEmbed.pos_embed)
 
     TOP = ("pos_embed.proj", "time_text_embed.timestep_embedder.linear_1", "time_text_embed.timestep_embedder.linear_2",
@@ -359,6 +361,15 @@ class VchitectXLTransformerModel:
             self._ws[name] = b
         return b[:n].view(*shape)
 
+    def step_timesteps(self, rows: int) -> torch.Tensor:
+        """The resident fp32 [B * F] buffer the timestep embedding reads.  forward() fills it from ``timestep``; a sampler that replays a
+        recorded step writes the step's timestep here instead (the one per-step input besides the latents)."""
+        b = self._ws.get("timesteps")
+        if b is None or b.numel() < rows:
+            b = torch.empty(rows, dtype=torch.float32, device=self.device)
+            self._ws["timesteps"] = b
+        return b[:rows]
+
     def cropped_pos_embed(self, hp: int, wp: int) -> torch.Tensor:
         """PatchEmbed.cropped_pos_embed: the centre hp x wp window of the max x max table, bf16 [hp * wp, C] on the device."""
         if (hp, wp) not in self._pos_crop:
@@ -372,7 +383,8 @@ class VchitectXLTransformerModel:
 
     @torch.no_grad()
     def forward(self, hidden_states, encoder_hidden_states=None, pooled_projections=None, timestep=None, joint_attention_kwargs=None,
-                return_dict: bool = True):
+                return_dict: bool = True, *, out: torch.Tensor = None):
+        """``out`` (an extension): a contiguous fp32 buffer of B * F * out_channels * H * W values the prediction is written to."""
         from types import SimpleNamespace
 
         w, C, cfg, dev = self.w, self.inner_dim, self.config, self.device
@@ -393,7 +405,9 @@ class VchitectXLTransformerModel:
         if ts.numel() != B:
             ts = ts.expand(B) if ts.numel() == 1 else ts[:B]
         pooled = pooled_projections.to(device=dev, dtype=self.dtype).reshape(B, -1)
-        tp = ops.timestep_embedding(ts.repeat(F).to(dev).contiguous(), 256)
+        tsb = self.step_timesteps(BF)
+        tsb.copy_(ts.repeat(F))
+        tp = ops.timestep_embedding(tsb, 256)
         te = "time_text_embed.timestep_embedder."
         e1 = ops.linear_small(tp, w[te + "linear_1.weight"], w[te + "linear_1.bias"], act_out=ops.ACT_SILU)
         temb = ops.linear_small(e1, w[te + "linear_2.weight"], w[te + "linear_2.bias"])
@@ -416,7 +430,7 @@ class VchitectXLTransformerModel:
         xo = ops.ln_modulate(x, None, None, mod_out[0, C:2 * C], mod_out[0, 0:C], F * S, mod_stride=2 * C, eps=1e-6,
                              out=self._buf("xn", (BF * S, C)))
         po = ops.gemm(xo, w["_proj_out.weight"], w["_proj_out.bias"], out=self._buf("proj", (BF * S, 192)))
-        out = ops.unpatchify_cvx(po, B, F, Hp, Wp, self.out_channels, p).view(BF, self.out_channels, Hh, Ww)
+        out = ops.unpatchify_cvx(po, B, F, Hp, Wp, self.out_channels, p, out=out).view(BF, self.out_channels, Hh, Ww)
         if not return_dict:
             return (out,)
         return SimpleNamespace(sample=out)

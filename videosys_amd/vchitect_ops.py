@@ -1,11 +1,13 @@
-"""Tensor-level wrappers of the two entry points that exist for Vchitect-2.0 (include/videosys_amd.h: vsys_attn_temporal_d64,
-vsys_scale_add_rows), on the launch route of videosys_amd.ops (torch.ops.vsys.launch / ctypes, recorded by program.py).  HIP device
-tensors only, no eager fallback.  Guard-band tests: tests/test_gpu_isolation_vchitect.py."""
+"""Tensor-level wrappers of the entry points that exist for Vchitect-2.0 (include/videosys_amd.h: vsys_attn_temporal_d64,
+vsys_scale_add_rows of the transformer; vsys_vae_first_im2col_nc, vsys_pixels_to_u8 of the SD3 VAE decode), on the launch route of
+videosys_amd.ops (torch.ops.vsys.launch / ctypes, recorded by program.py; the two decode kernels have no op code and go through
+ctypes).  HIP device tensors only, no eager fallback.  Guard-band tests: tests/test_gpu_isolation_vchitect.py,
+tests/test_gpu_isolation_vchitect_pipeline.py."""
 from __future__ import annotations
 
 import torch
 
-from .ops import _bf16, _call, _chk, _p
+from .ops import VaeGrid, _bf16, _call, _chk, _p
 
 
 def attn_temporal64(q_vid, k_vid, v_vid, q_txt, k_txt, v_txt, rope_cos, rope_sin, out_vid, out_txt, B, T, S, L, heads):
@@ -38,4 +40,26 @@ def scale_add_rows(a, b, scale, out=None):
     _bf16(a, b, out)
     assert a.dim() == 2 and a.shape == b.shape == out.shape and a.stride(1) == 1 and b.stride(1) == 1 and out.stride(1) == 1
     _call("vsys_scale_add_rows", _p(a), a.stride(0), _p(b), b.stride(0), _p(out), out.stride(0), a.shape[0], a.shape[1], float(scale))
+    return out
+
+
+def vae_first_im2col_nc(z_f32, kcols, scaling_factor, shift_factor):
+    """z fp32 [F, Cz, H, W] (Cz <= 32) -> bf16 [F*H*W, kcols] rows of a 3 x 3 conv over bf16(bf16(bf16(z) / scaling_factor) +
+    shift_factor): column tap * Cz + c, zero outside the image and from column 9 Cz on (include/videosys_amd.h)."""
+    _chk(z_f32)
+    assert z_f32.dtype == torch.float32 and z_f32.dim() == 4 and z_f32.is_contiguous()
+    F, Cz, H, W = z_f32.shape
+    out = torch.empty(F * H * W, kcols, dtype=torch.bfloat16, device=z_f32.device)
+    _call("vsys_vae_first_im2col_nc", _p(z_f32), F, Cz, H, W, kcols, float(scaling_factor), float(shift_factor), _p(out))
+    return out
+
+
+def pixels_to_u8(x, g: VaeGrid, out, f0):
+    """first 3 channels of the interior rows of grid g (x [g.rows, ldx] bf16, row-strided) -> out uint8 [Ftot, H, W, 3], frames
+    f0 .. f0 + g.n * g.T - 1: round-half-even(clamp(bf16(bf16(x / 2) + 0.5), 0, 1) * 255) (include/videosys_amd.h)."""
+    _chk(x, out)
+    _bf16(x)
+    assert x.dim() == 2 and x.shape[0] == g.rows and x.stride(1) == 1 and x.shape[1] >= 3
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 4 and tuple(out.shape[1:]) == (g.H, g.W, 3)
+    _call("vsys_pixels_to_u8", _p(x), g._c, g.n, x.stride(0), _p(out), out.shape[0], f0)
     return out
