@@ -807,6 +807,7 @@ NOT_COVERED = {
     "kv_set_constant_rows": "torch fills at set-up time, no kernel of the library",
     "rms_key_bound": "host arithmetic on two weight vectors",
     "ln_key_bound": "host arithmetic on the norm weights",
+    "static_max_allowed": "reads the VSYS_FLASH_STATIC switch (host side), no launch",
     "skinny_split": "host arithmetic",
     # out of scope of the guard-band tests
     "p2p_exchange": "peer-to-peer exchange: writes into other processes' memory by design, needs several ranks",

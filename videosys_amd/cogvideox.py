@@ -27,14 +27,9 @@ import numpy as np
 import torch
 
 from . import ops, pab
-from .utils import same_tensor
-
-
-def _sincos_1d(embed_dim: int, pos: np.ndarray) -> np.ndarray:
-    omega = np.arange(embed_dim // 2, dtype=np.float64) / (embed_dim / 2.0)
-    omega = 1.0 / 10000**omega
-    out = np.einsum("m,d->md", pos.reshape(-1), omega)
-    return np.concatenate([np.sin(out), np.cos(out)], axis=1)
+from .modules import sincos_1d
+from .utils import load_weights, same_tensor
+from .workspace import Workspace
 
 
 def cogvideox_pos_embed_3d(embed_dim, w, h, t, spatial_scale, temporal_scale) -> torch.Tensor:
@@ -44,8 +39,8 @@ def cogvideox_pos_embed_3d(embed_dim, w, h, t, spatial_scale, temporal_scale) ->
     gh = np.arange(h, dtype=np.float32) / spatial_scale
     gw = np.arange(w, dtype=np.float32) / spatial_scale
     grid = np.stack(np.meshgrid(gw, gh), axis=0).reshape([2, 1, h, w])
-    pos_s = np.concatenate([_sincos_1d(ds // 2, grid[0]), _sincos_1d(ds // 2, grid[1])], axis=1)
-    pos_t = _sincos_1d(dt, np.arange(t, dtype=np.float32) / temporal_scale)
+    pos_s = np.concatenate([sincos_1d(ds // 2, grid[0]), sincos_1d(ds // 2, grid[1])], axis=1)
+    pos_t = sincos_1d(dt, np.arange(t, dtype=np.float32) / temporal_scale)
     pos_s = np.repeat(pos_s[np.newaxis], t, axis=0)
     pos_t = np.repeat(pos_t[:, np.newaxis], w * h, axis=1)
     return torch.from_numpy(np.concatenate([pos_t, pos_s], axis=-1)).float().flatten(0, 1)
@@ -83,7 +78,8 @@ class CogVideoXTransformer3DModel:
         self.device, self.dtype = torch.device(device), dtype
         self.w: Dict[str, torch.Tensor] = {}
         self.parallel_manager = SimpleNamespace(sp_size=1, cp_size=1, dp_size=1, dp_rank=0, sp_group=None, cp_group=None)
-        self._ws = {}
+        self._ws = Workspace(self.device, dtype)
+        self._buf = self._ws.buf   # bound to this Workspace: _ws is cleared, never replaced (rebind _buf with it otherwise)
         self._kbounds = {}   # per block: the promise about its key norms (ops.ln_key_bound), None = none
         self._hidden_tap = None
         pf = (sample_frames - 1) // temporal_compression_ratio + 1
@@ -112,11 +108,9 @@ class CogVideoXTransformer3DModel:
     def _kbound(self, pre):
         """What lets the long-sequence attention kernel drop the running max (vsys_flash_attn_d64_kb): from the block's norm_q /
         norm_k weights, once.  VSYS_FLASH_STATIC=0 never promises."""
-        import os
-
         if pre not in self._kbounds:
             kb = None
-            if os.environ.get("VSYS_FLASH_STATIC", "1") != "0":
+            if ops.static_max_allowed():
                 g = self.w.get
                 kb = ops.ln_key_bound(g(pre + ".attn1.norm_q.weight"), g(pre + ".attn1.norm_q.bias"), g(pre + ".attn1.norm_k.weight"),
                                       g(pre + ".attn1.norm_k.bias"))
@@ -125,17 +119,10 @@ class CogVideoXTransformer3DModel:
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
         self._kbounds = {}
-        missing = [k for k in self.expected_keys() if k not in sd]
-        if strict and missing:
-            raise KeyError(f"missing keys: {missing[:8]}{'...' if len(missing) > 8 else ''}")
+        load_weights(self.w, sd, self.expected_keys(), device=self.device, dtype=self.dtype, strict=strict,
+                     reshape=("patch_embed.proj.weight",))
         dev = lambda t: t.detach().to(device=self.device, dtype=self.dtype).contiguous()
         C = self.C
-        for k in self.expected_keys():
-            if k in sd:
-                t = sd[k]
-                if k == "patch_embed.proj.weight":
-                    t = t.reshape(t.shape[0], -1)
-                self.w[k] = dev(t)
         mods_w, mods_b = [], []
         for i in range(self.L):
             p = f"transformer_blocks.{i}"
@@ -176,14 +163,6 @@ class CogVideoXTransformer3DModel:
 
     def reset_pab_state(self):
         self.attn_count = [0] * self.L
-
-    def _buf(self, name, shape, dtype=None):
-        n = int(np.prod(shape))
-        b = self._ws.get(name)
-        if b is None or b.numel() < n:
-            b = torch.empty(n, dtype=dtype or self.dtype, device=self.device)
-            self._ws[name] = b
-        return b[:n].view(*shape)
 
     def _rope(self, image_rotary_emb):
         if image_rotary_emb is None:
@@ -314,10 +293,7 @@ class CogVideoXTransformer3DModel:
 
     def _kv(self, batch, kv_len, heads=None):
         heads = heads or self.H
-        key = ("kv", batch, kv_len, heads)
-        if key not in self._ws:
-            self._ws[key] = ops.alloc_kv_buffers64(batch, heads, kv_len, self.device)
-        return self._ws[key]
+        return self._ws.once(("kv", batch, kv_len, heads), lambda: ops.alloc_kv_buffers64(batch, heads, kv_len, self.device))
 
 
 def synth_state_dict(num_layers=30, num_heads=30, head_dim=64, text_embed_dim=4096, in_channels=16, out_channels=16,

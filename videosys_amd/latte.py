@@ -28,15 +28,9 @@ import numpy as np
 import torch
 
 from . import dsp, ops, pab
-from .utils import same_tensor
-
-
-def _sincos_1d(embed_dim: int, pos: np.ndarray) -> np.ndarray:
-    """diffusers get_1d_sincos_pos_embed_from_grid ([sin | cos], float64 frequencies) — constant table."""
-    omega = np.arange(embed_dim // 2, dtype=np.float64) / (embed_dim / 2.0)
-    omega = 1.0 / 10000**omega
-    out = np.einsum("m,d->md", pos.reshape(-1), omega)
-    return np.concatenate([np.sin(out), np.cos(out)], axis=1)
+from .modules import sincos_1d
+from .utils import load_weights, same_tensor
+from .workspace import Workspace
 
 
 def latte_pos_embed_2d(embed_dim: int, gh: int, gw: int, base_size: int, interpolation_scale: float = 1.0) -> torch.Tensor:
@@ -45,15 +39,8 @@ def latte_pos_embed_2d(embed_dim: int, gh: int, gw: int, base_size: int, interpo
     grid_h = np.arange(gh, dtype=np.float32) / (gh / base_size) / interpolation_scale
     grid_w = np.arange(gw, dtype=np.float32) / (gw / base_size) / interpolation_scale
     grid = np.stack(np.meshgrid(grid_w, grid_h), axis=0).reshape([2, 1, gw, gh])
-    emb = np.concatenate([_sincos_1d(embed_dim // 2, grid[0]), _sincos_1d(embed_dim // 2, grid[1])], axis=1)
+    emb = np.concatenate([sincos_1d(embed_dim // 2, grid[0]), sincos_1d(embed_dim // 2, grid[1])], axis=1)
     return torch.from_numpy(emb).float()
-
-
-class _BlockState:
-    def __init__(self, block_idx, temporal):
-        self.block_idx, self.temporal = block_idx, temporal
-        self.attn_count = self.cross_count = self.mlp_count = 0
-        self.last_attn = self.last_cross = None
 
 
 class LatteT2V:
@@ -85,10 +72,11 @@ class LatteT2V:
         self.w: Dict[str, torch.Tensor] = {}
         self.parallel_manager = SimpleNamespace(sp_size=1, cp_size=1, dp_size=1, dp_rank=0, sp_group=None, cp_group=None)
         self._sp = None
-        self.states = [_BlockState(i // 2, bool(i % 2)) for i in range(2 * num_layers)]
-        self._pos_cache, self._ws = {}, {}
+        self.states = [pab.BlockState(i // 2, bool(i % 2)) for i in range(2 * num_layers)]
+        self._pos_cache, self._ws = {}, Workspace(self.device, dtype)
+        self._buf = self._ws.buf   # bound to this Workspace: _ws is cleared, never replaced (rebind _buf with it otherwise)
         self._text_cache = None
-        tpe = _sincos_1d(self.C, np.arange(0, video_length)[:, None].astype(np.float64))  # :1129-1130
+        tpe = sincos_1d(self.C, np.arange(0, video_length)[:, None].astype(np.float64))  # :1129-1130
         self.temp_pos_embed = torch.from_numpy(tpe).float().to(device=self.device, dtype=dtype).contiguous()
 
     # ------------------------------------------------------------------ weights
@@ -111,16 +99,9 @@ class LatteT2V:
         return keys
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
-        missing = [k for k in self.expected_keys() if k not in sd]
-        if strict and missing:
-            raise KeyError(f"missing keys: {missing[:8]}{'...' if len(missing) > 8 else ''}")
+        load_weights(self.w, sd, self.expected_keys(), device=self.device, dtype=self.dtype, strict=strict,
+                     reshape=("pos_embed.proj.weight",))
         dev = lambda t: t.detach().to(device=self.device, dtype=self.dtype).contiguous()
-        for k in self.expected_keys():
-            if k in sd:
-                t = sd[k]
-                if k == "pos_embed.proj.weight":
-                    t = t.reshape(t.shape[0], -1)
-                self.w[k] = dev(t)
         for i in range(2 * self.L):
             p = self.block_prefix(i)
             self.w[p + ".attn1.qkv.weight"] = dev(torch.cat([sd[f"{p}.attn1.{l}.weight"] for l in ("to_q", "to_k", "to_v")], 0))
@@ -145,14 +126,6 @@ class LatteT2V:
             self._sp = None
 
     # ------------------------------------------------------------------ helpers
-    def _buf(self, name, shape):
-        n = int(np.prod(shape))
-        b = self._ws.get(name)
-        if b is None or b.numel() < n:
-            b = torch.empty(n, dtype=self.dtype, device=self.device)
-            self._ws[name] = b
-        return b[:n].view(*shape)
-
     def _gemm(self, x, wname, **kw):
         w, b = self.w[wname + ".weight"], self.w[wname + ".bias"]
         if w.shape[0] % 192 == 0 and w.shape[1] % 64 == 0:
@@ -301,10 +274,7 @@ class LatteT2V:
         elif temporal:
             ops.attn_temporal(qkv, C, None, None, None, None, ao, B, Fr, S, H)
         else:
-            key = ("kv_spatial", B * Fr, S)
-            if key not in self._ws:
-                self._ws[key] = ops.alloc_kv_buffers(B * Fr, H, S, self.device)
-            kp, vt = self._ws[key]
+            kp, vt = self._ws.once(("kv_spatial", B * Fr, S), lambda: ops.alloc_kv_buffers(B * Fr, H, S, self.device))
             ops.attn_prep_kv(qkv[:, C:2 * C], qkv[:, 2 * C:], None, kp, vt, B * Fr, H, S)
             ops.flash_attn(qkv[:, :C], None, kp, vt, ao, B * Fr, H, S, S)
         aux = None
@@ -328,13 +298,13 @@ class LatteT2V:
             slab = pab.get_mlp_output(rng, timestep=timestep_int, block_idx=st.block_idx, is_temporal=temporal)
             ops.add_rows(x, slab)
             if timestep_int == rng[-1]:   # window closed: hand the slab back (stream order keeps the add above ahead of a reuse)
-                self._ws.setdefault("mlp_slab_pool", []).append(slab)
+                self._ws.give_slab(slab)
             return
         shift, scale, gate = mod_i[0, 3 * C:4 * C], mod_i[0, 4 * C:5 * C], mod_i[0, 5 * C:6 * C]
         xm = ops.adaln_modulate(x, shift, scale, Fr * S, C6, eps=self.config.norm_eps, out=self._buf("xm", (N, C)))
         hb = ops.gemm(xm, w[p + ".ff.net.0.proj.weight"], w[p + ".ff.net.0.proj.bias"], epilogue=ops.EPI_BIAS_GELU,
                       out=self._buf("mlp_h", (N, 4 * C)))
-        aux = self._mlp_slab(x) if broadcast_next else None
+        aux = self._ws.take_slab(x) if broadcast_next else None
         ops.gemm(hb, w[p + ".ff.net.2.weight"], w[p + ".ff.net.2.bias"], epilogue=ops.EPI_GATE_RES, gate=gate, gate_stride=C6,
                  rows_per_sample=Fr * S, res=x, aux=aux, out=x)
         if broadcast_next:
@@ -391,22 +361,8 @@ class LatteT2V:
         self._ff(i, x, mod_i, B, Fr, S, st, timestep_int, ats, temporal=True)
         return x
 
-    def _mlp_slab(self, like):
-        """A slab for a PAB MLP-broadcast window: taken from the pool of slabs that closed windows handed back (a window's stored
-        output lives until its last timestep, pab_mgr.py:148-174), so a generate() allocates at most as many 90 MB slabs as
-        windows are open at once instead of one per window opening."""
-        pool = self._ws.setdefault("mlp_slab_pool", [])
-        for k, b in enumerate(pool):
-            if b.shape == like.shape:
-                return pool.pop(k)
-        return torch.empty_like(like)
-
     def reset_pab_state(self):
-        for st in self.states:
-            st.attn_count = st.cross_count = st.mlp_count = 0
-        if pab.PAB_MANAGER is not None:
-            pab.PAB_MANAGER.config.mlp_spatial_outputs.clear()
-            pab.PAB_MANAGER.config.mlp_temporal_outputs.clear()
+        pab.reset_states(self.states)
 
 
 def synth_state_dict(num_layers=28, num_heads=16, head_dim=72, caption_channels=4096, in_channels=4, out_channels=8,

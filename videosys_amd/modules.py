@@ -3,9 +3,19 @@ tests: tests/test_rms_norm.py) as a stand-alone module.  Inside the transformers
 attention prep kernels (vsys_attn_prep_kv); this class is the same arithmetic as one launch for code that calls it directly."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import ops
+
+
+def sincos_1d(embed_dim: int, pos: np.ndarray) -> np.ndarray:
+    """diffusers get_1d_sincos_pos_embed_from_grid ([sin | cos], float64 frequencies) — the constant tables of Latte, CogVideoX and
+    Vchitect are built from it on the host."""
+    omega = np.arange(embed_dim // 2, dtype=np.float64) / (embed_dim / 2.0)
+    omega = 1.0 / 10000**omega
+    out = np.einsum("m,d->md", pos.reshape(-1), omega)
+    return np.concatenate([np.sin(out), np.cos(out)], axis=1)
 
 
 class LlamaRMSNorm:

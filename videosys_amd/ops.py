@@ -5,6 +5,7 @@ and sizes to libvideosys_amd.so.  All wrappers require CUDA(HIP) tensors and rai
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -95,7 +96,6 @@ def gemm(x, w, bias=None, *, epilogue=EPI_BIAS, gate=None, gate_stride=0, rows_p
     if out is None:
         out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
     assert out.stride(1) == 1
-    lib = _lib.load()
     _call("vsys_gemm_bf16", _p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(out), out.stride(0), M, N, K, epilogue,
                                   _p(gate), gate_stride, rows_per_sample, _p(res), res.stride(0) if res is not None else 0,
                                   _p(aux), aux.stride(0) if aux is not None else 0)
@@ -201,7 +201,6 @@ def linear_small(x, w, bias=None, act_in=ACT_NONE, act_out=ACT_NONE, out=None):
     N = w.shape[0]
     if out is None:
         out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
-    lib = _lib.load()
     _call("vsys_linear_small", _p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(out), out.stride(0), M, N, K, act_in,
                                      act_out)
     return out
@@ -215,7 +214,6 @@ def adaln_modulate(x, shift, scale, rows_per_sample, mod_stride, eps=1e-6, out=N
     rows, C = x.shape
     if out is None:
         out = torch.empty_like(x)
-    lib = _lib.load()
     _call("vsys_adaln_modulate", _p(x), _p(shift), _p(scale), _p(out), rows, C, rows_per_sample, mod_stride, eps)
     return out
 
@@ -228,7 +226,6 @@ def mod_table(table, t_mlp, out=None):
     B = t_mlp.shape[0]
     if out is None:
         out = torch.empty(nblk, B, C6, dtype=torch.bfloat16, device=table.device)
-    lib = _lib.load()
     _call("vsys_mod_table", _p(table), _p(t_mlp), _p(out), nblk, B, C6)
     return out
 
@@ -238,7 +235,6 @@ def timestep_embedding(t_f32, dim=256):
     assert t_f32.dtype == torch.float32 and t_f32.is_contiguous()
     B = t_f32.numel()
     out = torch.empty(B, dim, dtype=torch.bfloat16, device=t_f32.device)
-    lib = _lib.load()
     _call("vsys_timestep_embedding", _p(t_f32), _p(out), B, dim)
     return out
 
@@ -253,7 +249,6 @@ def patch_embed(z_f32, w, bias, pos, B, patch, C):
     ph, pw = patch[1], patch[2]
     Hp, Wp = -(-H // ph), -(-W // pw)
     out = torch.empty(B, T, Hp * Wp, C, dtype=torch.bfloat16, device=z_f32.device)
-    lib = _lib.load()
     _call("vsys_patch_embed", _p(z_f32), Bz, _p(w), _p(bias), _p(pos), _p(out), B, Cin, T, H, W, ph, pw, C)
     return out
 
@@ -296,7 +291,6 @@ def final_layer(x, table, tvec, w, bias, B, T, Hp, Wp, H, W, patch, Cout, eps=1e
     assert x.is_contiguous() and w.is_contiguous() and table.is_contiguous() and tvec.is_contiguous()
     C = x.shape[-1]
     out = torch.empty(B, Cout, T, H, W, dtype=torch.float32, device=x.device)
-    lib = _lib.load()
     _call("vsys_final_layer", _p(x), _p(table), _p(tvec), _p(w), _p(bias), _p(out), B, T, Hp, Wp, H, W, patch[1],
                                     patch[2], Cout, C, eps)
     return out
@@ -310,7 +304,6 @@ def cfg_euler_step(z_f32, model_out_f32, guidance, dt):
     Cout = model_out_f32.shape[1]
     assert model_out_f32.shape[0] == 2 * Bz
     thw = z_f32[0, 0].numel()
-    lib = _lib.load()
     _call("vsys_cfg_euler_step", _p(z_f32), _p(model_out_f32), Bz, Cin, Cout, thw, float(guidance), float(dt))
     return z_f32
 
@@ -324,7 +317,6 @@ def cfg_linear_step(z_f32, model_out_f32, guidance, c_z, c_eps, cond_first=False
     Cout = model_out_f32.shape[1]
     assert model_out_f32.shape[0] == 2 * Bz
     thw = z_f32[0, 0].numel()
-    lib = _lib.load()
     _call("vsys_cfg_linear_step", _p(z_f32), _p(model_out_f32), Bz, Cin, Cout, thw, float(guidance), float(c_z),
                                         float(c_eps), 1 if cond_first else 0)
     return z_f32
@@ -336,7 +328,6 @@ def add_bcast_rows(x, e, group, period):
     _bf16(x, e)
     assert x.is_contiguous() and e.is_contiguous() and x.shape[-1] == e.shape[-1] and e.shape[0] >= period
     rows = x.numel() // x.shape[-1]
-    lib = _lib.load()
     _call("vsys_add_bcast_rows", _p(x), _p(e), rows, x.shape[-1], group, period)
     return x
 
@@ -345,7 +336,6 @@ def add_rows(x, y):
     _chk(x, y)
     _bf16(x, y)
     assert x.is_contiguous() and y.is_contiguous() and x.numel() == y.numel()
-    lib = _lib.load()
     _call("vsys_add_rows", _p(x), _p(y), x.numel())
     return x
 
@@ -353,7 +343,6 @@ def add_rows(x, y):
 def copy_4d(src, dst, n0, n1, n2, C, sstr, dstr, n1_valid=None, n2_valid=None):
     _chk(src, dst)
     _bf16(src, dst)
-    lib = _lib.load()
     _call("vsys_copy_4d", _p(src), _p(dst), n0, n1, n2, C, sstr[0], sstr[1], sstr[2], dstr[0], dstr[1], dstr[2],
                                 n1 if n1_valid is None else n1_valid, n2 if n2_valid is None else n2_valid)
     return dst
@@ -365,7 +354,6 @@ def copy_4d_batch(src, dst, descs):
 
     _chk(src, dst)
     _bf16(src, dst)
-    lib = _lib.load()
     for i in range(0, len(descs), 16):
         part = descs[i:i + 16]
         flat = [int(v) for d in part for v in d]
@@ -388,8 +376,6 @@ def alloc_kv_buffers(batch, heads, kv_len, device):
 
 # ---- spatial K/V prep in the qkv GEMM's epilogue (include/videosys_amd.h, vsys_gemm_bf16_ln_qkv_kv)
 def _fused_kv_default() -> bool:
-    import os
-
     return os.environ.get("VSYS_FUSED_KV", "1") != "0"
 
 
@@ -448,7 +434,6 @@ def attn_prep_kv(k, v, k_norm_w, kp, vt, batch, heads, kv_len, eps=1e-6):
     assert k.stride(1) == 1 and v.stride(1) == 1 and kp.is_contiguous() and vt.is_contiguous()
     kv_pad = kp.shape[2]
     assert vt.shape[3] == kv_pad and vt.shape[2] == VT_ROWS
-    lib = _lib.load()
     _call("vsys_attn_prep_kv", _p(k), k.stride(0), _p(v), v.stride(0), _p(k_norm_w), _p(kp), _p(vt), batch, heads,
                                      kv_len, kv_pad, eps)
 
@@ -533,6 +518,12 @@ def flash_attn_varlen(q, q_norm_w, kp, vt, keys: VarlenKeys, out, heads, q_len, 
     return out
 
 
+def static_max_allowed() -> bool:
+    """May a model promise the attention kernels a key-norm bound (rms_key_bound / ln_key_bound)?  VSYS_FLASH_STATIC=0 never promises;
+    read at every call."""
+    return os.environ.get("VSYS_FLASH_STATIC", "1") != "0"
+
+
 def rms_key_bound(q_norm_w, k_norm_w, head_dim=HEAD_DIM):
     """The k_norm_bound of flash_attn for RMS-normed q and k (LlamaRMSNorm, normalization.py:28-33: x / rms(x) has norm sqrt(d), then
     the weight elementwise), or None when the promise |q_i| k_norm_bound <= 60 cannot be given from the weights alone.  Host-side,
@@ -557,7 +548,6 @@ def attn_temporal(qkv, C, q_norm_w, k_norm_w, rope_cos, rope_sin, out, B, T, S, 
     if rope_cos is not None:
         assert rope_cos.dtype == torch.float32 and rope_cos.is_contiguous() and rope_cos.shape == (T, HEAD_DIM)
         assert rope_sin.dtype == torch.float32 and rope_sin.is_contiguous() and rope_sin.shape == (T, HEAD_DIM)
-    lib = _lib.load()
     _call("vsys_attn_temporal_d72", _p(qkv), qkv.stride(0), C, _p(q_norm_w), _p(k_norm_w), _p(rope_cos), _p(rope_sin),
                                           _p(out), out.stride(0), B, T, S, heads, eps)
     return out
@@ -571,7 +561,6 @@ def gemm_gate2(x, w, bias, gate, gate_stride, rows_per_sample, seg_split, gate_a
     assert x.dim() == 2 and x.stride(1) == 1 and w.stride(1) == 1 and out.stride(1) == 1
     M, K = x.shape
     N = w.shape[0]
-    lib = _lib.load()
     _call("vsys_gemm_bf16_gate2", _p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(out), out.stride(0), M, N, K, _p(gate),
                                         gate_stride, rows_per_sample, seg_split, gate_alt, _p(res),
                                         res.stride(0) if res is not None else 0, _p(aux),
@@ -586,7 +575,6 @@ def ln_modulate(x, ln_w, ln_b, shift, scale, rows_per_sample, mod_stride=0, seg_
     rows, C = x.shape
     if out is None:
         out = torch.empty_like(x)
-    lib = _lib.load()
     _call("vsys_ln_modulate", _p(x), _p(ln_w), _p(ln_b), _p(shift), _p(scale), _p(out), rows, C, rows_per_sample, mod_stride,
                                     seg_split, mod_alt, eps)
     return out
@@ -597,7 +585,6 @@ def gate_add_rows(x, y, gate, rows_per_sample, gate_stride, seg_split=0, gate_al
     _bf16(x, y, gate)
     assert x.is_contiguous() and y.is_contiguous() and x.shape == y.shape
     rows, C = x.shape
-    lib = _lib.load()
     _call("vsys_gate_add_rows", _p(x), _p(y), _p(gate), rows, C, rows_per_sample, gate_stride, seg_split, gate_alt)
     return x
 
@@ -608,7 +595,6 @@ def im2col_patch(z_f32, B, p):
     assert z_f32.dtype == torch.float32 and z_f32.is_contiguous()
     Bz, F, Cin, H, W = z_f32.shape
     out = torch.empty(B * F * (H // p) * (W // p), Cin * p * p, dtype=torch.bfloat16, device=z_f32.device)
-    lib = _lib.load()
     _call("vsys_im2col_patch", _p(z_f32), Bz, _p(out), B, F, Cin, H, W, p)
     return out
 
@@ -620,7 +606,6 @@ def unpatchify_cvx(x, B, F, Hp, Wp, Cout, p, out=None):
     if out is None:
         out = torch.empty(B, F, Cout, Hp * p, Wp * p, dtype=torch.float32, device=x.device)
     assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * F * Cout * Hp * p * Wp * p
-    lib = _lib.load()
     _call("vsys_unpatchify_cvx", _p(x), x.stride(0), _p(out), B, F, Hp, Wp, Cout, p)
     return out
 
@@ -640,7 +625,6 @@ def attn_prep_kv64(k, v, ln_w, ln_b, rope_cos, rope_sin, rope_start, kp, vt, bat
     if rope_cos is not None:
         assert rope_cos.dtype == torch.float32 and rope_cos.is_contiguous() and rope_sin.is_contiguous() and rope_cos.shape[1] == 64
         rope_len = rope_cos.shape[0]
-    lib = _lib.load()
     _call("vsys_attn_prep_kv64", _p(k), k.stride(0), _p(v), v.stride(0), _p(ln_w), _p(ln_b), _p(rope_cos), _p(rope_sin),
                                        rope_start, rope_len, _p(kp), _p(vt), batch, heads, kv_len, kp.shape[2], eps)
 
@@ -728,7 +712,6 @@ def conv(a, grid: VaeGrid, w, bias, cin, kt, ks, out=None, res=None):
         out = torch.empty(M, N, dtype=torch.bfloat16, device=a.device)
     shift_rows = (grid.Wp + 1) if ks == 3 else 0
     a_ptr = a.data_ptr() - shift_rows * a.stride(0) * 2
-    lib = _lib.load()
     _call("vsys_conv_bf16", a_ptr, a.stride(0), _p(w), w.stride(0), _p(bias), _p(res), res.stride(0) if res is not None else 0,
                                   _p(out), None, out.stride(0), M, N, cin, kt, ks, ks, grid.Wp, grid.plane, 1, 0, 0, 0, 1.0)
     return out
@@ -745,7 +728,6 @@ def gemm128(a, w, bias=None, res=None, out=None, out_f32=None, out_scale=1.0, ba
     if out is None and out_f32 is None:
         out = torch.empty(M, N, dtype=torch.bfloat16, device=a.device)
     o = out if out is not None else out_f32
-    lib = _lib.load()
     _call("vsys_conv_bf16", _p(a), a.stride(-2), _p(w), w.stride(-2), _p(bias), _p(res), res.stride(-2) if res is not None else 0,
                                   _p(out), _p(out_f32), o.stride(-2), M, N, K, 1, 1, 1, 0, 0, batch, batch_a, batch_w, batch_o,
                                   float(out_scale))
@@ -761,7 +743,6 @@ def group_norm(x, gs: VaeGrid, y, gd: VaeGrid, C, gamma, beta, eps, silu_act, gr
     _bf16(x, y, gamma, beta)
     assert x.shape[0] == gs.rows and y.shape[0] == gd.rows and x.shape[1] == C and y.shape[1] == C
     assert x.is_contiguous() and y.is_contiguous()
-    lib = _lib.load()
     partial = torch.empty(gs.n * _GN_NBLK * (C // 4) * 2, dtype=torch.float32, device=x.device)
     stats = torch.empty(gs.n * groups * 2, dtype=torch.float32, device=x.device)
     _call("vsys_gn_stats", _p(x), gs._c, gs.n, C, groups, float(eps), _p(partial), _GN_NBLK, _p(stats))
@@ -794,7 +775,6 @@ def spatial_norm_silu(x, gs: VaeGrid, y, gd: VaeGrid, C, gamma, beta, yb, zdims,
     zT, zH, zW = zdims
     assert x.shape == (gs.rows, C) and y.shape == (gd.rows, C) and x.is_contiguous() and y.is_contiguous()
     assert yb.shape == (gs.n * zT * zH * zW, 2 * C) and yb.is_contiguous()
-    lib = _lib.load()
     partial = torch.empty(gs.n * _GN_NBLK * (C // 4) * 2, dtype=torch.float32, device=x.device)
     stats = torch.empty(gs.n * groups * 2, dtype=torch.float32, device=x.device)
     _call("vsys_gn_stats", _p(x), gs._c, gs.n, C, groups, float(eps), _p(partial), _GN_NBLK, _p(stats))
@@ -870,7 +850,6 @@ def t5_attention_mfma(qkv, bias_pad, center, lens, B, L, heads, out=None, ws=Non
     if ws is None:
         ws = (torch.empty(heads * kv_pad * 64, dtype=torch.bfloat16, device=qkv.device),
               torch.empty(heads * kv_pad * 64, dtype=torch.bfloat16, device=qkv.device))
-    lib = _lib.load()
     for b in range(B):
         q_b, o_b = qkv[b * L:(b + 1) * L], out[b * L:(b + 1) * L]
         _call("vsys_t5_attention_mfma", _p(q_b), qkv.stride(0), inner, _p(bias_pad), bias_pad.shape[1], center, int(lens[b]),
@@ -924,7 +903,6 @@ def linear_skinny(x, M, w, res=None, out=None, nsplit=None, part=None, wide=None
     if out is None:
         out = torch.empty(Mp, N, dtype=torch.bfloat16, device=x.device)
     assert out.shape[1] == N and out.stride(1) == 1 and (res is None or (res.shape[1] == N and res.stride(1) == 1))
-    lib = _lib.load()
     ldr = res.stride(0) if res is not None else 0
     if wide:
         _call("vsys_gemm_skinny_slices", _p(w), w.stride(0), _p(x), x.stride(0), _p(part), M, Mp, N, K, nsplit)

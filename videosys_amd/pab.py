@@ -126,6 +126,34 @@ class PABManager:
         return store.pop(key) if timestep == skip_range[-1] else store[key]
 
 
+class BlockState:
+    """PAB bookkeeping of one transformer block (open_sora_transformer_3d.py:141-147; Latte's blocks keep the same counters)."""
+
+    def __init__(self, block_idx, temporal):
+        self.block_idx = block_idx
+        self.temporal = temporal
+        self.attn_count = 0
+        self.cross_count = 0
+        # does last_attn / last_cross hold the output of this block's LAST computed call?  (slab elision writes a slab only when the
+        # next schedule entry will broadcast it: a caller that leaves the schedule must not be served a stale one)
+        self.attn_valid = False
+        self.cross_valid = False
+        self.mlp_count = 0
+        self.last_attn = None
+        self.last_cross = None
+
+
+def reset_states(states):
+    """Counters to zero and every stored MLP output dropped (an aborted generate() must not pin its slabs, nor may the next
+    prompt replay them)."""
+    for st in states:
+        st.attn_count = st.cross_count = st.mlp_count = 0
+        st.attn_valid = st.cross_valid = False
+    if PAB_MANAGER is not None:
+        PAB_MANAGER.config.mlp_spatial_outputs.clear()
+        PAB_MANAGER.config.mlp_temporal_outputs.clear()
+
+
 def set_pab_manager(config: PABConfig):
     global PAB_MANAGER
     PAB_MANAGER = PABManager(config) if config is not None else None

@@ -32,6 +32,7 @@ import torch
 
 from . import dsp, ops, pab, program
 from .utils import same_tensor
+from .workspace import Workspace
 
 
 class STDiT3Config:
@@ -92,24 +93,6 @@ def rope_tables(freqs: torch.Tensor, T: int, pos_dtype: torch.dtype):
     ang = torch.einsum("p,f->pf", seq.type(freqs.dtype), freqs)
     ang = ang.repeat_interleave(2, dim=-1)
     return ang.cos().float().contiguous(), ang.sin().float().contiguous()
-
-
-class _BlockState:
-    """PAB bookkeeping of one STDiT3Block (open_sora_transformer_3d.py:141-147)."""
-
-    def __init__(self, block_idx, temporal):
-        self.block_idx = block_idx
-        self.temporal = temporal
-        self.attn_count = 0
-        self.cross_count = 0
-        # does last_attn / last_cross hold the output of this block's LAST computed call?  (slab elision writes a slab only when the
-        # next schedule entry will broadcast it: a caller that leaves the schedule must not be served a stale one)
-        self.attn_valid = False
-        self.cross_valid = False
-        self.mlp_count = 0
-        self.last_attn: Optional[torch.Tensor] = None
-        self.last_cross: Optional[torch.Tensor] = None
-
 
 
 def text_lengths(mask=None, batch=None, y_lens=None, packed_rows=None):
@@ -185,12 +168,13 @@ class STDiT3:
         self.parallel_manager = SimpleNamespace(sp_size=1, cp_size=1, dp_size=1, dp_rank=0, sp_group=None, cp_group=None)
         self._sp: Optional[dsp.SequenceParallel] = None
         self._overlap, self._switch, self._scatter, self._side = False, "auto", "flat", None
-        self.states = [_BlockState(i // 2, bool(i % 2)) for i in range(2 * self.depth)]
+        self.states = [pab.BlockState(i // 2, bool(i % 2)) for i in range(2 * self.depth)]
         self._pos_cache = {}
         self._rope_cache = {}
         self._text_cache = None
         self._fps_cache = {}
-        self._ws = {}
+        self._ws = Workspace(self.device, dtype)
+        self._buf = self._ws.buf   # bound to this Workspace: _ws is cleared, never replaced (rebind _buf with it otherwise)
         self._hidden_tap = None   # test hook: callable(pair_index, x_rows) after every (spatial, temporal) block pair
         # launch programs (program.py): a step is recorded once per (geometry, PAB decision pattern, parallel layout) and replayed
         # through vsys_program_run afterwards; VSYS_PROGRAMS=0 issues every launch from Python every step
@@ -317,16 +301,6 @@ class STDiT3:
         _, _, T, H, W = x.shape
         p = self.patch_size
         return (-(-T // p[0]), -(-H // p[1]), -(-W // p[2]))
-
-    def _buf(self, name, shape):
-        b = self._ws.get(name)
-        n = 1
-        for s in shape:
-            n *= s
-        if b is None or b.numel() < n:
-            b = torch.empty(n, dtype=self.dtype, device=self.device)
-            self._ws[name] = b
-        return b[:n].view(*shape)
 
     def _pos(self, Hp, Wp, height, width):
         S = Hp * Wp
@@ -478,10 +452,7 @@ class STDiT3:
         return self._fold
 
     def _ln_stats(self, N):
-        key = ("ln_stats", N)
-        if key not in self._ws:
-            self._ws[key] = ops.ln_stats_buffer(N, self.hidden_size, self.device)
-        return self._ws[key]
+        return self._ws.once(("ln_stats", N), lambda: ops.ln_stats_buffer(N, self.hidden_size, self.device))
 
     def reset_text_cache(self):
         """Forget the per-prompt text projections (and their references to the prompt tensors) and the recorded steps."""
@@ -894,7 +865,7 @@ class STDiT3:
                 ops.add_rows(x, slab)
                 self._stats_fresh = False
             if timestep_int == skip_range[-1]:   # the window closed (the store dropped the entry): the slab is free again,
-                self._ws.setdefault("mlp_slab_pool", []).append(slab)   # in stream order behind the add above
+                self._ws.give_slab(slab)   # in stream order behind the add above
             return x
         hdim = w[p + ".mlp.fc1.weight"].shape[0]
         # (Measured in round 6 and not kept: the MLP one CFG sample at a time through a half-size hidden buffer, so that fc2's A operand is
@@ -906,7 +877,7 @@ class STDiT3:
             xm = ops.adaln_modulate(x, shift_mlp, scale_mlp, rps, C6, out=_buf("xm", (N, C)))
             hbuf = ops.gemm(xm, w[p + ".mlp.fc1.weight"], w[p + ".mlp.fc1.bias"], epilogue=ops.EPI_BIAS_GELU,
                             out=_buf("mlp_h", (N, hdim)))
-        aux = self._mlp_slab(x) if broadcast_next else None   # the post-gate output, written by the fc2 epilogue
+        aux = self._ws.take_slab(x) if broadcast_next else None   # the post-gate output, written by the fc2 epilogue
         write_x(hbuf, p + ".mlp.fc2", 2, gate=gate_mlp, aux=aux, want_stats=True)   # the next block's norm1 reads this x
         if broadcast_next:
             pab.save_mlp_output(timestep=timestep_int, block_idx=st.block_idx, ff_output=aux, is_temporal=temporal)
@@ -960,10 +931,7 @@ class STDiT3:
                 qkv = xt.view(Na, 3 * C)
             else:
                 qkv = ops.gemm(xt.view(Na, C), w[p + ".attn.qkv.weight"], w[p + ".attn.qkv.bias"], out=self._buf(f"qkv_o{i}", (Na, 3 * C)))
-            key = ("kv_spatial_o", i, nf, S_full)
-            if key not in self._ws:
-                self._ws[key] = ops.alloc_kv_buffers(nf, H, S_full, self.device)
-            kp, vt = self._ws[key]
+            kp, vt = self._ws.once(("kv_spatial_o", i, nf, S_full), lambda: ops.alloc_kv_buffers(nf, H, S_full, self.device))
             ops.attn_prep_kv(qkv[:, C:2 * C], qkv[:, 2 * C:], w[p + ".attn.k_norm.weight"], kp, vt, nf, H, S_full)
             ao = self._buf(f"attn_out_o{i}", (Na, C))
             ops.flash_attn(qkv[:, :C], w[p + ".attn.q_norm.weight"], kp, vt, ao, nf, H, S_full, S_full, k_norm_bound=self._kbound(p))
@@ -996,11 +964,8 @@ class STDiT3:
         """What travels through the DSP exchange of a spatial block: "activations" (reference order) or "qkv"."""
         if self._switch in ("activations", "qkv"):
             return self._switch
-        key = ("switch", B, T, S_full)
-        if key not in self._ws:
-            self._ws[key] = dsp.choose_spatial_switch(B, T, S_full, self.hidden_size, self._sp.P, overlapped=bool(self._overlap),
-                                                      scatter="sample")["order"]   # (called with the scattered view's B, T)
-        return self._ws[key]
+        return self._ws.once(("switch", B, T, S_full), lambda: dsp.choose_spatial_switch(   # (called with the scattered view's B, T)
+            B, T, S_full, self.hidden_size, self._sp.P, overlapped=bool(self._overlap), scatter="sample")["order"])
 
     def _kbound(self, p):
         """The promise about block ``p``'s spatial keys that lets the attention kernels drop the running max (ops.rms_key_bound:
@@ -1008,7 +973,7 @@ class STDiT3:
         kb = self._kbounds.get(p, 0)
         if kb == 0:
             kb = None
-            if os.environ.get("VSYS_FLASH_STATIC", "1") != "0":
+            if ops.static_max_allowed():
                 kb = ops.rms_key_bound(self.w[p + ".attn.q_norm.weight"], self.w[p + ".attn.k_norm.weight"])
             self._kbounds[p] = kb
         return kb
@@ -1020,33 +985,15 @@ class STDiT3:
         same 1.0 over all kv_len = kv_pad keys, and never touches 73-75 / 77-95 — both writers leave the same constants, which is
         what makes sharing safe."""
         key = ("kv_spatial", batch, kv_len)
-        if key not in self._ws:
-            self._ws[key] = ops.alloc_kv_buffers(batch, self.num_heads, kv_len, self.device)
+        kv = self._ws.once(key, lambda: ops.alloc_kv_buffers(batch, self.num_heads, kv_len, self.device))
         if constant_rows and key + ("const",) not in self._ws:
             assert kv_len % 64 == 0
-            ops.kv_set_constant_rows(self._ws[key][1])
+            ops.kv_set_constant_rows(kv[1])
             self._ws[key + ("const",)] = True
-        return self._ws[key]
-
-    def _mlp_slab(self, like):
-        """A slab for a PAB MLP-broadcast window: taken from the pool of slabs that closed windows handed back (a window's stored
-        output lives until its last timestep, pab_mgr.py:148-174), so a generate() allocates at most as many 90 MB slabs as
-        windows are open at once instead of one per window opening."""
-        pool = self._ws.setdefault("mlp_slab_pool", [])
-        for k, b in enumerate(pool):
-            if b.shape == like.shape:
-                return pool.pop(k)
-        return torch.empty_like(like)
+        return kv
 
     def reset_pab_state(self):
-        """Counters to zero and every stored MLP output dropped (an aborted generate() must not pin its slabs, nor may the next
-        prompt replay them)."""
-        for st in self.states:
-            st.attn_count = st.cross_count = st.mlp_count = 0
-            st.attn_valid = st.cross_valid = False
-        if pab.PAB_MANAGER is not None:
-            pab.PAB_MANAGER.config.mlp_spatial_outputs.clear()
-            pab.PAB_MANAGER.config.mlp_temporal_outputs.clear()
+        pab.reset_states(self.states)
 
 
 def _from_pretrained(cls, name, device="cuda", **kwargs):

@@ -158,6 +158,19 @@ def ctor_kwargs(fn, cfg: dict) -> dict:
     return {k: v for k, v in cfg.items() if k in names}
 
 
+def load_weights(dst, sd, keys, *, device, dtype, strict=True, reshape=None):
+    """The common body of the models' ``load_state_dict``: ``dst[k]`` = ``sd[k]`` on ``device`` in ``dtype``, contiguous, for every
+    ``k`` of ``keys`` that ``sd`` has (``strict``: all of them, else KeyError).  ``reshape``: the keys of convolution weights, stored
+    flattened to [out, -1] for the GEMM that runs them."""
+    missing = [k for k in keys if k not in sd]
+    if strict and missing:
+        raise KeyError(f"missing keys: {missing[:8]}{'...' if len(missing) > 8 else ''}")
+    for k in keys:
+        if k in sd:
+            t = sd[k].reshape(sd[k].shape[0], -1) if k in (reshape or ()) else sd[k]
+            dst[k] = t.detach().to(device=device, dtype=dtype).contiguous()
+
+
 def same_tensor(a, b) -> bool:
     """True when ``b`` is ``a`` or a fresh VIEW OBJECT of exactly the same elements (same storage, offset, shape, strides) at the
     same version counter — what a per-step ``y[rows]`` slice produces under CFG parallel.  Meant for caches that HOLD ``a``:

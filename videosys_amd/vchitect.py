@@ -26,6 +26,8 @@ import numpy as np
 import torch
 
 from . import ops, pab, vchitect_ops
+from .modules import sincos_1d
+from .workspace import Workspace
 
 HEAD_DIM = 64
 ROPE_THETA = 1e6
@@ -58,7 +60,8 @@ class VchitectAttention:
         self.device = torch.device(device)
         self.w: Dict[str, torch.Tensor] = {}
         self.parallel_manager = None
-        self._ws, self._rope = {}, {}
+        self._ws, self._rope = Workspace(self.device), {}
+        self._buf = self._ws.buf   # bound to this Workspace: _ws is cleared, never replaced (rebind _buf with it otherwise)
         self.spatial_count = self.cross_count = self.temporal_count = 0
         self.last_spatial = self.last_cross = self.last_temporal = None
         self.last_decisions = (False, False, False)
@@ -89,19 +92,8 @@ class VchitectAttention:
         self.spatial_count = self.cross_count = self.temporal_count = 0
         self.last_spatial = self.last_cross = self.last_temporal = None
 
-    def _buf(self, name, shape):
-        n = int(np.prod(shape))
-        b = self._ws.get(name)
-        if b is None or b.numel() < n:
-            b = torch.empty(n, dtype=torch.bfloat16, device=self.device)
-            self._ws[name] = b
-        return b[:n].view(*shape)
-
     def _kv(self, name, batch, kv_len):
-        key = (name, batch, kv_len)
-        if key not in self._ws:
-            self._ws[key] = ops.alloc_kv_buffers64(batch, self.H, kv_len, self.device)
-        return self._ws[key]
+        return self._ws.once((name, batch, kv_len), lambda: ops.alloc_kv_buffers64(batch, self.H, kv_len, self.device))
 
     def _lin(self, x, name, out):
         return ops.gemm(x, self.w[name + ".weight"], self.w[name + ".bias"], out=out)
@@ -202,13 +194,9 @@ def synth_attention_state_dict(dim: int, context_pre_only: bool = False, seed: i
 
 def sincos_2d(embed_dim: int, grid: int, base_size: int) -> torch.Tensor:
     """diffusers get_2d_sincos_pos_embed(embed_dim, grid, base_size=base_size, interpolation_scale=1): fp32 [grid * grid, embed_dim]."""
-    def one(dim, pos):
-        omega = 1.0 / 10000 ** (np.arange(dim // 2, dtype=np.float64) / (dim / 2.0))
-        out = np.einsum("m,d->md", pos.reshape(-1), omega)
-        return np.concatenate([np.sin(out), np.cos(out)], axis=1)
     g = np.arange(grid, dtype=np.float32) / (grid / base_size)
     gw, gh = np.meshgrid(g, g)          # w goes first
-    return torch.from_numpy(np.concatenate([one(embed_dim // 2, gw), one(embed_dim // 2, gh)], axis=1)).float()
+    return torch.from_numpy(np.concatenate([sincos_1d(embed_dim // 2, gw), sincos_1d(embed_dim // 2, gh)], axis=1)).float()
 
 
 class JointTransformerBlock:
@@ -295,7 +283,8 @@ class VchitectXLTransformerModel:
         self.transformer_blocks = [JointTransformerBlock(C, num_attention_heads, C, i == num_layers - 1, rope_scaling_factor, self.device)
                                    for i in range(num_layers)]
         self.w: Dict[str, torch.Tensor] = {}
-        self._ws = {}
+        self._ws = Workspace(self.device, dtype)
+        self._buf = self._ws.buf   # bound to this Workspace: _ws is cleared, never replaced (rebind _buf with it otherwise)
         self._pos_crop = {}
         self.parallel_manager = None
         self.use_programs = True     # samplers record a step once and replay it (pipeline_vchitect.py); False: eager issue
@@ -353,22 +342,10 @@ class VchitectXLTransformerModel:
         for b in self.transformer_blocks:
             b.attn.reset_pab_state()
 
-    def _buf(self, name, shape):
-        n = int(np.prod(shape))
-        b = self._ws.get(name)
-        if b is None or b.numel() < n:
-            b = torch.empty(n, dtype=self.dtype, device=self.device)
-            self._ws[name] = b
-        return b[:n].view(*shape)
-
     def step_timesteps(self, rows: int) -> torch.Tensor:
         """The resident fp32 [B * F] buffer the timestep embedding reads.  forward() fills it from ``timestep``; a sampler that replays a
         recorded step writes the step's timestep here instead (the one per-step input besides the latents)."""
-        b = self._ws.get("timesteps")
-        if b is None or b.numel() < rows:
-            b = torch.empty(rows, dtype=torch.float32, device=self.device)
-            self._ws["timesteps"] = b
-        return b[:rows]
+        return self._buf("timesteps", (rows,), torch.float32)
 
     def cropped_pos_embed(self, hp: int, wp: int) -> torch.Tensor:
         """PatchEmbed.cropped_pos_embed: the centre hp x wp window of the max x max table, bf16 [hp * wp, C] on the device."""
