@@ -447,6 +447,25 @@ int vsys_splitk_reduce(const void* part_f32, int64_t nsplit, int64_t slab, int64
 int vsys_t5_attention_mfma(const void* qkv, int64_t row_stride, int64_t inner, const void* bias_f32, int64_t bias_ld, int64_t bias_center,
                            int64_t kv_len, void* kp, void* vt, void* out, int64_t out_stride, int64_t L, int64_t heads, void* stream);
 
+/* ---- CLIP text encoders (the two CLIPTextModelWithProjection of Vchitect-2.0: transformers modeling_clip.py, third-party; call
+ * site pipeline_vchitect.py:368).  Embedding, LayerNorm and the pooled-row gather are vsys_gather_rows / vsys_add_bcast_rows /
+ * vsys_ln_modulate, the linears vsys_gemm_skinny_slices; neither entry point below has a VSYS_OP code (they run once per prompt). */
+/* CLIPAttention (transformers modeling_clip.py, third-party; call site pipeline_vchitect.py:368), head dim 64, causal:
+ * out_i = bf16(sum_{j <= i} w_j v_j), w_j = bf16(p_j / l) with p_j = exp(s_j - max_j s_j), s_j = (q_i . k_j) / 8 and l = sum_j p_j
+ * all in fp32 (the division from the unrounded p_j: `softmax(..., dtype=float32).to(bf16)`).  qkv rows (b, l) of row_stride
+ * elements, q | k | v at column 0 | inner | 2 inner, head h at h*64 (the layout of vsys_t5_attention); out bf16 [B*L, inner] with
+ * out_stride.  One launch covers all B samples and inner / 64 heads; 1 <= L <= 128.  Strides % 8 == 0, pointers 16-byte aligned.
+ * Rows at or past B*L and columns outside [0, 3 inner) are never read. */
+int vsys_clip_attention_d64(const void* qkv, int64_t row_stride, int64_t inner, void* out, int64_t out_stride, int64_t B, int64_t L,
+                            void* stream);
+/* vsys_splitk_reduce for layers with a bias and an activation (nn.Linear + CLIPMLP.activation_fn inside transformers' CLIPEncoderLayer,
+ * modeling_clip.py, third-party; call site pipeline_vchitect.py:368): y = bf16(((p_0 + p_1) + ...) + bias[n]) in fp32, slices in
+ * ascending order, bias (bf16 [N], may be NULL) last; act 0: none, 1: quick_gelu = bf16(y * bf16(sigmoid(bf16(1.702 y)))),
+ * 2: gelu = bf16(0.5 y (1 + erf(y / sqrt 2))) evaluated in fp32; then + res[m][n], added after the rounding and rounded again.
+ * bias == NULL and act == 0 give the bits of vsys_splitk_reduce.  out may alias res. */
+int vsys_splitk_reduce_bias_act(const void* part_f32, int64_t nsplit, int64_t slab, int64_t ldp, const void* res, int64_t ldr, void* out,
+                                int64_t ldo, int64_t M, int64_t N, const void* bias, int64_t act, void* stream);
+
 /* ---- VAE decode (VideoAutoencoderPipeline.decode, autoencoder_kl_open_sora.py:672-695) --------------
  * Activations are channels-last bf16 row matrices over a grid; a grid is described by int64 g[6] = {T, H, W, pad, tf,
  * sample_rows}: sample n, frame t, pixel (h, w) is row n*sample_rows + ((t + tf)*(H + 2 pad) + h + pad)*(W + 2 pad) + w + pad.

@@ -3,9 +3,10 @@
 Public names mirror ``videosys/__init__.py`` of the reference for the paths this build covers: ``initialize``,
 ``VideoSysEngine``, ``OpenSoraConfig`` / ``OpenSoraPABConfig`` / ``OpenSoraPipeline`` and ``LatteConfig`` /
 ``LattePABConfig`` / ``LattePipeline``, ``CogVideoXConfig`` / ``CogVideoXPABConfig`` / ``CogVideoXPipeline``, ``VchitectConfig`` /
-``VchitectPABConfig`` / ``VchitectXLPipeline``.
+``VchitectPABConfig`` / ``VchitectXLPipeline``; ``CLIPTextEncoder`` / ``ClipByteTokenizer`` are the text side of the last one.
 Importing the package does not need a GPU; running any op does (no CPU fallback).
 """
+from .clip import CLIPTextEncoder, ClipByteTokenizer  # noqa: F401
 from .dsp import initialize  # noqa: F401
 from .engine import VideoSysEngine  # noqa: F401
 from .pipeline_cogvideox import CogVideoXConfig, CogVideoXPABConfig, CogVideoXPipeline  # noqa: F401
@@ -15,4 +16,4 @@ from .pipeline_vchitect import VchitectConfig, VchitectPABConfig, VchitectXLPipe
 
 __all__ = ["initialize", "VideoSysEngine", "OpenSoraPipeline", "OpenSoraConfig", "OpenSoraPABConfig", "LattePipeline",
            "LatteConfig", "LattePABConfig", "CogVideoXPipeline", "CogVideoXConfig", "CogVideoXPABConfig", "VchitectXLPipeline", "VchitectConfig",
-           "VchitectPABConfig"]
+           "VchitectPABConfig", "CLIPTextEncoder", "ClipByteTokenizer"]

@@ -76,6 +76,8 @@ SIGNATURES = {
     "vsys_t5_attention_mfma": [_ptr, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr],
     "vsys_splitk_reduce_t": [_ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _ptr],
     "vsys_t5_attention": [_ptr, _i64, _i64, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr],
+    "vsys_clip_attention_d64": [_ptr, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr],
+    "vsys_splitk_reduce_bias_act": [_ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _ptr, _i64, _ptr],
     "vsys_copy_4d_batch": [_ptr, _ptr, _i64, _ptr, _ptr],
     "vsys_conv_bf16": [_ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                        _i64, _i64, _i64, _i64, _f32, _ptr],

@@ -528,6 +528,21 @@ int vsys_t5_attention(const void* qkv, int64_t row_stride, int64_t inner, const 
                              reinterpret_cast<const int*>(klen_i32), B16(out), out_stride, (int)B, (int)L, (int)heads, S(stream));
 }
 
+int vsys_clip_attention_d64(const void* qkv, int64_t row_stride, int64_t inner, void* out, int64_t out_stride, int64_t B, int64_t L,
+                            void* stream) {
+  if (!qkv || !out) return VSYS_ERR_ARG;
+  if (!fits_int(inner) || !fits_int(B) || !fits_int(L) || row_stride < 0 || out_stride < 0) return VSYS_ERR_SHAPE;
+  return launch_clip_attention_d64(B16(qkv), row_stride, (int)inner, B16(out), out_stride, (int)B, (int)L, S(stream));
+}
+
+int vsys_splitk_reduce_bias_act(const void* part_f32, int64_t nsplit, int64_t slab, int64_t ldp, const void* res, int64_t ldr, void* out,
+                                int64_t ldo, int64_t M, int64_t N, const void* bias, int64_t act, void* stream) {
+  if (!part_f32 || !out || act < 0 || act > 2) return VSYS_ERR_ARG;
+  if (!fits_int(nsplit) || !fits_int(M) || !fits_int(N)) return VSYS_ERR_SHAPE;
+  return launch_splitk_reduce_bias_act(reinterpret_cast<const float*>(part_f32), (int)nsplit, slab, ldp, B16(res), ldr, B16(out), ldo, (int)M,
+                                       (int)N, B16(bias), (int)act, S(stream));
+}
+
 int vsys_copy_4d_batch(const void* src, void* dst, int64_t nops, const int64_t* desc, void* stream) {
   if (!src || !dst || (nops > 0 && !desc)) return VSYS_ERR_ARG;
   if (nops < 0 || nops > VSYS_COPY_BATCH_MAX) return VSYS_ERR_SHAPE;

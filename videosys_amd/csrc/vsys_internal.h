@@ -170,6 +170,12 @@ int launch_t5_attention_mfma(const bf16_t* qkv, int64_t row_stride, int inner, c
                              int kv_len, bf16_t* kp, bf16_t* vt, bf16_t* out, int64_t out_stride, int L, int heads,
                              hipStream_t stream);
 
+// CLIP text encoder pieces (clip_ops.hip)
+int launch_clip_attention_d64(const bf16_t* qkv, int64_t row_stride, int inner, bf16_t* out, int64_t out_stride, int B, int L,
+                              hipStream_t stream);
+int launch_splitk_reduce_bias_act(const float* part, int S, int64_t slab, int64_t ldp, const bf16_t* res, int64_t ldr, bf16_t* out,
+                                  int64_t ldo, int M, int N, const bf16_t* bias, int act, hipStream_t stream);
+
 int launch_gemm(const GemmParams& p, int epi, hipStream_t stream);
 int launch_gemm2(const GemmParams& p, int epi, int wide, hipStream_t stream);
 int launch_gemm2_qkv_kv(const GemmParams& p, hipStream_t stream);   // EPI_LN_QKV_KV (gemm2_bf16.hip); raster fields as given

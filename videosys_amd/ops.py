@@ -914,12 +914,14 @@ def linear_skinny(x, M, w, res=None, out=None, nsplit=None, part=None, wide=None
     return out
 
 
-def gather_rows(table, ids):
-    _chk(table, ids)
-    _bf16(table)
+def gather_rows(table, ids, out=None):
+    _chk(table, ids, out)
+    _bf16(table, out)
     assert ids.dtype == torch.int64 and ids.is_contiguous() and table.is_contiguous()
     n, C = ids.numel(), table.shape[1]
-    out = torch.empty(n, C, dtype=torch.bfloat16, device=table.device)
+    if out is None:
+        out = torch.empty(n, C, dtype=torch.bfloat16, device=table.device)
+    assert out.is_contiguous() and out.numel() >= n * C
     _call("vsys_gather_rows", _p(table), _p(ids), _p(out), n, C, table.shape[0])
     return out
 

@@ -152,3 +152,47 @@ def build_text_encoder(spec, tokenizer=None, *, device, caption_channels: int = 
             spec.tokenizer = tokenizer
         return spec
     raise TypeError(f"text_encoder: expected a callable, a torch module, a directory or 'synthetic:<seed>', got {type(spec).__name__}")
+
+
+def clip_encoder_from(cfg: dict, sd, device):
+    """A clip.CLIPTextEncoder with the geometry of an HF CLIP text ``config.json`` and the weights of its state dict."""
+    from .clip import CLIPTextEncoder
+
+    enc = CLIPTextEncoder(**ctor_kwargs(CLIPTextEncoder.__init__, cfg), device=device)
+    enc.load_state_dict(sd)
+    return enc
+
+
+def build_clip_encoder(spec, tokenizer=None, *, device, geometry: dict, tokenizer_path=None):
+    """(encoder, tokenizer) of one of the two CLIP slots of the Vchitect pipeline (``text_encoder`` / ``text_encoder_2``,
+    pipeline_vchitect.py:194-201) from whatever the constructor was given — the counterpart of build_text_encoder for objects that are
+    called as ``CLIPTextModelWithProjection`` is (``enc(ids, output_hidden_states=True)``):
+      * None                      -> (None, tokenizer)
+      * ``"synthetic:<seed>"``    -> clip.CLIPTextEncoder of ``geometry`` with seeded weights + clip.ClipByteTokenizer (offline)
+      * a LOCAL directory         -> the HF checkpoint in it (config.json + model.safetensors); tokenizer from ``tokenizer`` or, when
+                                     that is None and ``tokenizer_path`` is a directory, ``CLIPTokenizer.from_pretrained`` of it
+      * a torch module (HF ``CLIPTextModelWithProjection``) -> its weights on the MI355X encoder (the module itself never runs)
+      * any other callable        -> itself (an injected encoder)."""
+    import os
+
+    from .clip import CLIPTextEncoder, ClipByteTokenizer
+
+    if spec is None or isinstance(spec, CLIPTextEncoder):
+        return spec, tokenizer
+    if isinstance(spec, str):
+        if spec.startswith("synthetic:"):
+            enc = CLIPTextEncoder(**geometry, device=device).init_random_(int(spec.split(":", 1)[1]))
+            return enc, tokenizer or ClipByteTokenizer(enc.config.vocab_size)
+        cfg, sd = read_component(spec)
+        if sd is None or not cfg:
+            raise FileNotFoundError(f"text encoder directory {spec!r}: expected config.json and model.safetensors in it")
+        if tokenizer is None and tokenizer_path and os.path.isdir(tokenizer_path):
+            from transformers import CLIPTokenizer
+
+            tokenizer = CLIPTokenizer.from_pretrained(tokenizer_path, local_files_only=True)
+        return clip_encoder_from(cfg, sd, device), tokenizer
+    if is_foreign_module(spec):
+        return clip_encoder_from(*module_state(spec), device), tokenizer
+    if callable(spec):
+        return spec, tokenizer
+    raise TypeError(f"text_encoder: expected a callable, a torch module, a directory or 'synthetic:<seed>', got {type(spec).__name__}")

@@ -4,11 +4,14 @@ sampling with VchitectXLTransformerModel (vchitect.py) -> SD3 VAE decode (vae_sd
 
 ``VchitectConfig`` / ``VchitectPABConfig`` take the reference's keywords with its defaults and drop into ``VideoSysEngine``.
 
-Text side.  The two CLIP encoders (CLIP-L, CLIP-bigG) are NOT built on the MI355X kernels: ``text_encoder`` / ``text_encoder_2`` are
-objects the caller injects and that are called exactly as :368-374 calls them (``enc(ids, output_hidden_states=True)``: element 0 is
-the pooled embedding, ``.hidden_states[-2]`` or ``[-(clip_skip + 2)]`` the prompt embedding), or the caller passes ``prompt_embeds`` +
-``pooled_prompt_embeds`` and the negative pair.  ``text_encoder_3`` is this build's T5 (t5.py) at max length 256, ``None`` gives the
-zeros of :295-300.  Tokenizers plug in as everywhere in this package.
+Text side.  The two CLIP encoders (CLIP-L, CLIP-bigG) are clip.CLIPTextEncoder (causal attention at head dim 64 and the
+weight-streaming linears with bias and activation, clip.py): ``text_encoder`` / ``text_encoder_2`` take ``"synthetic:<seed>"``, a
+local directory (config.json + model.safetensors), a torch module holding the HF weights, or any object that is called exactly as
+:368-374 calls them (``enc(ids, output_hidden_states=True)``: element 0 is the pooled embedding, ``.hidden_states[-2]`` or
+``[-(clip_skip + 2)]`` the prompt embedding); left at None they are read from ``<model_path>/text_encoder`` / ``text_encoder_2`` when
+that is a local checkpoint, else they stay None and the caller passes ``prompt_embeds`` + ``pooled_prompt_embeds`` and the negative
+pair.  ``text_encoder_3`` is this build's T5 (t5.py) at max length 256, ``None`` gives the zeros of :295-300.  Tokenizers plug in as
+everywhere in this package.
 
 Sampler.  ``FlowMatchEulerDiscreteScheduler`` below restates diffusers' class as the pipeline uses it.  One model object is called
 twice per step, uncond first then text (:925-941), so VchitectAttention's PAB counters advance twice per step and the second call of a
@@ -37,8 +40,10 @@ import torch
 
 from . import ops, pab, program
 from .pab import PABConfig
-from .pipeline import VideoSysPipeline, VideoSysPipelineOutput, build_text_encoder, is_foreign_module, module_state
+from .pipeline import (VideoSysPipeline, VideoSysPipelineOutput, build_clip_encoder, build_text_encoder, is_foreign_module,
+                       module_state)
 from .utils import ctor_kwargs, progress_wrap, randn_tensor as _randn, read_component
+from .clip import CLIP_BIGG, CLIP_L, CLIPTextEncoder
 from .vchitect import VchitectXLTransformerModel, synth_state_dict
 
 
@@ -69,6 +74,8 @@ class VchitectConfig:
         self.enable_pab = enable_pab
         self.pab_config = pab_config
         self.transformer_config = extra.pop("transformer_config", None)  # extension: geometry override for tests
+        # extension: geometry overrides of the two "synthetic:<seed>" CLIP encoders, {"text_encoder": {...}, "text_encoder_2": {...}}
+        self.clip_config = extra.pop("clip_config", None)
         if extra:
             raise TypeError(f"unexpected VchitectConfig kwargs: {sorted(extra)}")
 
@@ -167,8 +174,9 @@ class VchitectXLPipeline(VideoSysPipeline):
         """pipeline_vchitect.py:174-264, same parameter order.  Components left at None are read from ``config.model_path`` when that is
         a LOCAL checkpoint directory in the published layout (``transformer/``, ``vae/``, ``scheduler/``, ``text_encoder_3/`` +
         ``tokenizer_3/``); ``"synthetic:<seed>"`` builds seeded transformer and SD3 VAE weights; a hub id cannot be fetched (published
-        geometry, seeded transformer weights, no VAE: generate() then returns latents).  ``text_encoder`` / ``text_encoder_2``: injected
-        CLIP objects or None (module docstring).  ``text_encoder_3``: a t5.T5TextEncoder-like callable, a torch module holding HF T5
+        geometry, seeded transformer weights, no VAE: generate() then returns latents).  ``text_encoder`` / ``text_encoder_2``:
+        ``"synthetic:<seed>"``, a directory, a torch module with the HF weights, an injected CLIP object, or None = ``text_encoder/`` /
+        ``text_encoder_2/`` (+ ``tokenizer/`` / ``tokenizer_2/``) of a local ``model_path`` (pipeline.build_clip_encoder).  ``text_encoder_3``: a t5.T5TextEncoder-like callable, a torch module holding HF T5
         weights (+ ``tokenizer_3``), a directory or ``"synthetic:<seed>"`` (pipeline.build_text_encoder); None = the zeros of :295-300."""
         self._config = config
         self._dtype = self._check_dtype(dtype)
@@ -196,8 +204,18 @@ class VchitectXLPipeline(VideoSysPipeline):
         elif is_foreign_module(vae):
             vae = self._vae_from_state(*module_state(vae))
         self.vae = vae
-        self.text_encoder, self.text_encoder_2 = text_encoder, text_encoder_2
-        self.tokenizer, self.tokenizer_2 = tokenizer, tokenizer_2
+        clips = []
+        for sub, tok_sub, spec, tok in (("text_encoder", "tokenizer", text_encoder, tokenizer),
+                                        ("text_encoder_2", "tokenizer_2", text_encoder_2, tokenizer_2)):
+            tok_path = None
+            if spec is None and isinstance(name, str) and os.path.isdir(os.path.join(name, sub)):   # (:194-201 from_pretrained subfolders)
+                spec, tok_path = os.path.join(name, sub), os.path.join(name, tok_sub)
+            clips.append(build_clip_encoder(spec, tok, device=self._device, geometry=self._clip_geometry(sub), tokenizer_path=tok_path))
+        (self.text_encoder, self.tokenizer), (self.text_encoder_2, self.tokenizer_2) = clips
+        widths = [e.config.hidden_size for e in (self.text_encoder, self.text_encoder_2) if isinstance(e, CLIPTextEncoder)]
+        if sum(widths) > self.transformer.config.joint_attention_dim:
+            raise ValueError(f"the CLIP hidden sizes {widths} side by side are wider than joint_attention_dim = "
+                             f"{self.transformer.config.joint_attention_dim}: encode_prompt pads them to the T5 width (:494-496)")
         if text_encoder_3 is None and isinstance(name, str) and os.path.isdir(os.path.join(name, "text_encoder_3")):
             text_encoder_3 = os.path.join(name, "text_encoder_3")
         self.max_sequence_length_t5 = 256
@@ -214,11 +232,23 @@ class VchitectXLPipeline(VideoSysPipeline):
         self.step_stats = {"recorded": 0, "replayed": 0, "eager": 0}
         self.pab_trace: List[list] = []   # PAB on: per model call of the last generate(), every block's (temporal, cross, spatial)
         self._set_parallel()
-        self._init_stages(config.cpu_offload, self._device, text_encoder_3=getattr(self.text_encoder_3, "encoder", None),
+        own_clip = lambda e: e if isinstance(e, CLIPTextEncoder) else None   # (injected objects look after their own weights)
+        self._init_stages(config.cpu_offload, self._device, text_encoder=own_clip(self.text_encoder),
+                          text_encoder_2=own_clip(self.text_encoder_2), text_encoder_3=getattr(self.text_encoder_3, "encoder", None),
                           transformer=self.transformer, vae=self.vae)
 
     tokenizer_3 = property(lambda self: getattr(self.text_encoder_3, "tokenizer", None))
     vae_decoder = property(lambda self: self.vae)
+
+    def _clip_geometry(self, slot: str) -> dict:
+        """Constructor keywords of the ``"synthetic:<seed>"`` encoder of ``slot``: CLIP-L for ``text_encoder``, CLIP-bigG for
+        ``text_encoder_2``.  The transformer's ``pooled_projection_dim`` is the two ``projection_dim``s side by side, split 3 : 5
+        (2048 = 768 + 1280); ``config.clip_config[slot]`` overrides single fields."""
+        pd = self.transformer.config.pooled_projection_dim
+        first = pd * 3 // 8
+        geo = dict(CLIP_L, projection_dim=first) if slot == "text_encoder" else dict(CLIP_BIGG, projection_dim=pd - first)
+        geo.update((getattr(self._config, "clip_config", None) or {}).get(slot, {}))
+        return geo
 
     def _vae_from_state(self, cfg, sd):
         from .vae_sd3 import SCALING_FACTOR, SHIFT_FACTOR, AutoencoderKLSD3Decoder
@@ -262,6 +292,7 @@ class VchitectXLPipeline(VideoSysPipeline):
         if self.text_encoder_3 is None:
             return torch.zeros((batch_size, self.max_sequence_length_t5, self.transformer.config.joint_attention_dim), device=device,
                                dtype=dtype or self._dtype)
+        self._enter_stage("text_encoder_3")
         e = self.text_encoder_3(list(prompt))
         e = e[0] if isinstance(e, tuple) else e
         e = e.reshape(batch_size, e.shape[-2], e.shape[-1]).to(device=device)
@@ -270,7 +301,7 @@ class VchitectXLPipeline(VideoSysPipeline):
 
     def _get_clip_prompt_embeds(self, prompt: Union[str, List[str]], num_images_per_prompt: int = 1, device=None,
                                 clip_skip: Optional[int] = None, clip_model_index: int = 0):
-        """pipeline_vchitect.py:333-386 on the injected CLIP objects -> (prompt_embeds [B, 77, d], pooled [B, d'])."""
+        """pipeline_vchitect.py:333-386 on the CLIP encoder of the slot -> (prompt_embeds [B, 77, d], pooled [B, d'])."""
         device = device or self._device
         tokenizer = [self.tokenizer, self.tokenizer_2][clip_model_index]
         text_encoder = [self.text_encoder, self.text_encoder_2][clip_model_index]
@@ -285,6 +316,7 @@ class VchitectXLPipeline(VideoSysPipeline):
             removed_text = tokenizer.batch_decode(untruncated_ids[:, self.tokenizer_max_length - 1: -1])
             logging.warning("The following part of your input was truncated because CLIP can only handle sequences up to"
                             f" {self.tokenizer_max_length} tokens: {removed_text}")
+        self._enter_stage(("text_encoder", "text_encoder_2")[clip_model_index])   # (cpu_offload: model_cpu_offload_seq order)
         prompt_embeds = text_encoder(text_input_ids.to(device), output_hidden_states=True)
         pooled_prompt_embeds = prompt_embeds[0]
         if clip_skip is None:
@@ -498,7 +530,7 @@ class VchitectXLPipeline(VideoSysPipeline):
         have_clip = self.text_encoder is not None and self.text_encoder_2 is not None
         if not have_clip and (prompt_embeds is None or negative_prompt_embeds is None):
             raise RuntimeError(self._NO_CLIP)
-        self._enter_stage("text_encoder_3")
+        # (cpu_offload: every encoder enters its own stage when encode_prompt calls it)
         prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = self.encode_prompt(
             prompt=prompt, prompt_2=prompt_2, prompt_3=prompt_3, negative_prompt=negative_prompt, negative_prompt_2=negative_prompt_2,
             negative_prompt_3=negative_prompt_3, do_classifier_free_guidance=True, prompt_embeds=prompt_embeds,
