@@ -365,6 +365,21 @@ int vsys_attn_temporal_d64(const void* q_vid, int64_t q_vid_stride, const void* 
                            int64_t out_vid_stride, void* out_txt, int64_t out_txt_stride, int64_t B, int64_t T, int64_t S, int64_t L,
                            int64_t heads, void* stream);
 
+/* vsys_attn_temporal_d64 on the receive image of a sequence-parallel frame -> token switch (attentions.py:733-757 dynamic_switch):
+ * the same arithmetic, tile walk and rounding, hence the same bits; only the row of frame t differs.  The T real frames lie in slabs of
+ * Tl frames (slab = the rank the frames came from): frame t of token (b, s) is row
+ *     (t / Tl) * slab_rows + (b * Tl + t % Tl) * n + s          n = S (video tensors, slab_vid_rows) or L (text, slab_txt_rows)
+ * of q / k / v AND of the output, which is therefore the image the return collective sends.  Frames past T in the last slab are
+ * neither read nor written.  Tl >= 1.  Tl >= T is one slab (the slab strides are then unused) whose samples lie Tl frames apart:
+ * Tl == T is exactly vsys_attn_temporal_d64's call, Tl > T the same with Tl - T unused frames behind every sample.  With more than one
+ * slab a slab stride below B * Tl * n is refused.  All other checks as vsys_attn_temporal_d64.  Not in the op table:
+ * a recorded step issues it from the host closure of the collective it feeds (program.host_call). */
+int vsys_attn_temporal_d64_img(const void* q_vid, int64_t q_vid_stride, const void* k_vid, int64_t k_vid_stride, const void* v_vid,
+                               int64_t v_vid_stride, const void* q_txt, int64_t q_txt_stride, const void* k_txt, int64_t k_txt_stride,
+                               const void* v_txt, int64_t v_txt_stride, const void* rope_cos_f32, const void* rope_sin_f32, void* out_vid,
+                               int64_t out_vid_stride, void* out_txt, int64_t out_txt_stride, int64_t B, int64_t T, int64_t Tl,
+                               int64_t slab_vid_rows, int64_t slab_txt_rows, int64_t S, int64_t L, int64_t heads, void* stream);
+
 /* out[r] = bf16(bf16(a[r] * scale) + b[r]) over rows of C bf16 (C % 8 == 0; strides in elements, % 8 == 0), out may be a or b:
  * `hidden_states * 1.1 + cross_output` of VchitectAttnProcessor (attentions.py:899) with the reference's two roundings. */
 int vsys_scale_add_rows(const void* a, int64_t a_stride, const void* b, int64_t b_stride, void* out, int64_t out_stride, int64_t rows,

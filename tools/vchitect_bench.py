@@ -7,7 +7,15 @@
 
     python tools/vchitect_bench.py [--reps 5] [--out FILE.json] [--skip-step] [--skip-decode]
 
-Prints one JSON line; device time from HIP events around ``reps`` repetitions after one warm-up."""
+Prints one JSON line; device time from HIP events around ``reps`` repetitions after one warm-up.
+
+    python tools/vchitect_bench.py --ranks 8 [--reps 20] [--out FILE.json]
+
+times the same step as ONE rank (rank 0) of an N-way sequence-parallel group with the wire stubbed (tools/local_group.StubGroup: a
+collective is a device copy of the rank's own send buffer, so the results are meaningless and the time is the rank's own work):
+the recorded step of every route — "rows" (unpack, old kernel, pack) and "image" (vsys_attn_temporal_d64_img on the exchange image)
+over all_to_all_single, "p2p_rows" over the one-kernel exchange — and of the single-rank model in the same run, replayed in turn;
+per route the median of ``reps`` replays, each timed on the host between two stream synchronisations, and the launch count."""
 import argparse
 import json
 import os
@@ -36,7 +44,10 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-step", action="store_true")
     ap.add_argument("--skip-decode", action="store_true")
+    ap.add_argument("--ranks", type=int, default=0, help="time one rank of an N-way sequence-parallel group, wire stubbed")
     args = ap.parse_args()
+    if args.ranks:
+        return ranks_main(args)
     dev = torch.device("cuda:0")
     F, h, w = 40, 36, 60
     res = {"device": torch.cuda.get_device_name(0), "frames": F, "latent": [h, w], "reps": args.reps}
@@ -70,6 +81,79 @@ def main():
 
         res["step_ms_2b_40f_36x60"] = round(timed(step, args.reps), 3)
         res["step_stats"] = dict(pipe.step_stats)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+def ranks_main(args):
+    import statistics
+    import time
+    from types import SimpleNamespace
+
+    from tools.local_group import StubGroup
+    from videosys_amd import VchitectConfig, VchitectXLPipeline, ops, pab
+
+    dev, P = torch.device("cuda:0"), args.ranks
+    F, h, w, L = 40, 36, 60, 77 + 256
+    reps = max(args.reps, 20)
+    g = torch.Generator().manual_seed(0)
+    lat = torch.randn(1, F, 16, h, w, generator=g).to(dev)
+    pipe = VchitectXLPipeline(VchitectConfig("Vchitect/Vchitect-2.0-2B", transformer_config=dict(
+        num_layers=18, num_attention_heads=18, attention_head_dim=64, caption_projection_dim=1152, joint_attention_dim=4096,
+        pooled_projection_dim=2048)), vae=None)
+    pab.set_pab_manager(None)
+    emb = torch.randn(2, L, 4096, generator=g).to(torch.bfloat16)
+    pooled = torch.randn(2, 2048, generator=g).to(torch.bfloat16)
+    z, enc, pl, pred = pipe._step_buffers(lat, emb, pooled)
+    tr = pipe.transformer
+
+    def step():
+        pipe._issue_pair(z, enc, pl, pred, 500.0)
+        ops.cfg_euler_step(z, pred, 4.0, -1e-4)
+
+    mgr = SimpleNamespace(sp_size=P, cp_size=1, dp_size=1, dp_rank=0, sp_rank=0, cp_rank=0, sp_group=StubGroup(P, 0), cp_group=None)
+    programs, info = {}, {}
+    for name in ("single", "rows", "image", "p2p_rows"):
+        if name == "single":
+            tr.enable_parallel(1, 1, False)
+        else:
+            pipe._set_parallel(parallel_mgr=mgr)
+            if name != "p2p_rows":
+                tr._sp.p2p = None
+            for b in tr.transformer_blocks:
+                b.attn.attn_route = "image" if name == "image" else "rows"
+        pipe._step_program = None
+        step()                                  # records the pair of model calls
+        step()                                  # first replay
+        torch.cuda.synchronize()
+        programs[name] = pipe._step_program
+        prog = pipe._step_program[1]
+        assert prog is not None, f"the {name} step was not recordable"
+        # launches: the recorded ones + the guidance / Euler launch + what host actions launch themselves (the image route's attention,
+        # one per block and model call, has no op code and is issued by the closure of the collective it feeds)
+        closure_launches = 2 * len(tr.transformer_blocks) if name == "image" else 0
+        info[name] = {"launches_per_step": prog.n_launches + 1 + closure_launches,
+                      "of_which_issued_by_host_actions": closure_launches,
+                      "host_actions_per_step": sum(1 for seg in prog.segments if not isinstance(seg, tuple))}
+    times = {name: [] for name in programs}
+    for _ in range(reps):                       # the routes in turn, so that drift hits them alike
+        for name, ent in programs.items():
+            pipe._step_program = ent
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            step()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    res = {"device": torch.cuda.get_device_name(0), "ranks": P, "rank": 0, "frames": F, "latent": [h, w], "text_tokens": L, "replays": reps,
+           "what": "wire stubbed, random weights; per-rank step (two model calls + guidance) in ms, median of the replays; a collective of the "
+                   "stub is one device copy and is not counted as a launch"}
+    for name, ts in times.items():
+        info[name].update(step_ms_median=round(statistics.median(ts), 3), step_ms_min=round(min(ts), 3), step_ms_max=round(max(ts), 3))
+    res["routes"] = info
     line = json.dumps(res)
     print(line)
     if args.out:

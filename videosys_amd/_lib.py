@@ -65,6 +65,8 @@ SIGNATURES = {
     "vsys_attn_temporal_d72": [_ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _f32, _ptr],
     "vsys_attn_temporal_d64": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _i64,
                                _i64, _i64, _i64, _i64, _i64, _ptr],
+    "vsys_attn_temporal_d64_img": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _i64,
+                                   _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _ptr],
     "vsys_scale_add_rows": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _f32, _ptr],
     "vsys_vae_first_im2col_nc": [_ptr, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _ptr, _ptr],
     "vsys_pixels_to_u8": [_ptr, _ptr, _i64, _i64, _ptr, _i64, _i64, _ptr],

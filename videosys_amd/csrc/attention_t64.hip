@@ -36,6 +36,9 @@ struct T64Params {
   bf16_t *o_vid, *o_txt;
   int64_t o_vid_ld, o_txt_ld;
   int B, T, S, L, heads, hgroups;
+  // the exchange image (attn_temporal_d64_img_kernel only): frame t lies in slab t / Tl, at frame t % Tl of the slab's [B][Tl][n] rows
+  int Tl;
+  int64_t slab_vid, slab_txt;
 };
 
 // one rotary pair: (x0 + i x1)(c + i s) in fp32, back to bf16
@@ -48,7 +51,11 @@ __device__ __forceinline__ uint4 t64_rope(uint4 u, const float* __restrict__ cos
   return make_uint4(t64_rot(u.x, c.x, s.x), t64_rot(u.y, c.y, s.y), t64_rot(u.z, c.z, s.z), t64_rot(u.w, c.w, s.w));
 }
 
-__global__ __launch_bounds__(256, 2) void attn_temporal_d64_kernel(const T64Params p) {
+// IMG = false: rows (b, t, s).  IMG = true: the receive image of the frame -> token switch of a sequence-parallel step,
+// [slab = source rank][b][t % Tl][s] with a slab stride in rows; T counts the real frames, so the tail of the last slab is never touched.
+// Everything after the row address is the same code: same tile walk, same LDS use, same rounding, same bits.
+template <bool IMG>
+__device__ __forceinline__ void attn_temporal_d64_body(const T64Params& p) {
   __shared__ __attribute__((aligned(16))) char smem[4 * T64_WAVE_LDS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int piece = lane & 7, rsub = lane >> 3;      // cooperative loads: 8 lanes x 16 bytes = one head of one frame
@@ -62,7 +69,17 @@ __global__ __launch_bounds__(256, 2) void attn_temporal_d64_kernel(const T64Para
   const bool active = head < p.heads;               // (a wave without a head stages zeros and stores nothing; it keeps the barriers)
   const bool txt = sp >= p.S, rope = p.cos != nullptr;
   const int64_t n = txt ? p.L : p.S;                // rows per frame of this token's tensor
-  const int64_t r0 = (int64_t)b * T * n + (txt ? sp - p.S : sp);
+  const int64_t r0 = (int64_t)b * (IMG ? p.Tl : T) * n + (txt ? sp - p.S : sp);
+  const int64_t slab = txt ? p.slab_txt : p.slab_vid;
+  // row of frame t of this token (one division per 16-byte load in the image: 12 per lane and 32-key chunk, beside 2048 FMAs)
+  auto frow = [&](int t) -> int64_t {
+    if constexpr (IMG) {
+      const int sl = t / p.Tl;
+      return r0 + (int64_t)sl * slab + (int64_t)(t - sl * p.Tl) * n;
+    } else {
+      return r0 + (int64_t)t * n;
+    }
+  };
   const int64_t col = (int64_t)head * 64 + piece * 8;
   const int64_t qld = txt ? p.q_txt_ld : p.q_vid_ld, kld = txt ? p.k_txt_ld : p.k_vid_ld, vld = txt ? p.v_txt_ld : p.v_vid_ld,
                 old = txt ? p.o_txt_ld : p.o_vid_ld;
@@ -78,7 +95,7 @@ __global__ __launch_bounds__(256, 2) void attn_temporal_d64_kernel(const T64Para
       const int r = i * 8 + rsub, t = q0 + r;
       uint4 u = make_uint4(0, 0, 0, 0);
       if (active && t < T) {
-        u = *reinterpret_cast<const uint4*>(qb + (r0 + (int64_t)t * n) * qld);
+        u = *reinterpret_cast<const uint4*>(qb + frow(t) * qld);
         if (rope) u = t64_rope(u, p.cos + t * 32 + piece * 4, p.sin + t * 32 + piece * 4);
       }
       *reinterpret_cast<uint4*>(wl + r * T64_QPITCH + piece * 16) = u;
@@ -102,8 +119,8 @@ __global__ __launch_bounds__(256, 2) void attn_temporal_d64_kernel(const T64Para
         const int r = i * 8 + rsub, t = k0 + r;
         uint4 ku = make_uint4(0, 0, 0, 0), vu = make_uint4(0, 0, 0, 0);
         if (active && t < T) {
-          ku = *reinterpret_cast<const uint4*>(kb + (r0 + (int64_t)t * n) * kld);
-          vu = *reinterpret_cast<const uint4*>(vb + (r0 + (int64_t)t * n) * vld);
+          ku = *reinterpret_cast<const uint4*>(kb + frow(t) * kld);
+          vu = *reinterpret_cast<const uint4*>(vb + frow(t) * vld);
           if (rope) ku = t64_rope(ku, p.cos + t * 32 + piece * 4, p.sin + t * 32 + piece * 4);
         }
         *reinterpret_cast<uint4*>(wl + r * 128 + piece * 16) = ku;
@@ -166,10 +183,32 @@ __global__ __launch_bounds__(256, 2) void attn_temporal_d64_kernel(const T64Para
     for (int i = 0; i < 8; ++i) {
       const int r = i * 8 + rsub, t = q0 + r;
       if (active && t < T)
-        *reinterpret_cast<uint4*>(ob + (r0 + (int64_t)t * n) * old) = *reinterpret_cast<const uint4*>(wl + r * T64_QPITCH + piece * 16);
+        *reinterpret_cast<uint4*>(ob + frow(t) * old) = *reinterpret_cast<const uint4*>(wl + r * T64_QPITCH + piece * 16);
     }
     __syncthreads();
   }
+}
+
+__global__ __launch_bounds__(256, 2) void attn_temporal_d64_kernel(const T64Params p) { attn_temporal_d64_body<false>(p); }
+__global__ __launch_bounds__(256, 2) void attn_temporal_d64_img_kernel(const T64Params p) { attn_temporal_d64_body<true>(p); }
+
+// the checks both entry points share; 0 or a VSYS_ERR code (a refused call launches nothing)
+int t64_check(const void* const* ptrs, const int64_t* lds_v, const int64_t* lds_t, int B, int T, int S, int L, int heads) {
+  if (B < 1 || T < 1 || S < 0 || L < 0 || (int64_t)S + L < 1 || heads < 1 || (int64_t)heads * 64 > 0x7fffffff) return VSYS_ERR_SHAPE;
+  if ((ptrs[8] == nullptr) != (ptrs[9] == nullptr)) return VSYS_ERR_ARG;
+  if (S > 0 && (!ptrs[0] || !ptrs[1] || !ptrs[2] || !ptrs[3])) return VSYS_ERR_ARG;
+  if (L > 0 && (!ptrs[4] || !ptrs[5] || !ptrs[6] || !ptrs[7])) return VSYS_ERR_ARG;
+  const int64_t width = (int64_t)heads * 64;
+  for (int i = 0; i < 4; ++i) {
+    if (S > 0 && lds_v[i] < width) return VSYS_ERR_SHAPE;
+    if (L > 0 && lds_t[i] < width) return VSYS_ERR_SHAPE;
+    if ((S > 0 && (lds_v[i] % 8)) || (L > 0 && (lds_t[i] % 8))) return VSYS_ERR_ALIGN;
+  }
+  for (int i = 0; i < 10; ++i)
+    if (reinterpret_cast<uintptr_t>(ptrs[i]) % 16) return VSYS_ERR_ALIGN;
+  const int64_t grid = (int64_t)B * ((int64_t)S + L) * ((heads + 3) / 4);
+  if (grid > 0x7fffffff || (int64_t)T * 32 > 0x7fffffff) return VSYS_ERR_SHAPE;
+  return 0;
 }
 
 }  // namespace
@@ -179,30 +218,45 @@ int launch_attn_temporal_d64(const bf16_t* q_vid, int64_t q_vid_ld, const bf16_t
                              const bf16_t* v_txt, int64_t v_txt_ld, const float* rope_cos, const float* rope_sin, bf16_t* out_vid,
                              int64_t out_vid_ld, bf16_t* out_txt, int64_t out_txt_ld, int B, int T, int S, int L, int heads,
                              hipStream_t stream) {
-  if (B < 1 || T < 1 || S < 0 || L < 0 || (int64_t)S + L < 1 || heads < 1 || (int64_t)heads * 64 > 0x7fffffff) return VSYS_ERR_SHAPE;
-  if ((rope_cos == nullptr) != (rope_sin == nullptr)) return VSYS_ERR_ARG;
-  if (S > 0 && (!q_vid || !k_vid || !v_vid || !out_vid)) return VSYS_ERR_ARG;
-  if (L > 0 && (!q_txt || !k_txt || !v_txt || !out_txt)) return VSYS_ERR_ARG;
-  const int64_t width = (int64_t)heads * 64;
   const int64_t lds_v[4] = {q_vid_ld, k_vid_ld, v_vid_ld, out_vid_ld}, lds_t[4] = {q_txt_ld, k_txt_ld, v_txt_ld, out_txt_ld};
   const void* ptrs[10] = {q_vid, k_vid, v_vid, out_vid, q_txt, k_txt, v_txt, out_txt, rope_cos, rope_sin};
-  for (int i = 0; i < 4; ++i) {
-    if (S > 0 && lds_v[i] < width) return VSYS_ERR_SHAPE;
-    if (L > 0 && lds_t[i] < width) return VSYS_ERR_SHAPE;
-    if ((S > 0 && (lds_v[i] % 8)) || (L > 0 && (lds_t[i] % 8))) return VSYS_ERR_ALIGN;
-  }
-  for (int i = 0; i < 10; ++i)
-    if (reinterpret_cast<uintptr_t>(ptrs[i]) % 16) return VSYS_ERR_ALIGN;
+  if (const int rc = t64_check(ptrs, lds_v, lds_t, B, T, S, L, heads)) return rc;
   const int hgroups = (heads + 3) / 4;
   const int64_t grid = (int64_t)B * ((int64_t)S + L) * hgroups;
-  if (grid > 0x7fffffff || (int64_t)T * 32 > 0x7fffffff) return VSYS_ERR_SHAPE;
   T64Params p;
   p.q_vid = q_vid; p.k_vid = k_vid; p.v_vid = v_vid; p.q_txt = q_txt; p.k_txt = k_txt; p.v_txt = v_txt;
   p.q_vid_ld = q_vid_ld; p.k_vid_ld = k_vid_ld; p.v_vid_ld = v_vid_ld; p.q_txt_ld = q_txt_ld; p.k_txt_ld = k_txt_ld; p.v_txt_ld = v_txt_ld;
   p.cos = rope_cos; p.sin = rope_sin;
   p.o_vid = out_vid; p.o_txt = out_txt; p.o_vid_ld = out_vid_ld; p.o_txt_ld = out_txt_ld;
   p.B = B; p.T = T; p.S = S; p.L = L; p.heads = heads; p.hgroups = hgroups;
+  p.Tl = T; p.slab_vid = p.slab_txt = 0;
   hipLaunchKernelGGL(attn_temporal_d64_kernel, dim3((unsigned)grid), dim3(256), 0, stream, p);
+  return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
+}
+
+int launch_attn_temporal_d64_img(const bf16_t* q_vid, int64_t q_vid_ld, const bf16_t* k_vid, int64_t k_vid_ld, const bf16_t* v_vid,
+                                 int64_t v_vid_ld, const bf16_t* q_txt, int64_t q_txt_ld, const bf16_t* k_txt, int64_t k_txt_ld,
+                                 const bf16_t* v_txt, int64_t v_txt_ld, const float* rope_cos, const float* rope_sin, bf16_t* out_vid,
+                                 int64_t out_vid_ld, bf16_t* out_txt, int64_t out_txt_ld, int B, int T, int Tl, int64_t slab_vid,
+                                 int64_t slab_txt, int S, int L, int heads, hipStream_t stream) {
+  const int64_t lds_v[4] = {q_vid_ld, k_vid_ld, v_vid_ld, out_vid_ld}, lds_t[4] = {q_txt_ld, k_txt_ld, v_txt_ld, out_txt_ld};
+  const void* ptrs[10] = {q_vid, k_vid, v_vid, out_vid, q_txt, k_txt, v_txt, out_txt, rope_cos, rope_sin};
+  if (const int rc = t64_check(ptrs, lds_v, lds_t, B, T, S, L, heads)) return rc;
+  if (Tl < 1) return VSYS_ERR_SHAPE;
+  if (T > Tl) {   // more than one slab: a slab holds its B x Tl frames, so slabs never overlap
+    if (S > 0 && slab_vid < (int64_t)B * Tl * S) return VSYS_ERR_SHAPE;
+    if (L > 0 && slab_txt < (int64_t)B * Tl * L) return VSYS_ERR_SHAPE;
+  }
+  const int hgroups = (heads + 3) / 4;
+  const int64_t grid = (int64_t)B * ((int64_t)S + L) * hgroups;
+  T64Params p;
+  p.q_vid = q_vid; p.k_vid = k_vid; p.v_vid = v_vid; p.q_txt = q_txt; p.k_txt = k_txt; p.v_txt = v_txt;
+  p.q_vid_ld = q_vid_ld; p.k_vid_ld = k_vid_ld; p.v_vid_ld = v_vid_ld; p.q_txt_ld = q_txt_ld; p.k_txt_ld = k_txt_ld; p.v_txt_ld = v_txt_ld;
+  p.cos = rope_cos; p.sin = rope_sin;
+  p.o_vid = out_vid; p.o_txt = out_txt; p.o_vid_ld = out_vid_ld; p.o_txt_ld = out_txt_ld;
+  p.B = B; p.T = T; p.S = S; p.L = L; p.heads = heads; p.hgroups = hgroups;
+  p.Tl = Tl; p.slab_vid = slab_vid; p.slab_txt = slab_txt;
+  hipLaunchKernelGGL(attn_temporal_d64_img_kernel, dim3((unsigned)grid), dim3(256), 0, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
 }
 

@@ -445,6 +445,19 @@ int vsys_attn_temporal_d64(const void* q_vid, int64_t q_vid_stride, const void* 
                                   out_txt_stride, (int)B, (int)T, (int)S_, (int)L, (int)heads, S(stream));
 }
 
+int vsys_attn_temporal_d64_img(const void* q_vid, int64_t q_vid_stride, const void* k_vid, int64_t k_vid_stride, const void* v_vid,
+                               int64_t v_vid_stride, const void* q_txt, int64_t q_txt_stride, const void* k_txt, int64_t k_txt_stride,
+                               const void* v_txt, int64_t v_txt_stride, const void* rope_cos_f32, const void* rope_sin_f32, void* out_vid,
+                               int64_t out_vid_stride, void* out_txt, int64_t out_txt_stride, int64_t B, int64_t T, int64_t Tl,
+                               int64_t slab_vid_rows, int64_t slab_txt_rows, int64_t S_, int64_t L, int64_t heads, void* stream) {
+  if (!fits_int(B) || !fits_int(T) || !fits_int(Tl) || !fits_int(S_) || !fits_int(L) || !fits_int(heads)) return VSYS_ERR_SHAPE;
+  return launch_attn_temporal_d64_img(B16(q_vid), q_vid_stride, B16(k_vid), k_vid_stride, B16(v_vid), v_vid_stride, B16(q_txt),
+                                      q_txt_stride, B16(k_txt), k_txt_stride, B16(v_txt), v_txt_stride,
+                                      reinterpret_cast<const float*>(rope_cos_f32), reinterpret_cast<const float*>(rope_sin_f32),
+                                      B16(out_vid), out_vid_stride, B16(out_txt), out_txt_stride, (int)B, (int)T, (int)Tl, slab_vid_rows,
+                                      slab_txt_rows, (int)S_, (int)L, (int)heads, S(stream));
+}
+
 int vsys_scale_add_rows(const void* a, int64_t a_stride, const void* b, int64_t b_stride, void* out, int64_t out_stride, int64_t rows,
                         int64_t C, float scale, void* stream) {
   if (!a || !b || !out) return VSYS_ERR_ARG;

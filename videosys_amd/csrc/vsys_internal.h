@@ -289,6 +289,12 @@ int launch_attn_temporal_d64(const bf16_t* q_vid, int64_t q_vid_ld, const bf16_t
                              const bf16_t* v_txt, int64_t v_txt_ld, const float* rope_cos, const float* rope_sin, bf16_t* out_vid,
                              int64_t out_vid_ld, bf16_t* out_txt, int64_t out_txt_ld, int B, int T, int S, int L, int heads,
                              hipStream_t stream);
+// the same kernel body on the exchange image of a sequence-parallel step: frame t at slab t / Tl, frame t % Tl of the slab
+int launch_attn_temporal_d64_img(const bf16_t* q_vid, int64_t q_vid_ld, const bf16_t* k_vid, int64_t k_vid_ld, const bf16_t* v_vid,
+                                 int64_t v_vid_ld, const bf16_t* q_txt, int64_t q_txt_ld, const bf16_t* k_txt, int64_t k_txt_ld,
+                                 const bf16_t* v_txt, int64_t v_txt_ld, const float* rope_cos, const float* rope_sin, bf16_t* out_vid,
+                                 int64_t out_vid_ld, bf16_t* out_txt, int64_t out_txt_ld, int B, int T, int Tl, int64_t slab_vid,
+                                 int64_t slab_txt, int S, int L, int heads, hipStream_t stream);
 int launch_scale_add_rows(const bf16_t* a, int64_t lda, const bf16_t* b, int64_t ldb, bf16_t* out, int64_t ldo, int64_t rows, int C,
                           float scale, hipStream_t stream);
 

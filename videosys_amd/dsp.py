@@ -42,12 +42,16 @@ def group_rank(group) -> int:
     return group.rank if hasattr(group, "all_to_all_single") else dist.get_rank(group)
 
 
-def all_to_all_single(recv, send, group):
+def all_to_all_single(recv, send, group, before=None):
     """Stream-ordered all-to-all on torch's current stream.  A host-side action: under a launch-program recorder it is logged
-    and re-issued on every replay (program.host_call); the buffers are the SequenceParallel object's resident staging buffers."""
+    and re-issued on every replay (program.host_call); the buffers are the SequenceParallel object's resident staging buffers.
+    ``before``: a callable issued in the same host action, in front of the collective (a launch without an op code that fills
+    ``send``: vchitect_ops.attn_temporal64_img)."""
     from . import program
 
     def issue():
+        if before is not None:
+            before()
         with COMM_TIMER.comm():
             if hasattr(group, "all_to_all_single"):
                 group.all_to_all_single(recv, send)
@@ -58,7 +62,8 @@ def all_to_all_single(recv, send, group):
     program.host_call(issue)
 
 
-def all_gather_into_tensor(out, x, group):
+def all_gather_into_tensor(out, x, group, after=None):
+    """``after``: a callable issued in the same host action, behind the collective (a torch copy out of ``out``)."""
     from . import program
 
     def issue():
@@ -67,6 +72,8 @@ def all_gather_into_tensor(out, x, group):
                 group.all_gather_into_tensor(out, x)
             else:
                 dist.all_gather_into_tensor(out, x, group=group)
+        if after is not None:
+            after()
 
     program.keep(out), program.keep(x)
     program.host_call(issue)

@@ -26,7 +26,12 @@ Batch.  The reference indexes rows 0 and 1 of the CFG pair (:925-941): it works 
 of several prompts, ``num_images_per_prompt != 1`` and ``guidance_scale <= 1`` raise ValueError here.
 
 With PAB off the pair of model calls of a step is recorded once (program.Recorder) and replayed on the later steps;
-``transformer.use_programs = False`` forces eager issue (the switch of the other models); with PAB on the steps run eager."""
+``transformer.use_programs = False`` forces eager issue (the switch of the other models); with PAB on the steps run eager.
+
+More than one rank (:266-280).  ``_set_parallel`` shards the transformer by frames (vchitect.py).  Every rank runs generate() with
+the same seed, holds the whole latent and gets the whole prediction back (the model all-gathers it), so the sampler, the recorded
+step (collectives are re-issued from the program's host actions) and the returned frames are the same on every rank; the text encoders
+and the VAE decode stay replicated."""
 from __future__ import annotations
 
 import inspect
@@ -268,11 +273,17 @@ class VchitectXLPipeline(VideoSysPipeline):
         cfg, sd = read_component(name, "vae")
         return self._vae_from_state(cfg, sd) if sd is not None else None
 
-    def _set_parallel(self, dp_size: Optional[int] = None, sp_size: Optional[int] = None, enable_cp: Optional[bool] = False):
-        """pipeline_vchitect.py:266-280: sp = world size unless given.  Sequence parallelism of the Vchitect transformer is not built:
-        more than one rank raises the transformer's NotImplementedError."""
+    def _set_parallel(self, dp_size: Optional[int] = None, sp_size: Optional[int] = None, enable_cp: Optional[bool] = False,
+                      parallel_mgr=None):
+        """pipeline_vchitect.py:266-280: sp = world size unless given.  The transformer is sharded by frames (vchitect.py: every rank
+        calls generate() with the same seed and gets the same frames, the model gathering its prediction inside); the text encoders
+        and the VAE decode stay replicated.  ``parallel_mgr`` (an extension): an injected manager instead of the process group, as
+        the transformers take it."""
         import torch.distributed as dist
 
+        self._step_program = None          # a recorded step belongs to the sharding it was recorded under
+        if parallel_mgr is not None:
+            return self.transformer.enable_parallel(parallel_mgr=parallel_mgr)
         world = dist.get_world_size() if dist.is_initialized() else 1
         if world == 1:
             return
@@ -567,6 +578,9 @@ class VchitectXLPipeline(VideoSysPipeline):
                     enc.copy_(cfg_embeds.to(enc.device, enc.dtype)[:, None].expand_as(enc))
                 negative_prompt_embeds = back.get("negative_prompt_embeds", negative_prompt_embeds)
                 negative_pooled_prompt_embeds = back.get("negative_pooled_prompt_embeds", negative_pooled_prompt_embeds)
+        from . import dsp
+
+        dsp.check_exchange(self.transformer)   # a timed-out peer-to-peer exchange left stale rows: raise here, not a corrupt video
         if self.vae is None or output_type in ("latent", "latents"):
             self._enter_stage(None)
             out = z.clone()

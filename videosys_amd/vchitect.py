@@ -8,14 +8,29 @@ vsys_flash_attn_d64 without norm / RoPE for the joint spatial and the cross atte
 AdaLayerNormContinuous (vsys_ln_modulate), FeedForward (bias + GELU and gate + residual GEMM epilogues), the time-text embedding
 (vsys_timestep_embedding, vsys_linear_small), proj_out and unpatchify, with the reference's constructor config and state-dict names.
 The pipeline around it (flow-match sampler, T5, SD3 VAE decode) is pipeline_vchitect.py.  Not built: the two CLIP text encoders (they
-are injected objects there) and sequence parallelism.
+are injected objects there).
+
+Sequence parallelism (vchitect_transformer_3d.py:326-338,543-562; attentions.py:733-757,928-949).  Frames are sharded at rest: rank r of
+P keeps frames [r Fl, (r + 1) Fl), Fl = ceil(F / P), frames past F being zero rows written after the embedding; the text rows of a frame
+travel with it.  Spatial and cross attention run on the local frames.  Around the temporal attention the NORMED activations (C wide,
+a third of q | k | v) switch to a token shard — video and text tokens separately, Sl = ceil(S / P) and Ll = ceil(L / P), zero rows
+past S and L — so every rank attends over the global F frames of its tokens with RoPE positions 0 .. F - 1; `_qkv_temp` and `_add_qkv`
+run on the token shard, and the result switches back (dsp.SequenceParallel, both its exchange routes).  Over all_to_all_single the
+attention runs on the receive image as it lies and writes the send image of the way back (``attn_route = "image"``, the measured
+default: vsys_attn_temporal_d64_img, four copy launches a block instead of eight); ``"rows"`` unpacks and packs around the old kernel
+and is the route the peer-to-peer exchange uses.  The fp32 prediction of the local frames is all-gathered into the caller's ``out``.
 
 Every launch goes through ops._call and every buffer is resident, so a step can be recorded once (program.Recorder) and replayed.
 
 Two readings of the reference that matter:
   * cross attention keys are `encoder_hidden_states_key_proj[0]` viewed as (batchsize, -1, heads, 64) (:781-786): frame 0 of SAMPLE 0,
     dealt out over the B samples in runs of L / B keys.  That is what runs here (B == 1, the only batch the reference pipeline uses,
-    gives all L keys); L % B != 0 raises, as the reference's view does.
+    gives all L keys); L % B != 0 raises, as the reference's view does.  Under sequence parallelism row 0 is row 0 OF THE LOCAL SHARD:
+    sample 0's frame r Fl.  After the first block the text rows differ per frame, so a sharded run equals the reference's sharded
+    run and not the single-process one; it is kept literally.
+  * the `cur_frame == 1` rule (:836,909-919) reads the LOCAL frame count: with one frame per rank the temporal contributions are
+    multiplied by zero.  Kept literally, as the F == 1 path: the exchange and the attention still run (the caches are filled), nothing
+    is added.
   * the `(S T)` query order of cross attention (:788) is undone by :798 and attention is row-wise in the queries, so the video rows
     (batch B, q_len F S) and the text rows (batch B, q_len F L) are two launches over the same keys; nothing is transposed."""
 from __future__ import annotations
@@ -25,7 +40,7 @@ from typing import Dict
 import numpy as np
 import torch
 
-from . import ops, pab, vchitect_ops
+from . import dsp, ops, pab, program, vchitect_ops
 from .modules import sincos_1d
 from .workspace import Workspace
 
@@ -39,6 +54,36 @@ def rope_tables(frames: int, device, theta: float = ROPE_THETA, rope_scaling_fac
     ang = torch.outer(torch.arange(frames, dtype=torch.float) / rope_scaling_factor, freqs).float()
     cis = torch.polar(torch.ones_like(ang), ang)
     return cis.real.contiguous().to(device), cis.imag.contiguous().to(device)
+
+
+class _NoGroupOfThatSize(NotImplementedError, AssertionError):
+    """enable_parallel without an injected manager asked for a dp x cp x sp mesh that is not the size of the process group initialised
+    in this process (none = 1).  A NotImplementedError for callers written when sequence parallelism was not built; also the
+    AssertionError dsp.ParallelManager raises for the same mismatch."""
+
+
+def _resolve_parallel(dp_size, sp_size, enable_cp, parallel_mgr):
+    """vchitect_transformer_3d.py:326-338: `enable_cp` with an even sp_size halves it and builds a dp x cp x sp mesh.  Returns the
+    manager to use, or None for a single rank.  The CFG split (cp > 1) is not built, as for Latte and CogVideoX."""
+    import torch.distributed as dist
+
+    if parallel_mgr is not None:
+        if enable_cp and parallel_mgr.sp_size * getattr(parallel_mgr, "cp_size", 1) > 1:
+            raise NotImplementedError("Vchitect: the CFG split (enable_cp) is not built; shard with enable_cp=False")
+        if getattr(parallel_mgr, "cp_size", 1) > 1:
+            raise NotImplementedError("Vchitect: the CFG split (cp_size > 1) is not built")
+        return parallel_mgr if parallel_mgr.sp_size > 1 else None
+    dp, sp, cp = dp_size or 1, sp_size or 1, 1
+    if enable_cp and sp % 2 == 0:
+        sp, cp = sp // 2, 2
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    if dp * cp * sp != world:
+        raise _NoGroupOfThatSize(f"Vchitect sequence parallelism: there is no process group of {dp} x {cp} x {sp} = {dp * cp * sp} ranks in "
+                                 f"this process (the initialised world has {world}); initialise torch.distributed with that many ranks, "
+                                 f"or hand in a manager (parallel_mgr=)")
+    if cp > 1:
+        raise NotImplementedError("Vchitect: the CFG split (enable_cp) is not built; shard with enable_cp=False")
+    return dsp.ParallelManager(dp, cp, sp) if sp > 1 else None
 
 
 class VchitectAttention:
@@ -66,10 +111,91 @@ class VchitectAttention:
         self.last_spatial = self.last_cross = self.last_temporal = None
         self.last_decisions = (False, False, False)
         self._geometry = None
+        self._sp, self._sp_tag = None, ""
+        self.attn_route = None      # None: the measured default (_route); "rows" | "image" force one (as STDiT3's _switch)
 
-    def enable_parallel(self, dp_size=1, sp_size=1, enable_cp=False):
-        if (sp_size or 1) > 1:
-            raise NotImplementedError("Vchitect sequence parallelism (dynamic_switch, split_from_second_dim) is not built")
+    # Which temporal-attention route runs over all_to_all_single when nothing is forced: the image kernel, whose per-rank step (wire
+    # stubbed, 2B geometry) was 25.4 ms against 26.0 ms at 8 ranks and 40.0 against 40.7 ms at 4 (profiles/vchitect_sp_timing.json,
+    # DESIGN.md 3.3).  "rows" stays reachable through ``attn_route`` and is what the peer-to-peer exchange runs.
+    DEFAULT_A2A_ROUTE = "image"
+
+    def enable_parallel(self, dp_size=1, sp_size=1, enable_cp=False, parallel_mgr=None, copy_executor=None, sp=None, tag=""):
+        """The layer's side of VchitectXLTransformerModel.enable_parallel: ``sp`` is the model's dsp.SequenceParallel (one for all
+        blocks: they run one after the other and share its staging buffers), ``tag`` names this block's exchange sites.  Called on
+        its own it builds a SequenceParallel from the manager (or raises as the model does)."""
+        if sp is None:
+            mgr = _resolve_parallel(dp_size, sp_size, enable_cp, parallel_mgr)
+            if mgr is not None:
+                kw = {} if copy_executor is None else {"copy_executor": copy_executor}
+                sp = dsp.SequenceParallel(mgr.sp_group, **kw)
+            self.parallel_manager = mgr
+        self._sp, self._sp_tag = sp, tag
+        self._geometry = None
+
+    def _route(self):
+        """"rows" or "image" for this call.  The one-kernel peer-to-peer exchange writes straight into the peers' (b, t, s) tensors:
+        there is no receive image, so it always takes "rows"."""
+        if self._sp.p2p is not None:
+            return "rows"
+        r = self.attn_route or self.DEFAULT_A2A_ROUTE
+        if r not in ("rows", "image"):
+            raise ValueError(f"attn_route {r!r}: expected 'rows' or 'image'")
+        return r
+
+    def _zeroed(self, name, shape, F):
+        """A resident buffer of the SequenceParallel object that is zero when it is made (the send image of the way back: the image
+        kernel never writes the frames past F, which the peers receive as their padded frames).  One per F: another frame count
+        with the same image shape would leave its rows where this one's padding is."""
+        sp = self._sp
+        key = (name, tuple(shape), F)
+        if key not in sp._bufs:
+            sp._bufs[key] = torch.zeros(shape, dtype=torch.bfloat16, device=self.device)
+        return sp._bufs[key]
+
+    def _temporal_sharded(self, hs, enc, B, Fl, F, S, L, cos, sin):
+        """Temporal attention of a frame-sharded step: hs [B*Fl*S, C], enc [B*Fl*L, C] (normed, local frames) -> (tv [B*Fl*S, C],
+        tt [B*Fl*L, C]) rows of the local frames (zero rows for frames past F).  Two exchanges there, two back."""
+        sp, C, H = self._sp, self.C, self.H
+        P = sp.P
+        tag = self._sp_tag if sp.p2p is not None else ""   # a peer-to-peer site is one destination tensor: one site per block
+        Sl, Ll = -(-S // P), -(-L // P)
+        tv, tt = self._buf("temp_v", (B, Fl, S, C)), self._buf("temp_t", (B, Fl, L, C))
+        if self._route() == "rows":
+            xv = sp.to_spatial_shard(hs.view(B, Fl, S, C), F, Sl, out=self._buf("sp_xv", (B, F, Sl, C)), tag="v" + tag)
+            xt = sp.to_spatial_shard(enc.view(B, Fl, L, C), F, Ll, out=self._buf("sp_xt", (B, F, Ll, C)), tag="t" + tag)
+            nv, nt = B * F * Sl, B * F * Ll
+            qt = self._lin(xv.view(nv, C), "_qkv_temp", self._buf("qkv_temp", (nv, 3 * C)))
+            tq = self._lin(xt.view(nt, C), "_add_qkv", self._buf("tq_temp", (nt, 3 * C)))
+            ov, ot = self._buf("sp_ov", (nv, C)), self._buf("sp_ot", (nt, C))
+            vchitect_ops.attn_temporal64(qt[:, :C], qt[:, C:2 * C], qt[:, 2 * C:], tq[:, :C], tq[:, C:2 * C], tq[:, 2 * C:], cos, sin,
+                                         ov, ot, B, F, Sl, Ll, H)
+            sp.to_temporal_shard(ov.view(B, F, Sl, C), S, out=tv, tag="v" + tag)
+            sp.to_temporal_shard(ot.view(B, F, Ll, C), L, out=tt, tag="t" + tag)
+            return tv.view(B * Fl * S, C), tt.view(B * Fl * L, C)
+        # ---- "image": the GEMMs and the attention run on the receive image [P (source)][B][Fl][n][C] as it lies, the attention writes
+        # the send image of the way back; per tensor one pack there and one unpack back, nothing around the attention
+        pv, _, shape_v, _ = dsp.plan_switch_to_spatial_shard(B, Fl, F, S, Sl, C, P)
+        pt, _, shape_t, _ = dsp.plan_switch_to_spatial_shard(B, Fl, F, L, Ll, C, P)
+        _, uv, _, _ = dsp.plan_switch_to_temporal_shard(B, F, Sl, S, C, P)
+        _, ut, _, _ = dsp.plan_switch_to_temporal_shard(B, F, Ll, L, C, P)
+        send_v, recv_v = sp._buf("img_send_v", shape_v, hs), sp._buf("img_recv_v", shape_v, hs)
+        send_t, recv_t = sp._buf("img_send_t", shape_t, hs), sp._buf("img_recv_t", shape_t, hs)
+        sp.exec(hs, send_v, pv)
+        dsp.all_to_all_single(recv_v, send_v, sp.group)
+        sp.exec(enc, send_t, pt)
+        dsp.all_to_all_single(recv_t, send_t, sp.group)
+        nv, nt = P * B * Fl * Sl, P * B * Fl * Ll
+        qt = self._lin(recv_v.view(nv, C), "_qkv_temp", self._buf("qkv_temp", (nv, 3 * C)))
+        tq = self._lin(recv_t.view(nt, C), "_add_qkv", self._buf("tq_temp", (nt, 3 * C)))
+        back_v, back_t = self._zeroed("img_back_v", shape_v, F), self._zeroed("img_back_t", shape_t, F)
+        attend = vchitect_ops.attn_temporal64_img(qt[:, :C], qt[:, C:2 * C], qt[:, 2 * C:], tq[:, :C], tq[:, C:2 * C], tq[:, 2 * C:],
+                                                  cos, sin, back_v.view(nv, C), back_t.view(nt, C), B, F, Fl, Sl, Ll, H, defer=True)
+        # (no op code: the attention is issued by the host closure of the collective it feeds, so a replayed step gets no extra segment)
+        dsp.all_to_all_single(recv_v, back_v, sp.group, before=attend)
+        sp.exec(recv_v, tv, uv)
+        dsp.all_to_all_single(recv_t, back_t, sp.group)
+        sp.exec(recv_t, tt, ut)
+        return tv.view(B * Fl * S, C), tt.view(B * Fl * L, C)
 
     def expected_keys(self):
         names = [l for l in self.LINEARS if not (self.context_pre_only and l == "to_add_out")]
@@ -99,11 +225,15 @@ class VchitectAttention:
         return ops.gemm(x, self.w[name + ".weight"], self.w[name + ".bias"], out=out)
 
     @torch.no_grad()
-    def forward(self, hidden_states, encoder_hidden_states, batch: int, frames: int, timestep: int = None):
+    def forward(self, hidden_states, encoder_hidden_states, batch: int, frames: int, timestep: int = None, frames_global: int = None):
         """hidden_states bf16 [B*F*S, C] rows (b, f, s), encoder_hidden_states bf16 [B*F*L, C] rows (b, f, l) (the normed inputs of
         the block) -> (attn_output [B*F*S, C], context_attn_output [B*F*L, C]); resident buffers, valid until the next call.
-        ``timestep``: the Python int the sampler holds (PAB decisions; `int(timestep[0])` of the reference)."""
+        ``timestep``: the Python int the sampler holds (PAB decisions; `int(timestep[0])` of the reference).  Under sequence
+        parallelism ``frames`` is the local frame count Fl and ``frames_global`` the F the temporal attention runs over."""
         C, H, B, F = self.C, self.H, batch, frames
+        Fa = F if frames_global is None else frames_global
+        if self._sp is None and Fa != F:
+            raise ValueError("frames_global differs from frames, but the layer is not sharded (enable_parallel)")
         BF = B * F
         Nv, Nt = hidden_states.shape[0], encoder_hidden_states.shape[0]
         if Nv % BF or Nt % BF or hidden_states.shape[1] != C or encoder_hidden_states.shape[1] != C:
@@ -114,8 +244,8 @@ class VchitectAttention:
             raise ValueError(f"cross attention deals the {L} text keys of frame 0 out over {B} samples (attentions.py:781-786): "
                              f"L must be a multiple of the batch")
         Lk = L // B
-        if self._geometry != (B, F, S, L):     # the caches are views of the resident workspaces: another geometry invalidates them
-            self._geometry = (B, F, S, L)
+        if self._geometry != (B, F, S, L, Fa):     # the caches are views of the resident workspaces: another geometry invalidates them
+            self._geometry = (B, F, S, L, Fa)
             self.last_spatial = self.last_cross = self.last_temporal = None
         hs, enc = hidden_states, encoder_hidden_states
         use_pab = pab.enable_pab()
@@ -125,13 +255,16 @@ class VchitectAttention:
         if use_pab:
             bt, self.temporal_count = pab.if_broadcast_temporal(timestep, self.temporal_count)
         if not (bt and self.last_temporal is not None):
-            if F not in self._rope:
-                self._rope[F] = rope_tables(F, self.device, rope_scaling_factor=self.rope_scaling_factor)
-            cos, sin = self._rope[F]
-            qt = self._lin(hs, "_qkv_temp", self._buf("qkv_temp", (Nv, 3 * C)))
-            tv, tt = self._buf("temp_v", (Nv, C)), self._buf("temp_t", (Nt, C))
-            vchitect_ops.attn_temporal64(qt[:, :C], qt[:, C:2 * C], qt[:, 2 * C:], tq[:, :C], tq[:, C:2 * C], tq[:, 2 * C:], cos, sin,
-                                         tv, tt, B, F, S, L, H)
+            if Fa not in self._rope:
+                self._rope[Fa] = rope_tables(Fa, self.device, rope_scaling_factor=self.rope_scaling_factor)
+            cos, sin = self._rope[Fa]
+            if self._sp is not None:
+                tv, tt = self._temporal_sharded(hs, enc, B, F, Fa, S, L, cos, sin)
+            else:
+                qt = self._lin(hs, "_qkv_temp", self._buf("qkv_temp", (Nv, 3 * C)))
+                tv, tt = self._buf("temp_v", (Nv, C)), self._buf("temp_t", (Nt, C))
+                vchitect_ops.attn_temporal64(qt[:, :C], qt[:, C:2 * C], qt[:, 2 * C:], tq[:, :C], tq[:, C:2 * C], tq[:, 2 * C:], cos, sin,
+                                             tv, tt, B, F, S, L, H)
             self.last_temporal = (self._lin(tv, "to_out_temporal", self._buf("temp_vo", (Nv, C))), tt)
         tvo, tt = self.last_temporal
         # ---- cross attention (:860-878)
@@ -222,7 +355,7 @@ class JointTransformerBlock:
         self.attn.load_state_dict(sd, prefix + "attn.")
         return self
 
-    def forward(self, x, y, mod_v, mod_c, ms, batch, frames, buf, timestep=None):
+    def forward(self, x, y, mod_v, mod_c, ms, batch, frames, buf, timestep=None, frames_global=None):
         """x [B*F*S, C], y [B*F*L, C] updated in place (y untouched after a context_pre_only block: the reference returns None).
         mod_v / mod_c: row 0 of this block's modulation columns in the [B*F, ms] table (video: shift_msa, scale_msa, gate_msa,
         shift_mlp, scale_mlp, gate_mlp; context: the same six, or scale | shift of AdaLayerNormContinuous)."""
@@ -234,7 +367,7 @@ class JointTransformerBlock:
             yn = ops.ln_modulate(y, None, None, mod_c[C:2 * C], mod_c[0:C], L, mod_stride=ms, eps=1e-6, out=buf("yn", y.shape))
         else:
             yn = ops.ln_modulate(y, None, None, mod_c[0:C], mod_c[C:2 * C], L, mod_stride=ms, eps=1e-6, out=buf("yn", y.shape))
-        av, at = self.attn(xn, yn, batch, frames, timestep)
+        av, at = self.attn(xn, yn, batch, frames, timestep, frames_global)
         ops.gate_add_rows(x, av, mod_v[2 * C:3 * C], S, ms)
         xn = ops.ln_modulate(x, None, None, mod_v[3 * C:4 * C], mod_v[4 * C:5 * C], S, mod_stride=ms, eps=1e-6, out=buf("xn", x.shape))
         h = ops.gemm(xn, w["ff.net.0.proj.weight"], w["ff.net.0.proj.bias"], epilogue=ops.EPI_BIAS_GELU, out=buf("ff_h", (x.shape[0], 4 * C)))
@@ -257,7 +390,13 @@ class VchitectXLTransformerModel:
     (:548) pairs frame row i with sample i % B, and `norm_out(hidden_states, temb)` (:564) broadcasts only at B = 1.  Here :548 is kept
     literally for every B, and norm_out uses the temb of the sample a row belongs to (the only reading that exists for B > 1; the same
     thing at B = 1).  encoder_hidden_states may be [B, L, D] (every frame of a sample reads its prompt, what the broadcast of
-    norm1_context does at B = 1) or [B*F, L, D]."""
+    norm1_context does at B = 1) or [B*F, L, D].
+
+    Sequence parallelism (enable_parallel; module docstring).  A rank embeds its own frames straight from its slice of the latents
+    (and of a [B*F, L, D] encoder_hidden_states, which is split by frame), `cur_temb = temb.repeat(Fl, 1)` pairs local row i with
+    sample i % B, and the video AND text rows of a frame past F are zero rows written after the embedding (it cannot matter which:
+    a padded frame never reaches a real output row).  norm_out, proj_out and unpatchify run on the local frames and the fp32 prediction
+    is all-gathered — 256 bytes a token instead of 2 C — into the caller's ``out``, padding dropped."""
 
     def __init__(self, sample_size=128, patch_size=2, in_channels=16, num_layers=18, attention_head_dim=64, num_attention_heads=18,
                  joint_attention_dim=4096, caption_projection_dim=1152, pooled_projection_dim=2048, out_channels=16,
@@ -286,7 +425,7 @@ class VchitectXLTransformerModel:
         self._ws = Workspace(self.device, dtype)
         self._buf = self._ws.buf   # bound to this Workspace: _ws is cleared, never replaced (rebind _buf with it otherwise)
         self._pos_crop = {}
-        self.parallel_manager = None
+        self.parallel_manager, self._sp = None, None
         self.use_programs = True     # samplers record a step once and replay it (pipeline_vchitect.py); False: eager issue
         self.pos_embed = sincos_2d(C, pos_embed_max_size, sample_size // patch_size)      # [max * max, C] fp32 (PatchEmbed.pos_embed)
 
@@ -332,11 +471,30 @@ class VchitectXLTransformerModel:
         self.w["_proj_out.weight"], self.w["_proj_out.bias"] = dev(po), dev(pb)
         return self
 
-    def enable_parallel(self, dp_size=1, sp_size=1, enable_cp=False):
-        if enable_cp and (sp_size or 1) % 2 == 0:
-            sp_size = sp_size // 2
-        if (sp_size or 1) > 1:
-            raise NotImplementedError("Vchitect sequence parallelism (dynamic_switch, split_from_second_dim) is not built")
+    def enable_parallel(self, dp_size=1, sp_size=1, enable_cp=False, parallel_mgr=None, copy_executor=None):
+        """vchitect_transformer_3d.py:326-338.  ``parallel_mgr``: an injected manager (sp_size, sp_group, ...; the group a
+        torch.distributed ProcessGroup or an object of dsp's group protocol); without one the mesh dp x cp x sp must be the size of the
+        process group initialised in this process, else a NotImplementedError (no group of that size here).  The CFG split (enable_cp
+        with more than one rank) is not built."""
+        mgr = _resolve_parallel(dp_size, sp_size, enable_cp, parallel_mgr)
+        self.parallel_manager = mgr
+        if mgr is None:
+            self._sp = None
+        else:
+            kw = {} if copy_executor is None else {"copy_executor": copy_executor}
+            self._sp = dsp.SequenceParallel(mgr.sp_group, **kw)
+        for i, b in enumerate(self.transformer_blocks):
+            b.attn.parallel_manager = mgr
+            b.attn.enable_parallel(sp=self._sp, tag=str(i))
+
+    def _local_frames(self, F):
+        """(first frame, frames held, real frames among them) of this rank: Fl = ceil(F / P), rank r holds [r Fl, (r + 1) Fl)."""
+        sp = self._sp
+        if sp is None:
+            return 0, F, F
+        Fl = -(-F // sp.P)
+        f0 = sp.rank * Fl
+        return f0, Fl, max(0, min(Fl, F - f0))
 
     def reset_pab_state(self):
         for b in self.transformer_blocks:
@@ -375,39 +533,78 @@ class VchitectXLTransformerModel:
         elif enc.shape[0] != BF:
             raise ValueError("encoder_hidden_states must hold B or B * F samples")
         L = enc.shape[-2]
-        enc = enc.reshape(BF * L, -1).contiguous()
-        # ---- temb = time_text_embed(timestep, pooled) (:540), computed for the B*F rows of cur_temb = temb.repeat(F, 1) (:548)
+        enc = enc.reshape(B, F, L, enc.shape[-1])          # (a view: [B * F, L, D] as it lies, or the expanded [B, L, D])
+        sp = self._sp
+        f0, Fl, nreal = self._local_frames(F)       # single rank: (0, F, F)
+        BFl = B * Fl
+        # ---- temb = time_text_embed(timestep, pooled) (:540), computed for the B*Fl rows of cur_temb = temb.repeat(Fl, 1) (:548)
         ts = torch.as_tensor(timestep).detach().to("cpu").float().reshape(-1)
         timestep_int = int(ts[0])
         if ts.numel() != B:
             ts = ts.expand(B) if ts.numel() == 1 else ts[:B]
         pooled = pooled_projections.to(device=dev, dtype=self.dtype).reshape(B, -1)
-        tsb = self.step_timesteps(BF)
+        tsb = self.step_timesteps(BF)            # (the sampler writes B * F rows whatever the shard: the first B * Fl are read)
         tsb.copy_(ts.repeat(F))
+        tsb = tsb[:BFl]
         tp = ops.timestep_embedding(tsb, 256)
         te = "time_text_embed.timestep_embedder."
         e1 = ops.linear_small(tp, w[te + "linear_1.weight"], w[te + "linear_1.bias"], act_out=ops.ACT_SILU)
         temb = ops.linear_small(e1, w[te + "linear_2.weight"], w[te + "linear_2.bias"])
         tx = "time_text_embed.text_embedder."
-        p1 = ops.linear_small(pooled.repeat(F, 1).contiguous(), w[tx + "linear_1.weight"], w[tx + "linear_1.bias"], act_out=ops.ACT_SILU)
-        ops.add_rows(temb, ops.linear_small(p1, w[tx + "linear_2.weight"], w[tx + "linear_2.bias"]))     # [B*F, C]; rows 0 .. B-1 = temb
-        mod = ops.linear_small(temb, w["_mod.weight"], w["_mod.bias"], act_in=ops.ACT_SILU)           # [B*F, sum of the blocks' columns]
+        p1 = ops.linear_small(pooled.repeat(Fl, 1).contiguous(), w[tx + "linear_1.weight"], w[tx + "linear_1.bias"], act_out=ops.ACT_SILU)
+        ops.add_rows(temb, ops.linear_small(p1, w[tx + "linear_2.weight"], w[tx + "linear_2.bias"]))     # [B*Fl, C]; rows 0 .. B-1 = temb
+        mod = ops.linear_small(temb, w["_mod.weight"], w["_mod.bias"], act_in=ops.ACT_SILU)           # [B*Fl, sum of the blocks' columns]
         ms = mod.shape[1]
         mod_out = ops.linear_small(temb[:B], w["norm_out.linear.weight"], w["norm_out.linear.bias"], act_in=ops.ACT_SILU)   # [B, 2C]: scale | shift
         # ---- patch embed + cropped position table (:483-487), context_embedder (:541)
-        cols = ops.im2col_patch(hidden_states.to(device=dev, dtype=torch.float32).contiguous(), B, p)
-        x = ops.gemm(cols, w["pos_embed.proj.weight"], w["pos_embed.proj.bias"], out=self._buf("x", (BF * S, C)))
-        ops.add_bcast_rows(x, self.cropped_pos_embed(Hp, Wp), 1, S)
-        y = ops.gemm(enc, w["context_embedder.weight"], w["context_embedder.bias"], out=self._buf("y", (BF * L, C)))
+        z = hidden_states.to(device=dev, dtype=torch.float32)
+        x, y = self._buf("x", (BFl * S, C)), self._buf("y", (BFl * L, C))
+        if sp is None:
+            enc = enc.reshape(BF * L, -1).contiguous()
+            cols = ops.im2col_patch(z.contiguous(), B, p)
+            ops.gemm(cols, w["pos_embed.proj.weight"], w["pos_embed.proj.bias"], out=x)
+            ops.add_bcast_rows(x, self.cropped_pos_embed(Hp, Wp), 1, S)
+            ops.gemm(enc, w["context_embedder.weight"], w["context_embedder.bias"], out=y)
+        else:
+            # this rank's frames of every sample, straight from its slice of the latents and of the text (a view when B = 1: nothing
+            # is copied); the rows of the frames past F are zero (set_pad("temporal", F) + split_from_second_dim, :543-546)
+            for b in range(B if nreal else 0):
+                xb, yb = x[b * Fl * S:(b * Fl + nreal) * S], y[b * Fl * L:(b * Fl + nreal) * L]
+                cols = ops.im2col_patch(z[b:b + 1, f0:f0 + nreal].contiguous(), 1, p)
+                ops.gemm(cols, w["pos_embed.proj.weight"], w["pos_embed.proj.bias"], out=xb)
+                ops.add_bcast_rows(xb, self.cropped_pos_embed(Hp, Wp), 1, S)
+                ops.gemm(enc[b, f0:f0 + nreal].reshape(nreal * L, -1).contiguous(), w["context_embedder.weight"],
+                         w["context_embedder.bias"], out=yb)
+            if nreal < Fl:
+                npad = Fl - nreal
+                for t, n in ((x, S), (y, L)):       # (a copy of nothing: vsys_copy_4d zero-fills outside n1_valid = 0)
+                    ops.copy_4d(t, t[nreal * n:], B, npad * n, 1, C, (0, 0, 0), (Fl * n * C, C, 0), n1_valid=0)
         use_pab = pab.enable_pab()
         for i, blk in enumerate(self.transformer_blocks):
             v0, c0 = self._mod_off[i]
-            blk.forward(x, y, mod[0, v0:], mod[0, c0:], ms, B, F, self._buf, timestep_int if use_pab else None)
+            blk.forward(x, y, mod[0, v0:], mod[0, c0:], ms, B, Fl, self._buf, timestep_int if use_pab else None, F)
         # ---- norm_out (AdaLayerNormContinuous: scale | shift), proj_out, unpatchify (:564-581)
-        xo = ops.ln_modulate(x, None, None, mod_out[0, C:2 * C], mod_out[0, 0:C], F * S, mod_stride=2 * C, eps=1e-6,
-                             out=self._buf("xn", (BF * S, C)))
-        po = ops.gemm(xo, w["_proj_out.weight"], w["_proj_out.bias"], out=self._buf("proj", (BF * S, 192)))
-        out = ops.unpatchify_cvx(po, B, F, Hp, Wp, self.out_channels, p, out=out).view(BF, self.out_channels, Hh, Ww)
+        xo = ops.ln_modulate(x, None, None, mod_out[0, C:2 * C], mod_out[0, 0:C], Fl * S, mod_stride=2 * C, eps=1e-6,
+                             out=self._buf("xn", (BFl * S, C)))
+        po = ops.gemm(xo, w["_proj_out.weight"], w["_proj_out.bias"], out=self._buf("proj", (BFl * S, 192)))
+        if sp is None:
+            out = ops.unpatchify_cvx(po, B, F, Hp, Wp, self.out_channels, p, out=out).view(BF, self.out_channels, Hh, Ww)
+        else:
+            # gather_from_second_dim (:561-562) moved behind the row-wise tail: the fp32 prediction of the local frames travels
+            n = self.out_channels * Hh * Ww
+            if out is None:
+                out = torch.empty(BF * n, dtype=torch.float32, device=dev)
+            assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == BF * n
+            loc = ops.unpatchify_cvx(po, B, Fl, Hp, Wp, self.out_channels, p, out=self._buf("pred_local", (BFl * n,), torch.float32))
+            parts = self._buf("pred_parts", (sp.P * BFl * n,), torch.float32)
+            dst, P = out.view(B, F, n), sp.P
+
+            def drop_padding():     # rows (rank, b, f) -> (b, f), frames past F dropped: one strided copy (a view at B = 1)
+                dst.copy_(parts.view(P, B, Fl, n).permute(1, 0, 2, 3).reshape(B, P * Fl, n)[:, :F])
+
+            dsp.all_gather_into_tensor(parts, loc, sp.group, after=drop_padding)
+            program.keep(out)
+            out = out.view(BF, self.out_channels, Hh, Ww)
         if not return_dict:
             return (out,)
         return SimpleNamespace(sample=out)

@@ -1,5 +1,5 @@
 """Tensor-level wrappers of the entry points that exist for Vchitect-2.0 (include/videosys_amd.h: vsys_attn_temporal_d64,
-vsys_scale_add_rows of the transformer; vsys_vae_first_im2col_nc, vsys_pixels_to_u8 of the SD3 VAE decode), on the launch route of
+vsys_attn_temporal_d64_img, vsys_scale_add_rows of the transformer; vsys_vae_first_im2col_nc, vsys_pixels_to_u8 of the SD3 VAE decode), on the launch route of
 videosys_amd.ops (torch.ops.vsys.launch / ctypes, recorded by program.py; the two decode kernels have no op code and go through
 ctypes).  HIP device tensors only, no eager fallback.  Guard-band tests: tests/test_gpu_isolation_vchitect.py,
 tests/test_gpu_isolation_vchitect_pipeline.py."""
@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import torch
 
+from . import _lib, program
 from .ops import VaeGrid, _bf16, _call, _chk, _p
 
 
@@ -29,6 +30,44 @@ def attn_temporal64(q_vid, k_vid, v_vid, q_txt, k_txt, v_txt, rope_cos, rope_sin
     _call("vsys_attn_temporal_d64", _p(q_vid), ld(q_vid), _p(k_vid), ld(k_vid), _p(v_vid), ld(v_vid), _p(q_txt), ld(q_txt), _p(k_txt),
           ld(k_txt), _p(v_txt), ld(v_txt), _p(rope_cos), _p(rope_sin), _p(out_vid), ld(out_vid), _p(out_txt), ld(out_txt), B, T, S, L,
           heads)
+    return out_vid, out_txt
+
+
+def attn_temporal64_img(q_vid, k_vid, v_vid, q_txt, k_txt, v_txt, rope_cos, rope_sin, out_vid, out_txt, B, T, Tl, S, L, heads,
+                        defer=False):
+    """attn_temporal64 on the receive image of the frame -> token switch (vsys_attn_temporal_d64_img): *_vid [nslab * B * Tl * S, >=
+    heads*64] rows ordered (slab, b, t % Tl, s) with nslab >= ceil(T / Tl) (an image has one slab per rank, also for the ranks that
+    hold only padded frames), *_txt likewise with L; frames past T are neither read nor written, and out_* is the image the return
+    collective sends.  Same bits as attn_temporal64 on the un-imaged rows.
+    The entry point has no op code (the op table is pinned): the launch goes through ctypes on torch's current stream, and code
+    under a launch-program recorder issues it from a ``program.host_call`` closure (the collective's), never bare: ``defer=True`` checks
+    the arguments now and returns the closure that launches."""
+    ts = (q_vid, k_vid, v_vid, q_txt, k_txt, v_txt, out_vid, out_txt)
+    _chk(*ts, rope_cos, rope_sin)
+    _bf16(*ts)
+    nslab = -(-T // Tl)
+    for t, n in zip(ts, (S, S, S, L, L, L, S, L)):
+        if n > 0:
+            assert t is not None and t.dim() == 2 and t.stride(1) == 1 and t.shape[1] >= heads * 64
+            assert t.shape[0] >= nslab * B * Tl * n and t.shape[0] % (B * Tl * n) == 0
+    if rope_cos is not None:
+        assert rope_cos.dtype == torch.float32 and rope_cos.is_contiguous() and rope_cos.shape == (T, 32)
+        assert rope_sin.dtype == torch.float32 and rope_sin.is_contiguous() and rope_sin.shape == (T, 32)
+    ld = lambda t: 0 if t is None else t.stride(0)
+    dp = lambda t: None if t is None else t.data_ptr()
+    program.keep(ts), program.keep((rope_cos, rope_sin))
+    args = (dp(q_vid), ld(q_vid), dp(k_vid), ld(k_vid), dp(v_vid), ld(v_vid), dp(q_txt), ld(q_txt), dp(k_txt), ld(k_txt), dp(v_txt),
+            ld(v_txt), dp(rope_cos), dp(rope_sin), dp(out_vid), ld(out_vid), dp(out_txt), ld(out_txt), B, T, Tl, B * Tl * S, B * Tl * L, S, L,
+            heads)
+    fn = _lib.load().vsys_attn_temporal_d64_img
+
+    def issue():
+        _lib.check(fn(*args, torch.cuda.current_stream().cuda_stream), "vsys_attn_temporal_d64_img")
+
+    if defer:
+        return issue
+    assert program.active() is None, "vsys_attn_temporal_d64_img has no op code: under a recorder issue it from a host_call closure (defer=True)"
+    issue()
     return out_vid, out_txt
 
 
