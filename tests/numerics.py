@@ -197,3 +197,183 @@ def rms_q_chain(q, w, eps=1e-6):
     n = q * torch.rsqrt((q * q).mean(dim=-1, keepdim=True) + eps)
     qh = n * w
     return qh, (rnd(n) + acc(q.shape[-1], n.abs())) * w.abs() + rnd(qh)
+
+
+# ------------------------------------------------------------------------------------------------ VAE family
+# conv_kernel (csrc/conv_bf16.hip: tap-shifted conv and the plain 128-column GEMM), the GroupNorm / SpatialNorm / softmax / first-layer
+# kernels of csrc/vae_ops.hip.  Grids are ops.VaeGrid objects (plain Python: no device needed); tensors are float64 on the CPU.
+SILU_SLOPE = 1.1   # the largest slope of x / (1 + exp(-x)) is 1.0998 (at x = 2.3994)
+
+
+def grid_view(rows: torch.Tensor, g, C=None) -> torch.Tensor:
+    """The rows of grid ``g`` [g.rows, >= C] as [n, T + tf, Hp, Wp, C] (front frames and borders included; slack rows left out)."""
+    C = rows.shape[1] if C is None else C
+    return rows.reshape(g.n, g.sample_rows, -1)[:, :(g.T + g.tf) * g.plane].reshape(g.n, g.T + g.tf, g.Hp, g.Wp, -1)[..., :C]
+
+
+def grid_interior(rows: torch.Tensor, g, C=None) -> torch.Tensor:
+    """[n, T, H, W, C]: the voxels of grid ``g`` (what every VAE kernel is compared on)."""
+    return grid_view(rows, g, C)[:, g.tf:, g.pad:g.pad + g.H, g.pad:g.pad + g.W]
+
+
+def conv_gather(a_rows: torch.Tensor, g, cin: int, kt: int, ks: int) -> torch.Tensor:
+    """The im2col matrix of a causal (kt, ks, ks) convolution over the padded grid ``g``, [n T H W, kt ks ks cin] float64, column =
+    ((a ks + b) ks + c) cin + channel: for every tap the [n, T, H, W, cin] window of the 5-D grid view that starts at frame a (the tf =
+    kt - 1 front frames are the causal padding) and at pixel (b, c) of the bordered plane (ks = 3 on a pad = 1 grid; ks = 1 reads the
+    voxel itself on any grid).  Stated on voxel coordinates: no flat row arithmetic, unlike the kernel's row shifts."""
+    assert g.tf == kt - 1 and (ks == 1 or (ks == 3 and g.pad == 1))
+    x = grid_view(a_rows.double(), g, cin)
+    taps = []
+    for a in range(kt):
+        for b in range(ks):
+            for c in range(ks):
+                h0, w0 = (b, c) if ks == 3 else (g.pad, g.pad)
+                taps.append(x[:, a:a + g.T, h0:h0 + g.H, w0:w0 + g.W])
+    return torch.cat(taps, dim=-1).reshape(g.n * g.T * g.H * g.W, kt * ks * ks * cin)
+
+
+def linear_ref(a, w, bias=None, res=None, out_scale=None):
+    """conv_kernel's contract on an explicit A [M, K] (the rows themselves for gemm128, ``conv_gather`` for a conv), w [N, K]:
+      bf16 out   p = sum_k a_k w_k + b in fp32, s = sum_k |a_k w_k| + |b|:  out = bf16(p), bound acc(K + 1, s) + rnd(p);  with a residual
+                 the kernel computes bf16(res + bf16(p)): reference res + p, one more term rnd(res + p);
+      fp32 out   (``out_scale`` given; no bias, no residual) out = out_scale p: bound out_scale acc(K + 2, s) — no bf16 term, which is
+                 the point of the form (attention scores, split-K partials).
+    Returns (ref, bound), float64 [M, N]."""
+    K = a.shape[1]
+    p, s = matmul_ref(a, w)
+    if out_scale is not None:
+        assert bias is None and res is None
+        return out_scale * p, abs(out_scale) * acc(K + 2, s)
+    if bias is not None:
+        p, s = p + bias.double(), s + bias.double().abs()
+    bound = acc(K + 1, s) + rnd(p)
+    if res is not None:
+        p = p + res.double()
+        bound = bound + rnd(p)
+    return p, bound
+
+
+class NormRef:
+    """``ref`` / ``bound`` [n, T, H, W, C]; ``cancel`` = the part of ``bound`` that comes from the error of rstd (the cancellation of
+    var = E[x^2] - mu^2, carried to the output); ``n_t`` / ``lanes`` = the launch geometry the statistics term was derived from."""
+
+    def __init__(self, ref, bound, cancel, n_t, lanes):
+        self.ref, self.bound, self.cancel, self.n_t, self.lanes = ref, bound, cancel, n_t, lanes
+
+    def cancel_share(self) -> float:
+        """The largest share of an element's bound that the rstd (cancellation) term takes."""
+        return float((self.cancel / (self.bound + FLOOR)).max())
+
+
+def _silu64(x):
+    return x / (1.0 + torch.exp(-x))
+
+
+def group_norm_ref(x, groups, gamma, beta, eps, nblk, silu=False, yb=None) -> NormRef:
+    """GroupNorm (+ SiLU, or + SpatialNorm + SiLU) of x [n, T, H, W, C] float64 with its per-element bound.
+
+    Contract (vae_ops.hip):  y = [silu](bf16((x - mu) rstd gamma + beta)), statistics per (sample, group) over (T, H, W) and the group's
+    channels.  ``yb`` = (Y, B) [n, T, H, W, C] (the SpatialNorm maps ALREADY gathered at every voxel): y = silu(bf16(bf16(nf Y) + B)),
+    nf = bf16(GroupNorm(x)).
+
+    Statistics, from the launch geometry (gn_partial_kernel: ``nblk`` blocks per sample, lanes = 256 // (C / 8) position lanes per
+    block): a thread adds n_t = ceil(P / (nblk lanes)) positions of 4 channels in fp32, ``lanes`` such sums are added in fp32, the rest is
+    double (gn_finalize_kernel); x^2 of a bf16 x is exact in fp32.  With Ka = 4 n_t + lanes additions:
+      e_mu   = acc(Ka, E|x|) + 2^-24 |mu|          (the sum; the fp32 store of the mean)
+      r_q    = Ka 2^-24                            (relative, on E[x^2]: every term is >= 0)
+      d_var  = r_q E[x^2] + 2 |mu| e_mu + e_mu^2   (var = E[x^2] - mu^2 as the kernel forms it)
+      r_rstd = d / (2 (1 - d)) + 2^-24, d = d_var / (var + eps): holds the cancellation factor E[x^2] / (var + eps)
+    Output: t = (x - mu) rstd gamma, pre = t + beta:
+      e_pre  = |rstd gamma| e_mu + |t| r_rstd + 3 2^-24 (|t| + |beta|)     (the fp32 subtract / multiplies / add)
+      plain  bound = e_pre + rnd(pre)
+      SiLU   bound = SILU_SLOPE (e_pre + rnd(pre)) + rnd(y) + (U_EXP + U_RCP) |y|    (fast exp, fast reciprocal)
+      SpatialNorm   E1 = e_pre + rnd(pre);  E2 = |Y| E1 + rnd(pre Y);  E3 = E2 + rnd(pre Y + B);  then SiLU of q = pre Y + B as above."""
+    n, T, H, W, C = x.shape
+    cg = C // groups
+    P = T * H * W
+    lanes = 256 // (C // 8)
+    n_t = -(-P // (nblk * lanes))
+    Ka = 4 * n_t + lanes
+    xg = x.reshape(n, P, groups, cg)
+    mu = xg.mean(dim=(1, 3), keepdim=True)
+    ex2 = (xg * xg).mean(dim=(1, 3), keepdim=True)
+    eabs = xg.abs().mean(dim=(1, 3), keepdim=True)
+    var = (ex2 - mu * mu).clamp_min(0.0)
+    rstd = torch.rsqrt(var + eps)
+    e_mu = acc(Ka, eabs) + U_F32 * mu.abs()
+    d = (Ka * U_F32 * ex2 + 2 * mu.abs() * e_mu + e_mu * e_mu) / (var + eps)
+    assert float(d.max()) < 1.0, "the statistics bound has broken down (d_var >= var + eps)"
+    r_rstd = d / (2 * (1 - d)) + U_F32
+    ga, be = gamma.double().reshape(groups, cg), beta.double().reshape(groups, cg)
+    t = (xg - mu) * rstd * ga
+    pre = t + be
+    cancel = t.abs() * r_rstd
+    e_pre = (rstd * ga).abs() * e_mu + cancel + 3 * U_F32 * (t.abs() + be.abs())
+    shape = (n, T, H, W, C)
+    pre, e_pre, cancel = pre.reshape(shape), e_pre.reshape(shape), cancel.reshape(shape)
+    err, carried = e_pre + rnd(pre), cancel
+    if yb is not None:
+        Y, B = yb[0].double(), yb[1].double()
+        err = Y.abs() * err + rnd(pre * Y)
+        carried = Y.abs() * carried
+        pre = pre * Y + B
+        err = err + rnd(pre)
+        silu = True
+    if not silu:
+        return NormRef(pre, err, carried, n_t, lanes)
+    y = _silu64(pre)
+    return NormRef(y, SILU_SLOPE * err + rnd(y) + (U_EXP + U_RCP) * y.abs(), SILU_SLOPE * carried, n_t, lanes)
+
+
+def spatial_norm_maps(yb_rows, n, C, zdims, size):
+    """[Y | B] rows over the latent grid ([n zT zH zW, 2C]) -> (Y, B) [n, T, H, W, C] at the voxels of ``size`` = (T, H, W), indexed the
+    way the reference model does it (CogVideoXSpatialNorm3D): F.interpolate nearest, the first frame on its own when T is odd and > 1."""
+    import torch.nn.functional as F
+
+    zT, zH, zW = zdims
+    T, H, W = size
+    z = yb_rows.double().reshape(n, zT, zH, zW, 2 * C).permute(0, 4, 1, 2, 3)
+    if T > 1 and T % 2 == 1:
+        zi = torch.cat([F.interpolate(z[:, :, :1], size=(1, H, W)), F.interpolate(z[:, :, 1:], size=(T - 1, H, W))], dim=2)
+    else:
+        zi = F.interpolate(z, size=(T, H, W))
+    zi = zi.permute(0, 2, 3, 4, 1)
+    return zi[..., :C], zi[..., C:]
+
+
+def softmax_rows_ref(s: torch.Tensor, n: int):
+    """softmax_rows_kernel: p_j = bf16(exp(s_j - m) / l) over the first n of ld columns of fp32 scores s [rows, ld].  Relative bound
+    2^-8 + 2 U_EXP + U_RCP + acc(n, 1) + |s_j - m| 2^-23: the bf16 store, the fast exp of the element and of the sum's terms, the
+    reciprocal of the sum, the fp32 sum of n terms, and the fp32 subtraction + the scaling of the exponent's argument (2^-24 of
+    |s_j - m| each).  Returns (ref, bound) [rows, n] float64; columns n .. ld - 1 must be exactly zero and are the caller's to check."""
+    x = s.double()[:, :n]
+    dlt = x - x.amax(dim=1, keepdim=True)
+    e = torch.exp(dlt)
+    p = e / e.sum(dim=1, keepdim=True)
+    rel = U_BF16 + 2 * U_EXP + U_RCP + acc(n, 1.0) + dlt.abs() * 2.0**-23
+    return p, rel * p
+
+
+def first_im2col_ref(z, kt, kcols, params):
+    """first_im2col_kernel: z [4, F, H, W] (bf16 values) -> rows [F H W, kcols]; v = bf16(z scale + shift) per channel,
+    u = bf16(pq_w v + pq_b) in fp32, column (tap, channel) of a causal (kt, 3, 3) im2col, exact zeros outside the volume and in columns
+    >= 36 kt.  Bound: rnd(v) carried through |pq_w|, + acc(4, sum |pq_w v| + |pq_b|), + rnd(u).  ``params`` are the 28 numbers the
+    kernel receives as fp32.  Returns (ref, bound, nonzero mask) [F H W, kcols]; where the mask is False the output must be exactly 0."""
+    import torch.nn.functional as F
+
+    prm = torch.tensor([float(v) for v in params], dtype=torch.float32).double()
+    scale, shift, pw, pb = prm[0:4], prm[4:8], prm[8:24].reshape(4, 4), prm[24:28]
+    _, Fr, H, W = z.shape
+    v = z.double() * scale[:, None, None, None] + shift[:, None, None, None]
+    u = torch.einsum("oc,cfhw->ofhw", pw, v) + pb[:, None, None, None]
+    uabs = torch.einsum("oc,cfhw->ofhw", pw.abs(), v.abs()) + pb.abs()[:, None, None, None]
+    bound = torch.einsum("oc,cfhw->ofhw", pw.abs(), rnd(v)) + acc(4, uabs) + rnd(u)
+    inside = torch.ones_like(u)
+
+    def cols(x):
+        xp = F.pad(x, (1, 1, 1, 1, kt - 1, 0))
+        c = [xp[:, a:a + Fr, b:b + H, d:d + W] for a in range(kt) for b in range(3) for d in range(3)]
+        m = torch.stack(c, 0).permute(2, 3, 4, 0, 1).reshape(Fr * H * W, kt * 36)
+        return torch.cat([m, torch.zeros(Fr * H * W, kcols - kt * 36, dtype=m.dtype)], dim=1)
+
+    return cols(u), cols(bound), cols(inside) > 0

@@ -1,11 +1,16 @@
 """The element-wise bound of tests/numerics.py on synthetic data (no GPU): a correctly rounded result and a result with one
 rounding fewer than the contract pass; each of four planted GEMM defects fails, and the failure names the tile.  Second half: the
-softmax-attention bound (numerics.attention_ref) against a CPU emulation of the d72 flash contract and its planted defects."""
+softmax-attention bound (numerics.attention_ref) against a CPU emulation of the d72 flash contract and its planted defects.  Third part:
+the VAE family's bounds (conv / gemm128, GroupNorm, SpatialNorm, softmax_rows, first layer) against the restatements of
+tests/vae_cpu_emul.py and their planted defects, and the refusal of ops.conv for temporal taps over more than one sample."""
 import pytest
 import torch
+import torch.nn.functional as F
 
 import attn_families as fam
 import numerics as nm
+import vae_cpu_emul as emu
+import vae_numerics_cases as vc
 
 M, N, K = 1024, 384, 1024
 
@@ -248,3 +253,176 @@ def test_attention_bound_fp32_denominator_form():
     out_bad = (w.float() @ v.float().roll(1, 0)).to(torch.bfloat16)
     with pytest.raises(AssertionError, match="outside the bound"):
         nm.check_elementwise(out_bad, ref.out, ref.bound, "fp32-denominator emulation, v shifted by one key")
+
+
+# ------------------------------------------------------------------------------------------------ VAE family
+# The bounds of numerics.linear_ref / group_norm_ref / softmax_rows_ref / first_im2col_ref on the cases of tests/vae_numerics_cases.py:
+# the restatements of tests/vae_cpu_emul.py (fp32 arithmetic, bf16 storage: the kernels' contract) pass, every planted defect fails.
+NBLK = 128     # ops._GN_NBLK (asserted below)
+
+
+def _fails(out, ref, bound):
+    return nm.Bound("defect").add(out, ref, bound).bad > 0
+
+
+def test_gn_nblk_is_the_wrappers():
+    from videosys_amd import ops
+
+    assert ops._GN_NBLK == NBLK
+
+
+@pytest.mark.parametrize("kt,ks,pad", [(1, 3, 1), (3, 3, 1), (3, 1, 0), (3, 1, 1)])
+def test_conv_gather_reference_is_conv3d_in_float64(kt, ks, pad):
+    """numerics.conv_gather + one float64 matmul = F.conv3d in float64 over the zero-padded volume (two samples: the gather works on
+    voxel coordinates, so it has no trouble with n > 1)."""
+    from videosys_amd.ops import VaeGrid
+
+    n, T, H, W, cin, cout = 2, 3, 4, 5, 32, 8
+    gen = torch.Generator().manual_seed(kt * 10 + ks + pad)
+    x5 = torch.randn(n, T, H, W, cin, generator=gen).to(torch.bfloat16)
+    w = torch.randn(cout, kt, ks, ks, cin, generator=gen).to(torch.bfloat16)
+    g = VaeGrid(n, T, H, W, pad, kt - 1)
+    rows = vc.grid_rows(vc.storage(x5, g, border=0.0), g)
+    got = nm.conv_gather(rows, g, cin, kt, ks) @ w.double().reshape(cout, -1).t()
+    sp = ks // 2
+    want = F.conv3d(F.pad(x5.double().permute(0, 4, 1, 2, 3), (sp, sp, sp, sp, kt - 1, 0)), w.double().permute(0, 4, 1, 2, 3))
+    # (two float64 sums of the same exact products in different orders)
+    assert (got.reshape(n, T, H, W, cout) - want.permute(0, 2, 3, 4, 1)).abs().max().item() <= 1e-12
+
+
+@pytest.fixture(scope="module")
+def conv_cases():
+    return {name: vc.conv_case(name) for name in vc.CONV_CASES}
+
+
+def _interior_rows(out_rows, c):
+    return nm.grid_interior(out_rows, c["og"], c["cout"]).reshape(-1, c["cout"])
+
+
+def test_conv_restatements_pass_on_every_case(conv_cases):
+    for name, c in conv_cases.items():
+        a, res = vc.grid_rows(c["a_buf"], c["g"]), vc.conv_res_rows(c)
+        out = emu.conv(a, c["g"], c["w"], c["b"], c["cin"], c["kt"], c["ks"], res=res)
+        nm.Bound(f"conv (conv3d restatement) {name}").add(_interior_rows(out, c), c["ref"], c["bound"]).check()
+        if c["g"].n == 1:
+            out = emu.conv_taps(a, c["g"], c["w"], c["b"], c["cin"], c["kt"], c["ks"], res=res)
+            nm.Bound(f"conv (row-shift restatement) {name}").add(_interior_rows(out, c), c["ref"], c["bound"]).check()
+
+
+@pytest.mark.parametrize("defect,names", [("bf16_partials", ("27taps_M312", "cshift2_108tiles", "time_only_pad0", "M35_9tiles")),
+                                          ("ktile_left", ("27taps_M312", "cshift2_108tiles", "time_only_pad1", "xcd_27tiles")),
+                                          ("res_next_row", ("27taps_M312", "time_only_pad0"))])
+def test_conv_planted_defect_fails(conv_cases, defect, names):
+    for name in names:
+        c = conv_cases[name]
+        out = emu.conv_taps(vc.grid_rows(c["a_buf"], c["g"]), c["g"], c["w"], c["b"], c["cin"], c["kt"], c["ks"], res=vc.conv_res_rows(c), defect=defect)
+        assert _fails(_interior_rows(out, c), c["ref"], c["bound"]), f"{defect} passes on {name}"
+
+
+def test_gemm128_restatement_passes_and_fp32_form_has_no_bf16_term():
+    for K in vc.GEMM_K:
+        for M in (1, 257):
+            a, w, b, r = vc.gemm_operands(M, 128, K, K + M)
+            for bias, res in ((None, None), (b, None), (None, r), (b, r)):
+                ref, bound = nm.linear_ref(a, w, bias, res)
+                nm.check_elementwise(emu.gemm128(a, w, bias, res), ref, bound, f"gemm128 K={K} M={M}")
+    a, w, _, _ = vc.gemm_operands(200, 256, 64, 3)
+    ref, bound = nm.linear_ref(a, w, out_scale=0.125)
+    s32 = (a.float() @ w.float().t()) * 0.125
+    nm.check_elementwise(s32, ref, bound, "fp32 score form")
+    with pytest.raises(AssertionError, match="outside the bound"):       # scores rounded to bf16 on the way: what the form exists to avoid
+        nm.check_elementwise(s32.to(torch.bfloat16), ref, bound, "fp32 score form through bf16")
+
+
+@pytest.fixture(scope="module")
+def gn_cases():
+    return {name: vc.gn_case(name, NBLK, small=True) for name in vc.GN_CASES}
+
+
+def _gn_emulated(c, defect=None):
+    mean, rstd = emu.gn_stats_geometry(c["x5"], c["groups"], vc.GN_EPS, NBLK, defect=defect)
+    return emu.gn_apply_chunks(c["x5"], mean, rstd, c["groups"], c["gamma"], c["beta"], c["silu"], defect=defect)
+
+
+def test_group_norm_restatements_pass_on_every_case(gn_cases):
+    for name, c in gn_cases.items():
+        r = c["r"]
+        nm.Bound(f"group norm (kernel-order restatement) {name}").add(_gn_emulated(c), r.ref.reshape(-1, c["C"]), r.bound.reshape(-1, c["C"])).check()
+        # ... and through the wrapper-shaped restatement (torch's own fp32 group_norm), destination grid included
+        y = c["y_buf"].clone()
+        emu.group_norm(vc.grid_rows(c["x_buf"], c["gs"]), c["gs"], vc.grid_rows(y, c["gd"]), c["gd"], c["C"], c["gamma"], c["beta"], vc.GN_EPS,
+                       c["silu"], groups=c["groups"])
+        nm.Bound(f"group norm (torch restatement) {name}").add(nm.grid_interior(vc.grid_rows(y, c["gd"]), c["gd"]).reshape(-1, c["C"]),
+                                                                r.ref.reshape(-1, c["C"]), r.bound.reshape(-1, c["C"])).check()
+        assert vc.outside_interior_unchanged(y, c["y_buf"], c["gd"], c["C"])
+    off = gn_cases["offset_mean8"]["r"]
+    print(f"offset case: the rstd (cancellation) term takes up to {off.cancel_share():.3f} of an element's bound at n_t = {off.n_t}")
+    assert off.n_t == 8 and 0.0 < off.cancel_share() < 1.0
+
+
+@pytest.mark.parametrize("defect,names", [("upper_half_stats", ("two_samples_cg4", "cg12_idle", "cg12_silu_pad")), ("sample0_stats", ("two_samples_cg4",)),
+                                          ("q_bf16", ("8_per_thread", "offset_mean8", "65552_rows"))])
+def test_group_norm_planted_defect_fails(gn_cases, defect, names):
+    for name in names:
+        c = gn_cases[name]
+        assert _fails(_gn_emulated(c, defect), c["r"].ref.reshape(-1, c["C"]), c["r"].bound.reshape(-1, c["C"])), f"{defect} passes on {name}"
+
+
+def test_spatial_norm_restatement_passes_and_the_next_latent_voxel_fails():
+    for T, zT, C in vc.SN_CASES:
+        c = vc.sn_case(T, zT, C, NBLK)
+        mean, rstd = emu.gn_stats_geometry(c["x5"], c["groups"], vc.GN_EPS, NBLK)
+        ref, bound = c["r"].ref.reshape(-1, C), c["r"].bound.reshape(-1, C)
+        maps = emu.spatial_norm_gather(c["yb"], c["n"], C, c["zdims"], c["x5"].shape[1:4])
+        out = emu.gn_apply_chunks(c["x5"], mean, rstd, c["groups"], c["gamma"], c["beta"], True, yb=maps)
+        nm.Bound(f"spatial norm restatement T={T} zT={zT} C={C}").add(out, ref, bound).check()
+        bad = emu.spatial_norm_gather(c["yb"], c["n"], C, c["zdims"], c["x5"].shape[1:4], defect="zw_plus_1")
+        out = emu.gn_apply_chunks(c["x5"], mean, rstd, c["groups"], c["gamma"], c["beta"], True, yb=bad)
+        assert _fails(out, ref, bound), f"latent voxel zw + 1 passes at T={T} zT={zT} C={C}"
+        out = emu.gn_apply_chunks(c["x5"], mean, rstd, c["groups"], c["gamma"], c["beta"], True, yb=maps, defect="sample0_stats")
+        assert _fails(out, ref, bound)
+
+
+@pytest.mark.parametrize("case", vc.SOFTMAX_CASES, ids=lambda c: f"{c[0]}x{c[1]}of{c[2]}")
+def test_softmax_rows_restatement_passes_and_defects_fail(case):
+    rows, n, ld, kinds = vc.SOFTMAX_CPU_SCALE.get(case, case)
+    s = vc.softmax_scores(rows, n, ld, kinds)
+    vc.check_softmax(emu.softmax_rows(s, n), s, n, f"softmax restatement {rows} x {n} of {ld}")
+    if n > 1024:
+        with pytest.raises(AssertionError, match="outside the bound"):
+            vc.check_softmax(emu.softmax_rows(s, n, defect="sum_first_1024"), s, n, "columns >= 1024 left out of the sum")
+    if ld > n:
+        s2 = s.clone()
+        s2[:, n:] = s2[:, :1]         # (finite scores behind n, so that the un-zeroed columns hold ordinary probabilities)
+        with pytest.raises(AssertionError, match="not exactly zero"):
+            vc.check_softmax(emu.softmax_rows(s2, n, defect="pad_not_zeroed"), s2, n, "padded columns not zeroed")
+
+
+@pytest.mark.parametrize("kt,kcols", [(3, 128), (1, 64)])
+def test_first_layer_restatement_passes_and_a_shifted_tap_fails(kt, kcols):
+    z, params, ref, bound, mask = vc.first_case(kt, kcols)
+    out = emu.vae_first_im2col(z, kt, kcols, params)
+    vc.check_first(out, ref, bound, mask, f"first layer kt={kt}")
+    bad = out.clone()
+    bad[:, 0:4] = out[:, 4:8]         # tap 0 holding tap 1's pixels
+    with pytest.raises(AssertionError):
+        vc.check_first(bad, ref, bound, mask, "first layer, tap shifted")
+
+
+def test_conv_refuses_temporal_taps_on_more_than_one_sample():
+    """ops.conv shifts FLAT rows: with n > 1 the output grid (T plane rows per sample) and the input grid ((T + tf) plane rows per sample)
+    drift apart from the second sample on.  The wrapper refuses before it looks at a tensor (so: no device needed, nothing launched)."""
+    from videosys_amd import ops
+
+    g = ops.VaeGrid(2, 3, 4, 4, 1, 2)
+    a = torch.zeros(g.rows, 32, dtype=torch.bfloat16)
+    w = torch.zeros(128, 32 * 27, dtype=torch.bfloat16)
+    with pytest.raises(ValueError, match="wrong sample"):
+        ops.conv(a, g, w, None, 32, 3, 3)
+    with pytest.raises(ValueError, match="wrong sample"):                    # temporal-only taps all the same
+        ops.conv(torch.zeros(ops.VaeGrid(3, 2, 4, 4, 0, 2).rows, 32, dtype=torch.bfloat16), ops.VaeGrid(3, 2, 4, 4, 0, 2), w[:, :96], None, 32, 3, 1)
+    g1 = ops.VaeGrid(2, 1, 4, 4, 1, 0, sample_rows=40)                        # slack rows per sample: the same drift without temporal taps
+    with pytest.raises(ValueError, match="wrong sample"):
+        ops.conv(torch.zeros(g1.rows, 32, dtype=torch.bfloat16), g1, w[:, :288], None, 32, 1, 3)
+    with pytest.raises(ops._lib.VsysError, match="no CPU fallback"):          # what is allowed reaches the device check (still no launch)
+        ops.conv(torch.zeros(ops.VaeGrid(2, 1, 4, 4, 1, 0).rows, 32, dtype=torch.bfloat16), ops.VaeGrid(2, 1, 4, 4, 1, 0), w[:, :288], None, 32, 1, 3)

@@ -701,7 +701,14 @@ def conv(a, grid: VaeGrid, w, bias, cin, kt, ks, out=None, res=None):
 
     ``a`` MUST be the row view returned by ``grid.alloc`` (or a buffer laid out the same way): a 3 x 3 kernel reads up to
     grid.guard = W + 3 rows before the first and after the last row of the view, and the border pixels / front frames of the
-    grid must be zero — that is where the convolution's zero padding comes from."""
+    grid must be zero — that is where the convolution's zero padding comes from.
+
+    Temporal taps need ``grid.n == 1``: the kernel shifts FLAT rows, and the output grid has T * plane rows per sample where the
+    input grid has (T + tf) * plane, so from the second sample on a row shift would land in the frames of another sample."""
+    if grid.n > 1 and (kt > 1 or grid.sample_rows != grid.conv_out().sample_rows):
+        raise ValueError(f"conv: n = {grid.n} samples with kt = {kt}, {grid.sample_rows} input rows per sample: the output grid has "
+                         f"{grid.conv_out().sample_rows} rows per sample, so the flat row shift of a tap would read the frames of the "
+                         f"wrong sample from sample 1 on; run temporal convs (and grids with slack rows) one sample per launch")
     _chk(a, w, bias, res, out)
     _bf16(a, w, bias, res, out)
     assert grid.tf == kt - 1 and (ks == 1 or grid.pad == 1) and a.shape[0] == grid.rows and a.stride(1) == 1
