@@ -16,20 +16,189 @@ from oracle import stdit3_oracle as O
 
 
 def test_library_exports_every_declared_symbol():
+    """Every prototype of the two public headers, parsed HERE (not by the generator that writes the table), against the ctypes table:
+    same names, same argument types element for element, same return type."""
+    import ctypes
+
     import __graft_entry__ as ge
 
     ge.build()
     from videosys_amd import _lib
 
     lib = _lib.load()
-    hdr = open(os.path.join(ROOT, "include", "videosys_amd.h")).read()
-    declared = set(re.findall(r"\b(vsys_[a-z0-9_]+)\s*\(", hdr))
+
+    def prototypes(header):
+        text, out = open(os.path.join(ROOT, "include", header)).read(), {}
+        for ret, name, args in re.findall(r"^(int|const char\*) (vsys_\w+)\(([^;]*?)\);", text, flags=re.S | re.M):
+            params = [a.strip() for a in re.sub(r"\s+", " ", args).split(",")]
+            types = []
+            for prm in ([] if params == ["void"] else params):
+                ty = prm.rsplit(" ", 1)[0]
+                types.append(ctypes.c_void_p if ty.endswith("*") else {"float": ctypes.c_float, "int64_t": ctypes.c_int64, "int": ctypes.c_int}[ty])
+            out[name] = (types, ctypes.c_int if ret == "int" else ctypes.c_char_p)
+        return text, out
+
+    hdr, declared = prototypes("videosys_amd.h")
     assert len(declared) >= 16
-    for name in declared:
+    assert set(declared) == set(re.findall(r"\b(vsys_[a-z0-9_]+)\s*\(", hdr)), "a declaration the prototype pattern does not read"
+    assert set(declared) == set(_lib.SIGNATURES), "ctypes table out of sync with the header"
+    for name, (types, ret) in declared.items():
         assert hasattr(lib, name), f"{name} declared in include/videosys_amd.h but not exported"
-    assert declared - {"vsys_strerror"} == set(_lib.SIGNATURES), "ctypes table out of sync with the header"
+        sig = _lib.SIGNATURES[name]
+        assert len(sig) == len(types) and all(a is b for a, b in zip(sig, types)), f"{name}: bound as {sig}, declared as {types}"
+        fn = getattr(lib, name)
+        assert list(fn.argtypes) == types and fn.restype is ret, name
+    assert [n for n, (_, ret) in declared.items() if ret is not ctypes.c_int] == ["vsys_strerror"]
+    _, lab = prototypes("videosys_amd_lab.h")
+    assert set(lab) == set(_lib.LAB_SIGNATURES) == {"vsys_lab_flash_debug_buffer", "vsys_gemm_streamk_plan"}
+    for name, (types, ret) in lab.items():
+        sig = _lib.LAB_SIGNATURES[name]
+        assert len(sig) == len(types) and all(a is b for a, b in zip(sig, types)) and _lib.RESTYPES[name] is ret, name
+        assert not hasattr(lib, name), f"{name}: a lab entry point in the shipped library"
     assert lib.vsys_abi_version() == 1
     assert lib.vsys_strerror(-1) == b"unsupported shape"
+
+
+def test_c_abi_wrappers_reject_bad_arguments_before_any_launch():
+    """The entry points whose wrappers share a file-local helper in csrc/capi.hip (GEMM head, flash d72 / d64, copy descriptors) and
+    vsys_conv_bf16: a null operand, a count past int, batch * heads > 65535, a negative key-norm bound and a bad descriptor are answered
+    with the same code as ever and in the same order of checks, with no launch (there is no device here; the pointers are never read)."""
+    import ctypes
+
+    import __graft_entry__ as ge
+
+    ge.build()
+    from videosys_amd import _lib
+
+    lib = _lib.load()
+    SHAPE, ARG = -1, -3
+    P, BIG = 0x10000, 1 << 31
+
+    # flash d72: the trio shares its checks (the bound is the _kb variant's extra argument)
+    def d72(name, q=P, kp=P, vt=P, out=P, batch=2, heads=16, q_len=1024, kv_len=300, kv_pad=320, extra=()):
+        return getattr(lib, name)(q, 1152, None, kp, vt, out, 1152, batch, heads, q_len, kv_len, kv_pad, 1e-6, *extra, None)
+
+    for name, extra in (("vsys_flash_attn_d72", ()), ("vsys_flash_attn_d72_exact", ()), ("vsys_flash_attn_d72_kb", (4.0,))):
+        for op in ("q", "kp", "vt", "out"):
+            assert d72(name, extra=extra, **{op: None}) == ARG, (name, op)
+        for n in ("batch", "heads", "q_len", "kv_len", "kv_pad"):
+            assert d72(name, extra=extra, **{n: BIG}) == SHAPE, (name, n)
+            assert d72(name, extra=extra, **{n: -1}) == SHAPE, (name, n)
+        assert d72(name, extra=extra, batch=4096, heads=16) == SHAPE          # batch * heads = 65536
+        assert d72(name, extra=extra, q=None, batch=BIG) == ARG               # the operands are looked at first
+    assert d72("vsys_flash_attn_d72_kb", extra=(-0.5,)) == ARG
+    assert d72("vsys_flash_attn_d72_kb", extra=(float("nan"),)) == ARG
+    assert d72("vsys_flash_attn_d72_kb", extra=(-0.5,), batch=BIG) == ARG
+
+    # flash d64: the pair
+    def d64(name, q=P, ln_w=None, ln_b=None, kp=P, vt=P, out=P, rope_start=0, rope_len=0, batch=2, heads=16, q_len=512, kv_len=512,
+            kv_pad=512, extra=()):
+        return getattr(lib, name)(q, 1024, ln_w, ln_b, None, None, rope_start, rope_len, kp, vt, out, 1024, batch, heads, q_len, kv_len,
+                                  kv_pad, 1e-6, *extra, None)
+
+    for name, extra in (("vsys_flash_attn_d64", ()), ("vsys_flash_attn_d64_kb", (4.0,))):
+        for op in ("q", "kp", "vt", "out"):
+            assert d64(name, extra=extra, **{op: None}) == ARG, (name, op)
+        assert d64(name, extra=extra, ln_w=P) == ARG and d64(name, extra=extra, ln_b=P) == ARG      # LayerNorm weight without bias
+        for n in ("batch", "heads", "q_len", "kv_len", "kv_pad", "rope_start", "rope_len"):
+            assert d64(name, extra=extra, **{n: BIG}) == SHAPE, (name, n)
+            assert d64(name, extra=extra, **{n: -1}) == SHAPE, (name, n)
+        assert d64(name, extra=extra, ln_w=P, batch=BIG) == ARG
+    assert d64("vsys_flash_attn_d64_kb", extra=(-1.0,)) == ARG and d64("vsys_flash_attn_d64_kb", extra=(float("nan"),)) == ARG
+
+    # GEMM entry points: (x, ldx, w, ldw, bias, out, ldo, M, N, K) head, then each one's own operands
+    def gemm(x=P, w=P, out=P, M=256, N=1152, K=1152, epi=0, gate=None, res=None, aux=None, rps=0):
+        return lib.vsys_gemm_bf16(x, K, w, K, None, out, N, M, N, K, epi, gate, 0, rps, res, N, aux, N, None)
+
+    assert gemm(x=None) == ARG and gemm(w=None) == ARG and gemm(out=None) == ARG
+    assert gemm(M=BIG) == SHAPE and gemm(N=BIG) == SHAPE and gemm(K=BIG) == SHAPE and gemm(rps=BIG) == SHAPE and gemm(M=-1) == SHAPE
+    assert gemm(epi=0, gate=P) == ARG and gemm(epi=1, res=P) == ARG and gemm(epi=0, aux=P) == ARG    # only EPI_GATE_RES takes them
+    assert gemm(x=None, M=BIG) == ARG and gemm(M=BIG, gate=P) == SHAPE
+
+    def gemm_ln(x=P, wp=P, cs=P, cv=P, out=P, stats=P, M=256, N=3456, K=1152, epi=0):
+        return lib.vsys_gemm_bf16_ln(x, K, wp, K, cs, cv, out, N, M, N, K, epi, stats, M, 1e-6, None)
+
+    for op in ("x", "wp", "cs", "cv", "out", "stats"):
+        assert gemm_ln(**{op: None}) == ARG, op
+    assert gemm_ln(M=BIG) == SHAPE and gemm_ln(N=BIG) == SHAPE and gemm_ln(K=BIG) == SHAPE
+    assert gemm_ln(epi=2) == ARG
+    assert gemm_ln(K=1000) == SHAPE and gemm_ln(K=96 * 13) == SHAPE          # whole 96-column partials, at most 12 of them
+
+    def qkv_kv(x=P, stats=P, knw=P, q=P, kp=P, vt=P, M=1024, K=1152, S=256, heads=16):
+        return lib.vsys_gemm_bf16_ln_qkv_kv(x, K, P, K, P, P, stats, M, knw, q, 1152, kp, vt, M, K, S, heads, 1e-6, 1e-6, None)
+
+    for op in ("x", "stats", "knw", "q", "kp", "vt"):
+        assert qkv_kv(**{op: None}) == ARG, op
+    assert qkv_kv(M=BIG) == SHAPE and qkv_kv(K=BIG) == SHAPE and qkv_kv(S=BIG) == SHAPE
+    assert qkv_kv(heads=0) == SHAPE and qkv_kv(heads=4097) == SHAPE and qkv_kv(K=1000) == SHAPE
+
+    def gemm_stats(x=P, out=P, stats=P, M=256, rps=0):
+        return lib.vsys_gemm_bf16_stats(x, 1152, P, 1152, None, out, 1152, M, 1152, 1152, None, 0, rps, None, 1152, stats, M, None)
+
+    assert gemm_stats(x=None) == ARG and gemm_stats(out=None) == ARG and gemm_stats(stats=None) == ARG
+    assert gemm_stats(M=BIG) == SHAPE and gemm_stats(rps=BIG) == SHAPE
+
+    def gate_res_add(x=P, out=P, res=P, M=256, rps=0):
+        return lib.vsys_gemm_bf16_gate_res_add(x, 1152, P, 1152, None, out, 1152, M, 1152, 1152, None, 0, rps, res, 1152, None, None, None, None, 0,
+                                               None)
+
+    assert gate_res_add(x=None) == ARG and gate_res_add(out=None) == ARG and gate_res_add(res=None) == ARG
+    assert gate_res_add(M=BIG) == SHAPE and gate_res_add(rps=BIG) == SHAPE
+
+    def gate2(x=P, out=P, gate=P, M=256, rps=128, split=16):
+        return lib.vsys_gemm_bf16_gate2(x, 1152, P, 1152, None, out, 1152, M, 1152, 1152, gate, 0, rps, split, 1152, None, 1152, None, 1152, None)
+
+    assert gate2(x=None) == ARG and gate2(out=None) == ARG and gate2(gate=None) == ARG
+    assert gate2(M=BIG) == SHAPE and gate2(rps=BIG) == SHAPE and gate2(split=BIG) == SHAPE
+    assert gate2(split=-1) == SHAPE and gate2(split=129) == SHAPE              # the text rows are a prefix of the sample
+
+    def skinny(w=P, x=P, part=P, rows=4, rows_padded=16, N=4096, K=4096, nsplit=4):
+        return lib.vsys_gemm_skinny_slices(w, K, x, K, part, rows, rows_padded, N, K, nsplit, None)
+
+    assert skinny(w=None) == ARG and skinny(x=None) == ARG and skinny(part=None) == ARG
+    assert skinny(rows_padded=BIG) == SHAPE and skinny(N=BIG) == SHAPE and skinny(K=BIG) == SHAPE and skinny(nsplit=BIG) == SHAPE
+    assert skinny(nsplit=0) == SHAPE and skinny(K=4100) == SHAPE and skinny(rows=0) == SHAPE and skinny(rows=17) == SHAPE
+    assert skinny(K=64, nsplit=3) == SHAPE                                     # the last slice would be empty
+
+    # copy descriptors: 14 words per problem (vsys_copy_4d_batch), 17 (vsys_p2p_exchange)
+    def desc(words=14, n=1, **over):
+        base = dict(src_off=0, dst_off=0, n0=2, n1=3, n2=4, C=64, ss0=768, ss1=256, ss2=64, ds0=768, ds1=256, ds2=64, n1_valid=3, n2_valid=4,
+                    dst=P, flag=P, remote=0)
+        base.update(over)
+        return (ctypes.c_int64 * (words * n))(*(list(base.values())[:words] * n))
+
+    batch = lambda src=P, dst=P, nops=1, d=None: lib.vsys_copy_4d_batch(src, dst, nops, desc() if d is None else d, None)
+    assert batch(src=None) == ARG and batch(dst=None) == ARG and lib.vsys_copy_4d_batch(P, P, 1, None, None) == ARG
+    assert batch(nops=-1) == SHAPE and batch(nops=17, d=desc(n=17)) == SHAPE
+    for k in ("n0", "n1", "n2", "C", "n1_valid", "n2_valid"):
+        assert batch(d=desc(**{k: BIG})) == SHAPE and batch(d=desc(**{k: -1})) == SHAPE, k
+    assert batch(d=desc(src_off=-8)) == SHAPE and batch(d=desc(dst_off=-8)) == SHAPE
+
+    def p2p(src=P, nops=1, d=None, my_flags=P, n_flags=2, self_index=0, state=P):
+        return lib.vsys_p2p_exchange(src, nops, desc(17) if d is None else d, my_flags, n_flags, self_index, state, 1000, None)
+
+    assert p2p(src=None) == ARG and p2p(my_flags=None) == ARG and p2p(state=None) == ARG
+    assert lib.vsys_p2p_exchange(P, 1, None, P, 2, 0, P, 1000, None) == ARG
+    assert p2p(nops=-1) == SHAPE and p2p(nops=17, d=desc(17, n=17)) == SHAPE and p2p(n_flags=BIG) == SHAPE
+    assert p2p(self_index=-1) == SHAPE and p2p(self_index=2) == SHAPE
+    for k in ("n0", "n1", "n2", "C", "n1_valid", "n2_valid"):
+        assert p2p(d=desc(17, **{k: BIG})) == SHAPE, k
+    assert p2p(d=desc(17, src_off=-8)) == SHAPE and p2p(d=desc(17, dst_off=-8)) == SHAPE
+    assert p2p(d=desc(17, dst=0)) == SHAPE                                     # a problem without a destination
+
+    # vsys_conv_bf16
+    def conv(a=P, w=P, bias=None, res=None, out=P, out32=None, M=4096, N=128, cin=128, kt=3, kh=3, kw=3, row_pitch=66, plane_pitch=4356, batch=1):
+        return lib.vsys_conv_bf16(a, cin, w, cin * kt * kh * kw, bias, res, N, out, out32, N, M, N, cin, kt, kh, kw, row_pitch, plane_pitch, batch,
+                                  0, 0, 0, 1.0, None)
+
+    assert conv(a=None) == ARG and conv(w=None) == ARG
+    assert conv(out=None) == ARG and conv(out32=P) == ARG                      # exactly one of the two outputs
+    assert conv(out=None, out32=P, bias=P) == ARG and conv(out=None, out32=P, res=P) == ARG
+    for n in ("M", "N", "cin", "row_pitch", "plane_pitch", "batch"):
+        assert conv(**{n: BIG}) == SHAPE, n
+    assert conv(kt=0) == SHAPE and conv(kt=4) == SHAPE and conv(kh=2) == SHAPE and conv(kh=4, kw=4) == SHAPE and conv(cin=0) == SHAPE
+    assert conv(cin=1 << 27) == SHAPE                                          # 27 taps: K past int
+    assert conv(plane_pitch=(1 << 31) - 1) == SHAPE                            # the farthest tap's row offset past int
 
 
 def test_no_cpu_fallback():

@@ -62,21 +62,22 @@ constexpr int LN_BLOCK = 96;   // columns per LayerNorm partial (= the column wi
 enum { ACT_NONE = VSYS_ACT_NONE, ACT_SILU = VSYS_ACT_SILU, ACT_GELU_TANH = VSYS_ACT_GELU_TANH };
 
 struct GemmParams {
-  const bf16_t* A; int64_t lda;   // activations [M, K]
-  const bf16_t* W; int64_t ldw;   // nn.Linear weight [N, K]
-  const bf16_t* bias;             // [N] or null
-  bf16_t* out; int64_t ldo;       // [M, N]
-  int M, N, K;
-  const bf16_t* gate; int64_t gate_stride;  // per-sample gate row [N] at gate + sample*gate_stride, or null (gate = 1)
-  const bf16_t* res; int64_t ldr;           // residual [M, N] or null
-  bf16_t* aux; int64_t ldaux;               // optional copy of gate*(acc+bias) (PAB cache slab) or null
-  int rows_per_sample;
+  // (every member has a default: `GemmParams p;` is fully defined, an entry point sets only what it uses)
+  const bf16_t* A = nullptr; int64_t lda = 0;   // activations [M, K]
+  const bf16_t* W = nullptr; int64_t ldw = 0;   // nn.Linear weight [N, K]
+  const bf16_t* bias = nullptr;                 // [N] or null
+  bf16_t* out = nullptr; int64_t ldo = 0;       // [M, N]
+  int M = 0, N = 0, K = 0;
+  const bf16_t* gate = nullptr; int64_t gate_stride = 0;  // per-sample gate row [N] at gate + sample*gate_stride, or null (gate = 1)
+  const bf16_t* res = nullptr; int64_t ldr = 0;           // residual [M, N] or null
+  bf16_t* aux = nullptr; int64_t ldaux = 0;               // optional copy of gate*(acc+bias) (PAB cache slab) or null
+  int rows_per_sample = 0;
   // CogVideoX joint [text | video] rows: rows whose position inside the sample is < seg_split take their gate vector
   // gate_alt elements further on (enc_gate vs gate of CogVideoXLayerNormZero); 0 = one gate per sample
-  int seg_split; int64_t gate_alt;
+  int seg_split = 0; int64_t gate_alt = 0;
   // EPI_F32_SLICES only (launch_gemm2_slices): K slice length, fp32 output [slices][N][M] (element (m, n) of slice s at
   // out32[s * slab + n * ldo32 + m]: "A" is the weight here, so this is activation-row-major)
-  int ks; float* out32; int64_t slab, ldo32;
+  int ks = 0; float* out32 = nullptr; int64_t slab = 0, ldo32 = 0;
   // AdaLN fold.  Row statistics travel as per-96-column partials (mean_b, M2_b) at stats[b * ld + row], b = column / 96:
   //   EPI_GATE_RES_STATS writes them for x_new = res + gate (acc + bias) (what it stores to out);
   //   EPI_LN_BIAS / EPI_LN_GELU combine the ln_nb partials of a row into (mu, rstd) and compute
@@ -115,15 +116,15 @@ __host__ __device__ inline int qkv_kv_column(int n, int heads) {
 
 // implicit-GEMM convolution / 128-column GEMM (conv_bf16.hip).  A points at the row that tap (0,0,0) reads for output row 0.
 struct ConvParams {
-  const bf16_t* A; int64_t lda;   // activation rows [*, cin]
-  const bf16_t* W; int64_t ldw;   // [N, taps*cin], k = tap*cin + channel
-  const bf16_t* bias;             // [N] or null
-  const bf16_t* res; int64_t ldr; // residual rows [M, N] added after rounding, or null
-  bf16_t* out; float* out32; int64_t ldo;  // exactly one of out / out32
-  int M, N, K;
-  int cin, taps, cshift, taps_hw, kw, row_pitch, plane_pitch, max_tap_rows;
-  int batch; int64_t batch_a, batch_w, batch_o;  // gridDim.y operand strides in elements
-  float out_scale;                // fp32 output only
+  const bf16_t* A = nullptr; int64_t lda = 0;   // activation rows [*, cin]
+  const bf16_t* W = nullptr; int64_t ldw = 0;   // [N, taps*cin], k = tap*cin + channel
+  const bf16_t* bias = nullptr;                 // [N] or null
+  const bf16_t* res = nullptr; int64_t ldr = 0; // residual rows [M, N] added after rounding, or null
+  bf16_t* out = nullptr; float* out32 = nullptr; int64_t ldo = 0;  // exactly one of out / out32
+  int M = 0, N = 0, K = 0;
+  int cin = 0, taps = 0, cshift = 0, taps_hw = 0, kw = 0, row_pitch = 0, plane_pitch = 0, max_tap_rows = 0;
+  int batch = 0; int64_t batch_a = 0, batch_w = 0, batch_o = 0;  // gridDim.y operand strides in elements
+  float out_scale = 0.f;                        // fp32 output only
 };
 int launch_conv(const ConvParams& p, hipStream_t stream);
 

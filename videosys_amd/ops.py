@@ -42,8 +42,6 @@ def _call(name: str, *args):
     launch-program recorder (program.py) the launch is also logged for replay.  Route: ``torch.ops.vsys.launch`` (the TORCH_LIBRARY
     fragment of csrc/torch_binding.cpp: tensors travel as tensors) for every entry point that has a VSYS_OP code — the whole denoise
     step — and ctypes for the rest (VAE, T5) or when the fragment is not there."""
-    import ctypes
-
     s = torch.cuda.current_stream()
     rec = program.active()
     sig = _lib.SIGNATURES[name][:-1]
@@ -54,17 +52,7 @@ def _call(name: str, *args):
     if op is None:
         _lib.check(getattr(_lib.load(), name)(*args, s.cuda_stream), name)
         return
-    tensors, ints, floats = [], [], []
-    for v, t in zip(args, sig):
-        if t is _lib._f32:
-            floats.append(float(v))
-            continue
-        if isinstance(v, _TPtr):
-            tensors.append(v.t)
-            ints.append(0)
-        else:
-            tensors.append(None)
-            ints.append(ctypes.addressof(v) if isinstance(v, ctypes.Array) else (0 if v is None else int(v)))
+    tensors, ints, floats = _lib.split_args(args, sig)   # (a tensor's slot also carries its address; the dispatcher takes the tensor's)
     try:
         tv.launch(op, tensors, ints, floats, s.cuda_stream)
     except RuntimeError as e:

@@ -100,15 +100,7 @@ class Recorder:
         if h not in self.streams:
             self.streams.append(h)
             self.side_objs[h] = stream_obj
-        ints, floats = [], []
-        for v, t in zip(args, argtypes):
-            if t is _f32:
-                floats.append(float(v))
-            elif isinstance(v, ctypes.Array):      # a host array the launch reads (copy descriptors): address + keep-alive
-                self.keep.append(v)
-                ints.append(ctypes.addressof(v))
-            else:
-                ints.append(0 if v is None else int(v))
+        _, ints, floats = _lib.split_args(args, argtypes, self.keep)   # (a host array the launch reads is kept alive)
         if len(ints) > N_INT or len(floats) > N_FLOAT:
             self.invalid = self.invalid or f"{name}: too many arguments for a vsys_cmd"
             return
