@@ -18,6 +18,10 @@ __device__ __forceinline__ bf16_t f2bf(float f) { return __builtin_bit_cast(bf16
 __device__ __forceinline__ uint32_t pack2bf(float lo, float hi) {
   return (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
 }
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+// the same two roundings from a register pair: ONE v_cvt_pk_bf16_f32, no separate halves to OR together
+__device__ __forceinline__ uint32_t pack2bf(f32x2 v) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2)); }
 __device__ __forceinline__ float bflo(uint32_t u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float bfhi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
 
@@ -136,6 +140,12 @@ struct LnAcc {
   float p, s1, s2;
   __device__ __forceinline__ void init(float pivot) { p = pivot; s1 = 0.f; s2 = 0.f; }
   __device__ __forceinline__ void add(float x) { const float d = x - p; s1 += d; s2 = fmaf(d, d, s2); }
+  // two values in turn, the differences taken on a register pair (v_pk_add_f32): the same operations in the same order as add(x.x); add(x.y)
+  __device__ __forceinline__ void add2(f32x2 x) {
+    const f32x2 d = x - f32x2{p, p};
+    s1 += d.x; s2 = fmaf(d.x, d.x, s2);
+    s1 += d.y; s2 = fmaf(d.y, d.y, s2);
+  }
   __device__ __forceinline__ float2 finish(float n) const { return make_float2(p + s1 / n, fmaxf(s2 - s1 * s1 / n, 0.f)); }
 };
 // two equal-sized (n each) partials -> one

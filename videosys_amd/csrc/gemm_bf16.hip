@@ -719,10 +719,10 @@ __global__ __launch_bounds__(Geo<BM_>::NT + PROD * 256, PROD ? 3 : 2) void gemm_
   // serialise 12 HBM round trips per wave (CDNA4 vmcnt also counts the stores).
   constexpr bool GATED = EPI == EPI_GATE_RES || EPI == EPI_GATE_RES_STATS;
   constexpr bool LN = EPI == EPI_LN_BIAS || EPI == EPI_LN_GELU;
-  if constexpr (!RES_EARLY) fetch_res();
+  if constexpr (!RES_EARLY && !(MF && GATED)) fetch_res();   // (the 16x16x32 gated epilogues fetch through a descriptor, below)
   char* st = smem + wave * OUT_WAVE_BYTES;
   const int ncol0 = col0 + wn * 96;
-  if constexpr (EPI == EPI_GATE_RES_STATS) {
+  if constexpr (EPI == EPI_GATE_RES_STATS && !MF) {
     // The residual rows go INTO the wave's image first (coalesced 16-byte units), so that the accumulator pass below sees
     // x_new = res + gate (acc + bias) in the layout where a lane owns one token row: it rounds x_new as the store phase of the
     // plain epilogue does, takes the LayerNorm partial of its 48 columns on the way, and the store phase becomes a copy.
@@ -750,7 +750,11 @@ __global__ __launch_bounds__(Geo<BM_>::NT + PROD * 256, PROD ? 3 : 2) void gemm_
         for (int g = 0; g < 4; ++g) {
           const uint2 o = *reinterpret_cast<const uint2*>(st + m_local * OUT_ROW_BYTES + (j * 32 + 8 * g + 4 * hi) * 2);
           if (j == 0 && g == 0) lacc.init(bflo(o.x));
-          lacc.add(bflo(o.x)); lacc.add(bfhi(o.x)); lacc.add(bflo(o.y)); lacc.add(bfhi(o.y));
+          if constexpr (MF) {
+            lacc.add2(f32x2{bflo(o.x), bfhi(o.x)}); lacc.add2(f32x2{bflo(o.y), bfhi(o.y)});
+          } else {
+            lacc.add(bflo(o.x)); lacc.add(bfhi(o.x)); lacc.add(bflo(o.y)); lacc.add(bfhi(o.y));
+          }
         }
       const float2 mine = lacc.finish(48.f);
       const float2 other = make_float2(__shfl_xor(mine.x, 32, 64), __shfl_xor(mine.y, 32, 64));
@@ -759,6 +763,205 @@ __global__ __launch_bounds__(Geo<BM_>::NT + PROD * 256, PROD ? 3 : 2) void gemm_
       if (hi == 0 && grow < p.M) p.stats_out[(int64_t)(ncol0 / LN_BLOCK) * p.stats_ld + grow] = blk;
     }
   };
+  if constexpr (MF && GATED) {
+    // ---- the gate + residual epilogues on 16x16x32, written for INSTRUCTION COUNT (DESIGN 3.1 "What the gate + residual epilogue
+    // costs"): the values, the rounding points and the summation order of the 32x32x16 forms further down, which stay the bit reference.
+    //  * addresses: 16-byte unit ``it`` of the wave's 64 x 96 image is (row, chunk) = ((lane + 64 it) / 12, (lane + 64 it) % 12) and
+    //    192 = 16 x 12, so unit 3 a + b is unit b sixteen rows further down — three divisions per lane, not twelve per operand; every
+    //    operand is ONE wave-uniform descriptor (from the wave's first row to the end of its last EXISTING row: rows past M read 0 and
+    //    are not written, so there is no ragged-tile form) plus a 32-bit per-lane offset shared by the operands of one leading dimension;
+    //  * bias add, gate multiply and residual add run on register pairs (v_pk_add_f32 / v_pk_mul_f32: two IEEE operations each);
+    //  * no gate = no multiply (x * 1.0f is x); one sample and one segment for the wave's 64 rows (every launch of the denoise step)
+    //    = ONE gate row, unpacked once per column block instead of once per token block;
+    //  * the image is the wave's own: a wave barrier orders it, not a workgroup barrier.
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    constexpr bool STATS = EPI == EPI_GATE_RES_STATS;
+    const int rowb = row0 + (wave_u >> 1) * 64, colb = col0 + (wave_u & 1) * 96;
+    const int nrows = p.M - rowb < 64 ? p.M - rowb : 64;   // rows of the wave's 64 that exist (<= 0: none)
+    char* img = smem + wave_u * OUT_WAVE_BYTES;
+    int u_row[3], u_col[3], u_img[3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      const int q = lane + 64 * b;
+      u_row[b] = q / 12;
+      u_col[b] = (q - u_row[b] * 12) * 16;
+      u_img[b] = u_row[b] * OUT_ROW_BYTES + u_col[b];
+    }
+    auto rows_rsrc = [&](const bf16_t* base, int64_t ld) {
+      const int64_t bytes = nrows > 0 ? ((int64_t)(nrows - 1) * ld + 96) * 2 : 0;   // (launch_gemm: 64 rows of ld stay below 2^31 bytes)
+      return __builtin_amdgcn_make_buffer_rsrc((void*)(base + (int64_t)rowb * ld + colb), 0, (int)bytes, 0x00020000);
+    };
+    int off_r[3], off_o[3];   // byte offsets of units 0 .. 2 under the leading dimensions ldr / ldo; unit 3 a + b is 16 a rows on
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      off_r[b] = u_row[b] * ((int)p.ldr * 2) + u_col[b];
+      off_o[b] = u_row[b] * ((int)p.ldo * 2) + u_col[b];
+    }
+    const int step_r = (int)p.ldr * 32, step_o = (int)p.ldo * 32;
+    auto add8 = [](u32x4 a, u32x4 b) {   // bf16(a + b) on eight values
+      u32x4 r;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        r[k] = pack2bf(f32x2{bflo(a[k]), bfhi(a[k])} + f32x2{bflo(b[k]), bfhi(b[k])});
+      }
+      return r;
+    };
+    u32x4 rres16[12];
+#pragma unroll
+    for (int it = 0; it < 12; ++it) rres16[it] = u32x4{0, 0, 0, 0};
+    if (p.res != nullptr) {
+      const auto rs_res = rows_rsrc(p.res, p.ldr);
+#pragma unroll
+      for (int it = 0; it < 12; ++it) rres16[it] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, off_r[it % 3] + (it / 3) * step_r, 0, 0);
+    }
+    if constexpr (STATS) {
+      // The residual rows go INTO the wave's image first (coalesced 16-byte units): the accumulator pass below then forms
+      // x_new = bf16(res + bf16(gate (acc + bias))) where it holds the accumulators, and the store phase is a copy.
+#pragma unroll
+      for (int it = 0; it < 12; ++it) *reinterpret_cast<u32x4*>(img + u_img[it % 3] + (it / 3) * (16 * OUT_ROW_BYTES)) = rres16[it];
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+    }
+    f32x2 bia[6][2];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) bia[j][0] = bia[j][1] = f32x2{0.f, 0.f};
+    if (p.bias != nullptr) {
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        const uint2 b_ = *reinterpret_cast<const uint2*>(p.bias + colb + j * 16 + 4 * lq);
+        bia[j][0] = f32x2{bflo(b_.x), bfhi(b_.x)};
+        bia[j][1] = f32x2{bflo(b_.y), bfhi(b_.y)};
+      }
+    }
+    // accumulator pass.  KIND 0: no gate; 1: the wave's rows share one gate row; 2: a gate row per token (a sample or segment boundary
+    // inside the wave's 64 rows)
+    const int r_lo = rowb < p.M ? rowb : p.M - 1, r_hi = rowb + 63 < p.M ? rowb + 63 : p.M - 1;   // clamped as the per-token form clamps
+    uint2 o16[4][6];   // u = bf16(gate (acc + bias)), as the accumulators lie
+    auto acc_pass = [&](auto kind_tag, int sample_lo, bool alt_lo) {
+      constexpr int KIND = decltype(kind_tag)::value;
+      f32x2 g1[KIND == 1 ? 6 : 1][2];
+      uint2 gg[KIND == 2 ? 4 : 1][KIND == 2 ? 6 : 1];
+      if constexpr (KIND == 1) {
+        const bf16_t* gate_row = p.gate + (int64_t)sample_lo * p.gate_stride + colb + (alt_lo ? p.gate_alt : (int64_t)0);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+          const uint2 g_ = *reinterpret_cast<const uint2*>(gate_row + j * 16 + 4 * lq);
+          g1[j][0] = f32x2{bflo(g_.x), bfhi(g_.x)};
+          g1[j][1] = f32x2{bflo(g_.y), bfhi(g_.y)};
+        }
+      }
+      if constexpr (KIND == 2) {
+        // the gate rows of all four token blocks in ONE burst (24 x 8 B per lane), not four dependent round trips
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          int grow = rowb + i * 16 + l15;
+          grow = grow < p.M ? grow : p.M - 1;
+          const int sample = grow / p.rows_per_sample;
+          const bf16_t* gate_row = p.gate + (int64_t)sample * p.gate_stride + colb + 4 * lq;
+          if (p.seg_split > 0 && grow - sample * p.rows_per_sample < p.seg_split) gate_row += p.gate_alt;
+#pragma unroll
+          for (int j = 0; j < 6; ++j) gg[i][j] = *reinterpret_cast<const uint2*>(gate_row + j * 16);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+          f32x2 v0 = acc16[i][j].lo + bia[j][0], v1 = acc16[i][j].hi + bia[j][1];
+          if constexpr (KIND == 1) {
+            v0 *= g1[j][0];
+            v1 *= g1[j][1];
+          }
+          if constexpr (KIND == 2) {
+            const uint2 g_ = gg[KIND == 2 ? i : 0][KIND == 2 ? j : 0];
+            v0 *= f32x2{bflo(g_.x), bfhi(g_.x)};
+            v1 *= f32x2{bflo(g_.y), bfhi(g_.y)};
+          }
+          o16[i][j].x = pack2bf(v0);
+          o16[i][j].y = pack2bf(v1);
+        }
+      }
+    };
+    if (p.gate == nullptr) {
+      acc_pass(std::integral_constant<int, 0>{}, 0, false);
+    } else {
+      const int s_lo = r_lo / p.rows_per_sample, s_hi = r_hi / p.rows_per_sample;
+      const bool alt_lo = p.seg_split > 0 && r_lo - s_lo * p.rows_per_sample < p.seg_split;
+      const bool alt_hi = p.seg_split > 0 && r_hi - s_hi * p.rows_per_sample < p.seg_split;
+      if (s_lo == s_hi && alt_lo == alt_hi) acc_pass(std::integral_constant<int, 1>{}, s_lo, alt_lo);
+      else acc_pass(std::integral_constant<int, 2>{}, 0, false);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        uint2 o = o16[i][j];
+        uint2* at = reinterpret_cast<uint2*>(img + (i * 16 + l15) * OUT_ROW_BYTES + (j * 16 + 4 * lq) * 2);
+        if constexpr (STATS) {
+          // + residual (the two roundings of the plain epilogue: bf16(u), then bf16(u + res)); the statistics follow from the image
+          const uint2 rr = *at;
+          o.x = pack2bf(f32x2{bflo(o.x), bfhi(o.x)} + f32x2{bflo(rr.x), bfhi(rr.x)});
+          o.y = pack2bf(f32x2{bflo(o.y), bfhi(o.y)} + f32x2{bflo(rr.y), bfhi(rr.y)});
+        }
+        *at = o;
+      }
+    }
+    if constexpr (STATS) stats_from_image();   // (waits for the image itself)
+    else {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+    }
+    // store phase: all twelve image reads are issued before the first store
+    u32x4 val[12], r1[EPI == EPI_GATE_RES ? 12 : 1], r2[EPI == EPI_GATE_RES ? 12 : 1];
+    if constexpr (EPI == EPI_GATE_RES) {
+      // folded PAB broadcasts (GemmParams::add1 / add2, leading dimension ldr): fetched in one burst while the image is read
+      if (p.add1 != nullptr) {
+        const auto rs_1 = rows_rsrc(p.add1, p.ldr);
+#pragma unroll
+        for (int it = 0; it < 12; ++it) r1[it] = __builtin_amdgcn_raw_buffer_load_b128(rs_1, off_r[it % 3] + (it / 3) * step_r, 0, 0);
+      }
+      if (p.add2 != nullptr) {
+        const auto rs_2 = rows_rsrc(p.add2, p.ldr);
+#pragma unroll
+        for (int it = 0; it < 12; ++it) r2[it] = __builtin_amdgcn_raw_buffer_load_b128(rs_2, off_r[it % 3] + (it / 3) * step_r, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int it = 0; it < 12; ++it) val[it] = *reinterpret_cast<const u32x4*>(img + u_img[it % 3] + (it / 3) * (16 * OUT_ROW_BYTES));
+    if constexpr (EPI == EPI_GATE_RES) {
+      if (p.aux != nullptr) {   // the PAB cache slab takes gate (acc + bias), before the residual
+        const auto rs_aux = rows_rsrc(p.aux, p.ldaux);
+        const int ldaux2 = (int)p.ldaux * 2;
+#pragma unroll
+        for (int it = 0; it < 12; ++it)
+          __builtin_amdgcn_raw_buffer_store_b128(val[it], rs_aux, (u_row[it % 3] + 16 * (it / 3)) * ldaux2 + u_col[it % 3], 0, 0);
+      }
+      if (p.res != nullptr) {
+#pragma unroll
+        for (int it = 0; it < 12; ++it) val[it] = add8(val[it], rres16[it]);
+      }
+      if (p.add1 != nullptr) {
+#pragma unroll
+        for (int it = 0; it < 12; ++it) val[it] = add8(val[it], r1[it]);
+      }
+      if (p.add2 != nullptr) {
+#pragma unroll
+        for (int it = 0; it < 12; ++it) val[it] = add8(val[it], r2[it]);
+      }
+    }
+    const auto rs_out = rows_rsrc(p.out, p.ldo);
+#pragma unroll
+    for (int it = 0; it < 12; ++it) __builtin_amdgcn_raw_buffer_store_b128(val[it], rs_out, off_o[it % 3] + (it / 3) * step_o, 0, 0);
+    if constexpr (EPI == EPI_GATE_RES) {
+      if (p.stats_out != nullptr) {
+        // LayerNorm partials next to a PAB slab copy: what was stored goes back into the image, where a lane pair owns a token row
+#pragma unroll
+        for (int it = 0; it < 12; ++it) *reinterpret_cast<u32x4*>(img + u_img[it % 3] + (it / 3) * (16 * OUT_ROW_BYTES)) = val[it];
+        stats_from_image();
+      }
+    }
+    return;
+  }
   if constexpr (MF) {
     // ---- 16x16x32 accumulators: token 16 i + l15 of the wave's 64 rows, columns 16 j + 4 lq .. + 3
     if constexpr (LN) {
@@ -794,34 +997,13 @@ __global__ __launch_bounds__(Geo<BM_>::NT + PROD * 256, PROD ? 3 : 2) void gemm_
           *reinterpret_cast<uint2*>(st + (i * 16 + l15) * OUT_ROW_BYTES + (j * 16 + 4 * lq) * 2) = o;
         }
       }
-    } else {
+    } else {   // (EPI_BIAS / EPI_BIAS_GELU: the gated epilogues have returned above)
       uint2 bb16[6];
 #pragma unroll
       for (int j = 0; j < 6; ++j) bb16[j] = make_uint2(0, 0);
       if (p.bias != nullptr) {
 #pragma unroll
         for (int j = 0; j < 6; ++j) bb16[j] = *reinterpret_cast<const uint2*>(p.bias + ncol0 + j * 16 + 4 * lq);
-      }
-      // the gate rows of all four token blocks in ONE burst (24 x 8 B per lane): loaded per token block inside the loop below they were
-      // four dependent global round trips per wave (vmcnt(5) .. vmcnt(0) four times over), ~1 us each with one wave per SIMD
-      uint2 gg[GATED ? 4 : 1][6];
-      if (GATED) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 6; ++j) gg[i][j] = make_uint2(0x3f803f80u, 0x3f803f80u);  // bf16 1.0 pairs
-        if (p.gate != nullptr) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            int grow = row0 + wm * 64 + i * 16 + l15;
-            grow = grow < p.M ? grow : p.M - 1;
-            const int sample = grow / p.rows_per_sample;
-            const bf16_t* gate_row = p.gate + (int64_t)sample * p.gate_stride + ncol0 + 4 * lq;
-            if (p.seg_split > 0 && grow - sample * p.rows_per_sample < p.seg_split) gate_row += p.gate_alt;
-#pragma unroll
-            for (int j = 0; j < 6; ++j) gg[i][j] = *reinterpret_cast<const uint2*>(gate_row + j * 16);
-          }
-        }
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -837,23 +1019,12 @@ __global__ __launch_bounds__(Geo<BM_>::NT + PROD * 256, PROD ? 3 : 2) void gemm_
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = gelu_tanh(v[r]);
           }
-          if (GATED) {
-            const uint2 g_ = gg[GATED ? i : 0][j];
-            v[0] *= bflo(g_.x); v[1] *= bfhi(g_.x); v[2] *= bflo(g_.y); v[3] *= bfhi(g_.y);
-          }
           uint2 o;
           o.x = pack2bf(v[0], v[1]);
           o.y = pack2bf(v[2], v[3]);
-          if constexpr (EPI == EPI_GATE_RES_STATS) {
-            // + residual (same two roundings as the plain epilogue: bf16(u), then bf16(u + res)); the statistics follow from the image
-            const uint2 rr = *reinterpret_cast<const uint2*>(st + m_local * OUT_ROW_BYTES + n_local * 2);
-            o.x = pack2bf(bflo(o.x) + bflo(rr.x), bfhi(o.x) + bfhi(rr.x));
-            o.y = pack2bf(bflo(o.y) + bflo(rr.y), bfhi(o.y) + bfhi(rr.y));
-          }
           *reinterpret_cast<uint2*>(st + m_local * OUT_ROW_BYTES + n_local * 2) = o;
         }
       }
-      if constexpr (EPI == EPI_GATE_RES_STATS) stats_from_image();
     }
   }
   if constexpr (LN && !MF) {
@@ -1289,6 +1460,9 @@ int launch_gemm(const GemmParams& p_, int epi, hipStream_t stream) {
   // tile-relative operand offsets are 32-bit (buffer addressing): checked for EVERY epilogue, in front of the per-epilogue dispatch
   if (p.lda * 512 + (int64_t)p.K * 2 >= 0x7fffffff || p.ldw * 384 + (int64_t)p.K * 2 >= 0x7fffffff) return VSYS_ERR_SHAPE;
   if ((epi == EPI_GATE_RES || epi == EPI_GATE_RES_STATS) && p.gate && p.rows_per_sample <= 0) return VSYS_ERR_SHAPE;
+  // the gated epilogues address 64 rows of out / res / aux with 32-bit byte offsets from a wave's first row
+  if ((epi == EPI_GATE_RES || epi == EPI_GATE_RES_STATS) && (p.ldo * 128 >= 0x7fffffff || (p.res && p.ldr * 128 >= 0x7fffffff) || (p.aux && p.ldaux * 128 >= 0x7fffffff)))
+    return VSYS_ERR_SHAPE;
   const bool ln = epi == EPI_LN_BIAS || epi == EPI_LN_GELU;
   if (ln && (!p.cs || !p.cv || !p.ln_stats || p.ln_nb < 1 || p.ln_nb > 12 || p.ln_nb * LN_BLOCK != p.K || p.ln_ld < p.M)) return VSYS_ERR_SHAPE;
   if (epi == EPI_GATE_RES_STATS && (!p.stats_out || p.stats_ld < p.M || p.aux)) return VSYS_ERR_ARG;
