@@ -344,6 +344,38 @@ int vsys_flash_attn_d64_kb(const void* q, int64_t q_stride, const void* ln_w, co
                         int64_t out_stride, int64_t batch, int64_t heads, int64_t q_len, int64_t kv_len, int64_t kv_pad, float eps, float k_norm_bound,
                         void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Open-Sora-Plan v1.2 (OpenSoraT2V): full 3-D self-attention and masked cross-attention at head_dim 96.
+ * Neither entry point has a VSYS_OP code (the op table keeps its size): a launch program replays them from a host closure.
+ * ------------------------------------------------------------------------------------------------------------------ */
+
+/* K side of AttnProcessor2_0 (open_sora_plan_v120_transformer_3d.py:886-1128) with RoPE3D (:63-118): the 96 columns of a head are
+ * three chunks of 32 (frame, row, column position); inside a chunk out = x cos + rotate_half(x) sin, rotate_half = (-x[16:32],
+ * x[0:16]).  rope_cos / rope_sin: fp32 [kv_len, 96], one row per KEY TOKEN (the same tables for every sample and head), applied
+ * column by column; NULL = no rotation (cross-attention).  Rounding: k^ = bf16((fp32(k cos) + fp32(rot(k) sin)) * 96^-0.5 log2(e)):
+ * two fp32 products and one fp32 sum (no fused multiply-add), the softmax scale in fp32, ONE rounding to bf16.
+ * kp [batch, H, kv_pad, 96] plain rows, vt [batch, H, 96, kv_pad] transposed V, kv_pad % 64 == 0; keys kv_len <= s < kv_pad are
+ * written as zeros in both.  k(b, s, h) at k + (b*kv_len + s)*k_stride + h*96, v likewise; strides % 8 == 0.  k, v, kp, vt and the
+ * tables are read / written 16 bytes at a time: a base pointer that is not 16-byte aligned is VSYS_ERR_ALIGN. */
+int vsys_attn_prep_kv96(const void* k, int64_t k_stride, const void* v, int64_t v_stride, const void* rope_cos_f32,
+                        const void* rope_sin_f32, void* kp, void* vt, int64_t batch, int64_t heads, int64_t kv_len, int64_t kv_pad,
+                        void* stream);
+
+/* softmax(q k^T / sqrt(96)) v for head_dim 96, non-causal (F.scaled_dot_product_attention in AttnProcessor2_0,
+ * open_sora_plan_v120_transformer_3d.py:1090-1110), q rotated on the fly: q^ = bf16(fp32(q cos) + fp32(rot(q) sin)) with
+ * rope_cos / rope_sin fp32 [q_len, 96] (NULL = none).  (kp, vt) are the layouts of vsys_attn_prep_kv96.  Keys >= kv_len are masked;
+ * with kv_lens (device int32 [batch], NULL = none) sample b attends to its first min(kv_lens[b], kv_len) keys — the count is read
+ * on the device, so a replayed launch carries no count; kv_lens[b] < 1 is the caller's error (that sample's rows are not finite).
+ * The logits of masked keys are overwritten, so Kp may hold anything there; their Vt entries must be FINITE (they are multiplied by
+ * a zero probability): the zeros vsys_attn_prep_kv96 writes behind kv_len, or the ordinary values of padded text tokens.
+ * Logits and the running maximum in fp32, P rounded to bf16 for P V, the row sum from the fp32 p, one division, one rounding.
+ * q(b, s, h) at q + (b*q_len + s)*q_stride + h*96, out likewise; q_stride % 8 == 0, out_stride % 4 == 0.  Writes only the q_len
+ * rows x heads*96 columns of out.  Base pointers: q, kp, vt and the tables 16-byte aligned, out 8-byte, kv_lens 4-byte, else
+ * VSYS_ERR_ALIGN. */
+int vsys_flash_attn_d96(const void* q, int64_t q_stride, const void* rope_cos_f32, const void* rope_sin_f32, const void* kp,
+                        const void* vt, const void* kv_lens_i32, void* out, int64_t out_stride, int64_t batch, int64_t heads,
+                        int64_t q_len, int64_t kv_len, int64_t kv_pad, void* stream);
+
 /* Temporal self-attention over the T frames of every (b, s) token: RMS qk-norm, RoPE (cos/sin fp32 [T, 72], NULL =
  * none), fp32 softmax (attentions.py:75-78,95-97,111-120; open_sora_transformer_3d.py:203-206).
  * q_norm_w == k_norm_w == NULL: no qk-norm (Latte temporal blocks, latte_transformer_3d.py:680-760).

@@ -37,6 +37,7 @@ _MODULES = {
     "models.transformers.latte_transformer_3d": "latte",            # LatteT2V
     "models.transformers.cogvideox_transformer_3d": "cogvideox",    # CogVideoXTransformer3DModel
     "models.transformers.vchitect_transformer_3d": "vchitect",      # VchitectXLTransformerModel, JointTransformerBlock
+    "models.transformers.open_sora_plan_v120_transformer_3d": "open_sora_plan",   # OpenSoraT2V, OpenSoraT2V_ROPE_L_122 (transformer only)
     "models.autoencoders.autoencoder_kl_open_sora": "vae_open_sora",    # OpenSoraVAE_V1_2
     "models.autoencoders.autoencoder_kl_cogvideox": "vae_cogvideox",    # AutoencoderKLCogVideoX
     "pipelines.open_sora": "pipeline_open_sora",              # OpenSoraConfig, OpenSoraPABConfig, OpenSoraPipeline

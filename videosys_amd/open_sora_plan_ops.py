@@ -1,0 +1,79 @@
+"""Tensor-level wrappers of the head-dim-96 attention entry points of Open-Sora-Plan v1.2 (include/videosys_amd.h:
+vsys_attn_prep_kv96, vsys_flash_attn_d96).  HIP device tensors only, no eager fallback.
+
+Neither entry point has an op code (the op table is pinned, csrc/gen/program_gen.py NO_OP), so the launch goes through ctypes on
+torch's current stream, and under a launch-program recorder it is a ``program.host_call`` closure: the program keeps the tensors
+alive and re-issues the same call, with the same addresses, at the same position of every replay.  The per-sample key counts of the
+cross-attention are read by the kernel from device memory, so a replay carries no count.
+Element-wise tests: tests/test_gpu_osp_attention.py; guard bands: tests/test_gpu_isolation_osp.py."""
+from __future__ import annotations
+
+import torch
+
+from . import _lib, program
+from .ops import _bf16, _chk, kv_pad_len
+
+HEAD_DIM = 96
+
+
+def alloc_kv_buffers96(batch, heads, kv_len, device):
+    """(kp [batch, heads, kv_pad, 96], vt [batch, heads, 96, kv_pad]) for kv_len keys, kv_pad = the next multiple of 64."""
+    kv_pad = kv_pad_len(kv_len)
+    kp = torch.zeros(batch, heads, kv_pad, HEAD_DIM, dtype=torch.bfloat16, device=device)
+    vt = torch.zeros(batch, heads, HEAD_DIM, kv_pad, dtype=torch.bfloat16, device=device)
+    return kp, vt
+
+
+def _issue(name, tensors, args):
+    """Launch ``name`` now and, under a recorder, at this position of every replay."""
+    fn = getattr(_lib.load(), name)
+    program.keep(tensors)
+
+    def issue():
+        _lib.check(fn(*args, torch.cuda.current_stream().cuda_stream), name)
+
+    program.host_call(issue)
+
+
+def _tables(rope_cos, rope_sin, rows):
+    if rope_cos is None:
+        assert rope_sin is None
+        return
+    for t in (rope_cos, rope_sin):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, HEAD_DIM)
+
+
+def attn_prep_kv96(k, v, rope_cos, rope_sin, kp, vt, batch, heads, kv_len):
+    """k, v: 2-D row-strided views [batch * kv_len, >= heads * 96] -> kp (RoPE3D rotation with the per-token fp32 tables
+    [kv_len, 96], None = none; softmax scale folded in; one rounding) and vt (transposed); keys past kv_len are written as zeros."""
+    _chk(k, v, rope_cos, rope_sin, kp, vt)
+    _bf16(k, v, kp, vt)
+    assert k.dim() == 2 and v.dim() == 2 and k.stride(1) == 1 and v.stride(1) == 1 and kp.is_contiguous() and vt.is_contiguous()
+    assert k.shape[0] >= batch * kv_len and v.shape[0] >= batch * kv_len and k.shape[1] >= heads * HEAD_DIM and v.shape[1] >= heads * HEAD_DIM
+    kv_pad = kp.shape[-2]
+    assert tuple(kp.shape[-3:]) == (heads, kv_pad, HEAD_DIM) and tuple(vt.shape[-3:]) == (heads, HEAD_DIM, kv_pad)
+    assert kp.numel() == vt.numel() == batch * heads * kv_pad * HEAD_DIM
+    _tables(rope_cos, rope_sin, kv_len)
+    dp = lambda t: None if t is None else t.data_ptr()
+    _issue("vsys_attn_prep_kv96", (k, v, rope_cos, rope_sin, kp, vt),
+           (dp(k), k.stride(0), dp(v), v.stride(0), dp(rope_cos), dp(rope_sin), dp(kp), dp(vt), batch, heads, kv_len, kv_pad))
+
+
+def flash_attn96(q, rope_cos, rope_sin, kp, vt, kv_lens, out, batch, heads, q_len, kv_len):
+    """out = softmax(rope(q) k^T / sqrt(96)) v on the layouts of attn_prep_kv96.  q, out: 2-D row-strided views [batch * q_len, >=
+    heads * 96]; rope tables fp32 [q_len, 96] or None; kv_lens: device int32 [batch] (sample b sees its first kv_lens[b] keys, every
+    count >= 1 — the caller's to guarantee) or None."""
+    _chk(q, rope_cos, rope_sin, kp, vt, kv_lens, out)
+    _bf16(q, kp, vt, out)
+    assert q.dim() == 2 and out.dim() == 2 and q.stride(1) == 1 and out.stride(1) == 1
+    assert q.shape[0] >= batch * q_len and out.shape[0] >= batch * q_len and q.shape[1] >= heads * HEAD_DIM and out.shape[1] >= heads * HEAD_DIM
+    kv_pad = kp.shape[-2]
+    assert kp.numel() == vt.numel() == batch * heads * kv_pad * HEAD_DIM and kv_len <= kv_pad
+    _tables(rope_cos, rope_sin, q_len)
+    if kv_lens is not None:
+        assert kv_lens.dtype == torch.int32 and kv_lens.is_contiguous() and kv_lens.numel() == batch
+    dp = lambda t: None if t is None else t.data_ptr()
+    _issue("vsys_flash_attn_d96", (q, rope_cos, rope_sin, kp, vt, kv_lens, out),
+           (dp(q), q.stride(0), dp(rope_cos), dp(rope_sin), dp(kp), dp(vt), dp(kv_lens), dp(out), out.stride(0), batch, heads, q_len,
+            kv_len, kv_pad))
+    return out
