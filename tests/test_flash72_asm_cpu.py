@@ -1,6 +1,7 @@
 """CPU (-m "not gpu"): the hand-allocated instruction stream of flash_attn_d72_w64 (csrc/attention_w64.hip).
 
-  * the committed csrc/flash72_w64_asm.inc is what csrc/gen/flash72_gen.py generates (the build does not run the generator);
+  * the committed csrc/flash72_w64_asm.inc and flash72_w64_map.inc (the register map for the C++ around the statements) are what
+    csrc/gen/flash72_gen.py generates (the build does not run the generator);
   * tools/gcn_emu.py executes that text for all four waves of a workgroup — LDS-DMA pieces and ds_read results landing as LATE and
     as EARLY as the counters allow, both stepping orders of the waves — around the numpy restatement of the kernel's C++ prologue /
     epilogue (tools/flash72_emu_case.py), against float64 attention on the same bf16 inputs: even / odd tile counts, a ragged last
@@ -23,8 +24,115 @@ def test_committed_include_is_what_the_generator_emits(tmp_path):
 
     out = str(tmp_path / "f.inc")
     G.write_inc(out)
-    with open(out) as a, open(os.path.join(ROOT, "videosys_amd", "csrc", "flash72_w64_asm.inc")) as b:
-        assert a.read() == b.read(), "regenerate: python videosys_amd/csrc/gen/flash72_gen.py"
+    for made, committed in ((out, "flash72_w64_asm.inc"), (str(tmp_path / G.MAP_NAME), G.MAP_NAME)):
+        with open(made) as a, open(os.path.join(ROOT, "videosys_amd", "csrc", committed)) as b:
+            assert a.read() == b.read(), "regenerate: python videosys_amd/csrc/gen/flash72_gen.py"
+
+
+INC = os.path.join(ROOT, "videosys_amd", "csrc", "flash72_w64_asm.inc")
+MAP_INC = os.path.join(ROOT, "videosys_amd", "csrc", "flash72_w64_map.inc")   # the register map (same generator)
+# SHA-256 of the bodies of the statement and clobber macros as they were before the register map was emitted beside them (what
+# is compared where the git history is not at hand)
+STREAM_SHA256 = {
+    "FLASH72_W64_ASM_V0": "5b45406e2dcfaf077a20df2592ae187a1a2d6b20efb10c6c08f0203d054095af",
+    "FLASH72_W64_ASM_V1": "fbd64e2dbb049f9b239d0761f818eddd830709a7a2db1eb16647f271943dab3a",
+    "FLASH72_W64_ASM_V3": "11e65af3142252dc0dd4f664247d99941a1f80e7eecd19fc53b7209cde3d58a5",
+    "FLASH72_W64_ASM_V5": "f0b335ea4d897771d8e8d07f6d417cc49dad9619ad3b1471b956fc2c8df49329",
+    "FLASH72_W64_ASM_V7": "1f14935bcd15312e2f81a0427261ee87243428645075a8f921a2b49d87246ddf",
+    "FLASH72_W64_ASM_V8": "659659d8f1738e592e38de71d6688b8ea9e265dffa3b98306b559c170a612757",
+    "FLASH72_W64_ASM_V9": "c791c1727f07f5ce694b3ce3a9c07476288743286d4f11f190e73e8b3da0a9a7",
+    "FLASH72_W64_ASM_V10": "53495374199d7866d6bf2d0297d2aa01fd9fa67604877404cbecf6e3345928b5",
+    "FLASH72_W64P_ASM": "9434f8e56bdab912869bab3d91ff4a269a4ed4f9339261aeb06c592e63eb4a23",
+    "FLASH72_W64P_ASM_S": "d83e951965d0ca58950ac0e04a00246f6aaf664a257b02bb04a5dd839435349c",
+    "FLASH72_W64P_ASM_STAMP": "45e044565d63417e15fd97e1707ac01fe978aee499c8baeb12bae1fb5fb8abe9",
+    "FLASH72_W64_CLOBBERS": "e57dec33721bbe9c814a8820fd239295d08ba00f601f22d00403a4d0fa593834",
+    "FLASH72_W64_CLOBBERS_PHASE": "44aeb90af82ff78881af3e8c73bd82288eee702f2aaed0e7a6e1b126d9efa8e2",
+    "FLASH64_W64_ASM_V1": "6b5ba2432b05683060f1a02827e6e030a4872b106b58e85193b069f2d5612565",
+    "FLASH64_W64_ASM_V4": "7d3b30a224b0a9342d52bc5e0e152a78d94573a78fa9dd57e2f8f6ece426c56c",
+    "FLASH64_W64_ASM_V5": "928eca17d2745fd5ab22fa197fb201a42215ce57071ba6d263592f4b3aaf6c7a",
+    "FLASH64_W64_CLOBBERS": "32bd8b39c4ca26bf2aa46c1dbac5054bd9c06aa385d4f5fd5e6c6e35359c0edf",
+}
+
+
+def _macros(text):
+    """{name: body} of every #define of the include (a body runs over its backslash-continued lines; parameters are not part of it)"""
+    import re
+
+    out, name = {}, None
+    for ln in text.split("\n"):
+        m = re.match(r"#define (\w+)(\(.*?\))? ?(.*)$", ln)
+        if m:
+            name = m.group(1)
+            out[name] = [m.group(3)]
+        elif name and out[name][-1].endswith("\\"):
+            out[name].append(ln)
+        else:
+            name = None
+    return {k: "\n".join(v) for k, v in out.items()}
+
+
+def test_statement_and_clobber_macros_are_the_parents():
+    """The register map is emitted beside the include; the generated statements and their clobber lists did not move by a byte:
+    compared with the parent commit's include where git has it, with the recorded SHA-256 in any case."""
+    import hashlib
+    import subprocess
+
+    with open(INC) as fh:
+        now = _macros(fh.read())
+    assert set(now) == set(STREAM_SHA256), sorted(now)
+    try:
+        r = subprocess.run(["git", "show", "HEAD~:videosys_amd/csrc/flash72_w64_asm.inc"], cwd=ROOT, capture_output=True, text=True, timeout=60)
+        parent = _macros(r.stdout) if r.returncode == 0 else {}
+    except (OSError, subprocess.SubprocessError):
+        parent = {}
+    for name, sha in STREAM_SHA256.items():
+        if name in parent:
+            assert now[name] == parent[name], name
+        assert hashlib.sha256(now[name].encode()).hexdigest() == sha, name
+
+
+def test_register_map_macros_are_the_generators_allocation():
+    """What the C++ around the statements uses of the register map — Q into a[Q ...], O out of a[O ...], the d64 row sum, the operand
+    names — is emitted from the generator's own Q, O, NCC and operand lists, and the operand lists name exactly what the generated
+    texts read."""
+    import re
+
+    import flash72_gen as G
+
+    with open(MAP_INC) as fh:
+        now = _macros(fh.read())
+    for fam, ncc, ndt in (("FLASH72_W64", G.NCC, 3), ("FLASH64_W64", 4, 2)):
+        assert ncc == (5 if ndt == 3 else 4)
+        for blk in "AB":
+            w = now[f"{fam}_WRITE_Q_{blk}"]
+            text, rest = w.split('" : : ')
+            regs = [Q for Q in range(G.Q[blk], G.Q[blk] + 4 * ncc)]
+            assert [(int(a_), int(i)) for a_, i in re.findall(r"v_accvgpr_write_b32 a(\d+), %(\d+)", text)] == list(zip(regs, range(4 * ncc)))
+            assert text.endswith("s_nop 1\\n\\t") == (blk == "B")
+            ins, clob = rest.split(" : ")
+            assert re.findall(r'"v"\(\(qw_\)\[(\d)\]\.([xyzw])\)', ins) == [(str(i // 4), "xyzw"[i % 4]) for i in range(4 * ncc)]
+            assert re.findall(r'"a(\d+)"', clob) == [str(r) for r in regs]
+            assert max(regs) < (G.Q["B"] if blk == "A" else G.KF) and G.O["B"] + 48 <= G.Q["A"]
+            r = now[f"{fam}_READ_O_{blk}"]
+            reads = re.findall(r'asm volatile\("v_accvgpr_read_b32 %0, a(\d+)" : "=v"\((.*?)\)\);', r)
+            want = [(str(G.O[blk] + 16 * dt + k), f"(o_)[{dt}][{k}]") for dt in range(ndt) for k in range(16)]
+            if ndt == 2:
+                want.append((str(G.O[blk] + 36), "lsum_"))      # accumulator 4 of the third 32-dim block: the ones rows of Vt
+            assert reads == want and r.count("v_accvgpr") == len(want)
+    forms = {"FLASH72_W64_OPERANDS": [G.generate(v) for v in (0, 1, 3, 7, 8, 9, 10)], "FLASH72_W64_OPERANDS_S": [G.generate(5)],
+             "FLASH72_W64P_OPERANDS": [G.generate(1, persist=True), G.generate(1, persist=True, pstamp=True)],
+             "FLASH72_W64P_OPERANDS_S": [G.generate(5, persist=True)],
+             "FLASH64_W64_OPERANDS": [G.generate(1, d64=True), G.generate(4, d64=True)], "FLASH64_W64_OPERANDS_S": [G.generate(5, d64=True)]}
+    for macro, texts in forms.items():
+        bound = re.findall(r'\[(\w+)\] "([sv])"\((\w+)\)', now[macro])
+        assert all(n == var for n, _, var in bound) and len({n for n, _, _ in bound}) == len(bound)
+        assert all((c == "v") == (n in G.VECTOR_OPERANDS) for n, c, _ in bound)
+        for lines in texts:
+            used = set(re.findall(r"%\[(\w+)\]", "\n".join(lines))) - {"t0", "t1", "t2"}     # (the lab stamps are outputs)
+            assert used == {n for n, _, _ in bound}, (macro, used ^ {n for n, _, _ in bound})
+    for src in ("attention_w64.hip", "attention64_w64.hip", "flash_w64.h"):
+        with open(os.path.join(ROOT, "videosys_amd", "csrc", src)) as fh:
+            assert "v_accvgpr" not in fh.read(), src
 
 
 def test_steady_state_gaps_hold_at_most_five_fillers():

@@ -11,18 +11,21 @@
 // the row sum of P rides on the matrix pipe, which has the slack here (40 MFMAs against ~190 VALU issues per tile), where
 // flash_attn_d64_kernel adds it on the VALU.  At CogVideoX's 17 776 keys an item walks 278 tiles, so the one-item-per-workgroup
 // form's seams (attention_w64.hip) do not matter.
-#include "common.h"
-#include "vsys_internal.h"
-
-#include "flash72_w64_asm.inc"
+//
+// The register map (Q into / O out of the accumulator file, the statements' operand names) comes from the generator with the
+// stream (FLASH64_W64_WRITE_Q_*, _READ_O_*, _OPERANDS in flash72_w64_map.inc); the variables the statement reads carry its
+// operand names (the operand list binds by name).  Descriptors, fragment addressing, the row bound and the launch are flash_w64.h,
+// shared with attention_w64.hip.
+#include "flash_w64.h"
 
 namespace vsys {
 namespace {
 
-constexpr int HD = 64, KROW = 128, VROW = 128;
+using w64::VROW;
+constexpr int HD = 64, KROW = 128;
 constexpr int K_TILE_BYTES = 64 * KROW;              // 8192
 constexpr int KV_STAGE = K_TILE_BYTES + 96 * VROW;   // 20480: K tile + Vt image of 96 rows (64 fetched + 32 constant)
-constexpr int W64_STAGES = 4;
+constexpr int W64_STAGES = w64::STAGES;
 
 struct Flash64W64Params {
   const bf16_t* q; int64_t q_stride;
@@ -35,18 +38,6 @@ struct Flash64W64Params {
   float eps;
   float k_bound;   // VAR 5: upper bound on the norm of every Kp row (FlashW64Params::k_bound, attention_w64.hip)
 };
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ u32x4 make_rsrc64(const void* base, unsigned bytes) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-  u32x4 r;
-  r.x = __builtin_amdgcn_readfirstlane((unsigned)a);
-  r.y = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);
-  r.z = __builtin_amdgcn_readfirstlane(bytes);
-  r.w = 0x00020000u;
-  return r;
-}
 
 // VAR: placement variant of the generated stream (flash72_gen.py body(): 1 = as the d72 kernel, 4 = one more P unit in the PV phase)
 template <int VAR>
@@ -65,14 +56,14 @@ __global__ __launch_bounds__(256, 1) void flash_attn_d64_w64_kernel(Flash64W64Pa
   // Vt pieces w, w + 4 (rows 8 j + (lane >> 3), slot (lane & 7) holding logical slot (lane & 7) ^ ((row >> 1) & 7))
   const bf16_t* kbase = p.kp + (int64_t)bh * p.kv_pad * HD;
   const bf16_t* vbase = p.vt + (int64_t)bh * HD * p.kv_pad;
-  const u32x4 rsrc_k = make_rsrc64(kbase, (unsigned)(p.kv_pad * HD * 2)), rsrc_v = make_rsrc64(vbase, (unsigned)(HD * p.kv_pad * 2));
-  const int k_voff = lane * 16;
-  const int v_voff = ((lane >> 3) * p.kv_pad * 2 + (((lane & 7) ^ (lane >> 4)) << 4)) ^ ((wave_u & 1) << 6);
+  const w64::u32x4 rk = w64::make_rsrc(kbase, (unsigned)(p.kv_pad * HD * 2)), rv = w64::make_rsrc(vbase, (unsigned)(HD * p.kv_pad * 2));
+  const int kvo = lane * 16;
+  const int vvo = ((lane >> 3) * p.kv_pad * 2 + (((lane & 7) ^ (lane >> 4)) << 4)) ^ ((wave_u & 1) << 6);
   const int wl = wave_u * 1024;
   const int sv0 = wave_u * 8 * p.kv_pad * 2, sv1 = (wave_u + 4) * 8 * p.kv_pad * 2;
-  const int lb = (int)(unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)smem;
-  const int ntiles = (p.kv_len + 63) >> 6;
-  const int lim = p.kv_len - (ntiles - 1) * 64 - 16 * hi;
+  const int lb = w64::lds_base(smem);
+  const int nt = (p.kv_len + 63) >> 6;
+  const int lim = p.kv_len - (nt - 1) * 64 - 16 * hi;
 
   // rows 64..95 of every stage's Vt image: constant — row 72 (read by the hi = 0 half) and 76 (hi = 1) are ones, so accumulator 4 of
   // the third PV block is sum_k P[k][q]; the rest is MFMA padding
@@ -83,15 +74,15 @@ __global__ __launch_bounds__(256, 1) void flash_attn_d64_w64_kernel(Flash64W64Pa
   }
 
   // ---- fragment read offsets inside a stage
-  const int krow = 16 * ((l31 >> 2) & 1) + 4 * (l31 >> 3) + (l31 & 3);
+  const int krow = w64::frag_krow(l31);
   const int k_roff = krow * KROW + ((hi ^ ((krow >> 1) & 7)) << 4);   // logical chunk 2 cc + hi at physical chunk ^ ((row >> 1) & 7)
   const int kfa0 = k_roff, kfa1 = k_roff ^ (1 << 5), kfa2 = k_roff ^ (2 << 5), kfa3 = k_roff ^ (3 << 5);
-  const int v_roff = K_TILE_BYTES + l31 * VROW + (((2 * hi) ^ ((l31 >> 1) & 7)) << 4);
-  const int vfa0 = v_roff ^ (0 << 4), vfa1 = v_roff ^ (1 << 4), vfa2 = v_roff ^ (4 << 4), vfa3 = v_roff ^ (5 << 4);
+  const w64::VtFrag vf = w64::vt_frag<K_TILE_BYTES>(l31, hi);
+  const int vfa0 = vf.vfa0, vfa1 = vf.vfa1, vfa2 = vf.vfa2, vfa3 = vf.vfa3;
 
   // ---- Q fragments of the two 32-row blocks (B operand: lane holds Q[row][16c + 8hi .. +8], c = 0..3): LayerNorm + RoPE as
   // flash_attn_d64_kernel's prologue
-  unsigned qw[2][16];
+  uint4 qw[2][4];
   float nmv[2] = {0.f, 0.f};   // VAR 5: -(row bound) of this lane's query row in block A / B
 #pragma unroll
   for (int blk = 0; blk < 2; ++blk) {
@@ -147,83 +138,28 @@ __global__ __launch_bounds__(256, 1) void flash_attn_d64_w64_kernel(Flash64W64Pa
         }
       }
     }
-    if constexpr (VAR == 5) {
-      float qn2 = 0.f;
+    if constexpr (VAR == 5) nmv[blk] = w64::neg_row_bound<4>(x, p.k_bound);
 #pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) qn2 += x[c][e] * x[c][e];
-      qn2 += __shfl_xor(qn2, 32, 64);
-      nmv[blk] = -(sqrtf(qn2) * p.k_bound * 1.015625f);
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const uint4 pk = pack8(x[c]);
-      qw[blk][4 * c + 0] = pk.x; qw[blk][4 * c + 1] = pk.y; qw[blk][4 * c + 2] = pk.z; qw[blk][4 * c + 3] = pk.w;
-    }
+    for (int c = 0; c < 4; ++c) qw[blk][c] = pack8(x[c]);
   }
-  // Q -> a[96:111] (block A), a[116:131] (block B)
-#define QW(b_, i_) "v"(qw[b_][i_])
-  asm volatile(
-      "v_accvgpr_write_b32 a96, %0\n\tv_accvgpr_write_b32 a97, %1\n\tv_accvgpr_write_b32 a98, %2\n\tv_accvgpr_write_b32 a99, %3\n\t"
-      "v_accvgpr_write_b32 a100, %4\n\tv_accvgpr_write_b32 a101, %5\n\tv_accvgpr_write_b32 a102, %6\n\tv_accvgpr_write_b32 a103, %7\n\t"
-      "v_accvgpr_write_b32 a104, %8\n\tv_accvgpr_write_b32 a105, %9\n\tv_accvgpr_write_b32 a106, %10\n\tv_accvgpr_write_b32 a107, %11\n\t"
-      "v_accvgpr_write_b32 a108, %12\n\tv_accvgpr_write_b32 a109, %13\n\tv_accvgpr_write_b32 a110, %14\n\tv_accvgpr_write_b32 a111, %15\n\t"
-      :
-      : QW(0, 0), QW(0, 1), QW(0, 2), QW(0, 3), QW(0, 4), QW(0, 5), QW(0, 6), QW(0, 7), QW(0, 8), QW(0, 9), QW(0, 10), QW(0, 11), QW(0, 12), QW(0, 13), QW(0, 14), QW(0, 15)
-      : "a96", "a97", "a98", "a99", "a100", "a101", "a102", "a103", "a104", "a105", "a106", "a107", "a108", "a109", "a110", "a111");
-  asm volatile(
-      "v_accvgpr_write_b32 a116, %0\n\tv_accvgpr_write_b32 a117, %1\n\tv_accvgpr_write_b32 a118, %2\n\tv_accvgpr_write_b32 a119, %3\n\t"
-      "v_accvgpr_write_b32 a120, %4\n\tv_accvgpr_write_b32 a121, %5\n\tv_accvgpr_write_b32 a122, %6\n\tv_accvgpr_write_b32 a123, %7\n\t"
-      "v_accvgpr_write_b32 a124, %8\n\tv_accvgpr_write_b32 a125, %9\n\tv_accvgpr_write_b32 a126, %10\n\tv_accvgpr_write_b32 a127, %11\n\t"
-      "v_accvgpr_write_b32 a128, %12\n\tv_accvgpr_write_b32 a129, %13\n\tv_accvgpr_write_b32 a130, %14\n\tv_accvgpr_write_b32 a131, %15\n\t"
-      "s_nop 1\n\t"
-      :
-      : QW(1, 0), QW(1, 1), QW(1, 2), QW(1, 3), QW(1, 4), QW(1, 5), QW(1, 6), QW(1, 7), QW(1, 8), QW(1, 9), QW(1, 10), QW(1, 11), QW(1, 12), QW(1, 13), QW(1, 14), QW(1, 15)
-      : "a116", "a117", "a118", "a119", "a120", "a121", "a122", "a123", "a124", "a125", "a126", "a127", "a128", "a129", "a130", "a131");
-#undef QW
+  FLASH64_W64_WRITE_Q_A(qw[0]);
+  FLASH64_W64_WRITE_Q_B(qw[1]);
 
   // ---- the tile loop
-#define W64_LOOP(TEXT_)                                                                                                          \
-  asm volatile(TEXT_                                                                                                             \
-               :                                                                                                                 \
-               : [rk] "s"(rsrc_k), [rv] "s"(rsrc_v), [wl] "s"(wl), [sv0] "s"(sv0), [sv1] "s"(sv1), [lb] "s"(lb), [nt] "s"(ntiles), \
-                 [lim] "v"(lim), [kvo] "v"(k_voff), [vvo] "v"(v_voff), [kfa0] "v"(kfa0), [kfa1] "v"(kfa1), [kfa2] "v"(kfa2),       \
-                 [kfa3] "v"(kfa3), [vfa0] "v"(vfa0), [vfa1] "v"(vfa1), [vfa2] "v"(vfa2), [vfa3] "v"(vfa3)                         \
-               : FLASH64_W64_CLOBBERS)
   if constexpr (VAR == 5) {   // no running max: the row bounds ride in as the -m splat
-    asm volatile(FLASH64_W64_ASM_V5
-                 :
-                 : [rk] "s"(rsrc_k), [rv] "s"(rsrc_v), [wl] "s"(wl), [sv0] "s"(sv0), [sv1] "s"(sv1), [lb] "s"(lb), [nt] "s"(ntiles),
-                   [lim] "v"(lim), [kvo] "v"(k_voff), [vvo] "v"(v_voff), [kfa0] "v"(kfa0), [kfa1] "v"(kfa1), [kfa2] "v"(kfa2),
-                   [kfa3] "v"(kfa3), [vfa0] "v"(vfa0), [vfa1] "v"(vfa1), [vfa2] "v"(vfa2), [vfa3] "v"(vfa3), [nma] "v"(nmv[0]),
-                   [nmb] "v"(nmv[1])
-                 : FLASH64_W64_CLOBBERS);
+    const float nma = nmv[0], nmb = nmv[1];
+    asm volatile(FLASH64_W64_ASM_V5 : : FLASH64_W64_OPERANDS_S : FLASH64_W64_CLOBBERS);
   }
-  else if constexpr (VAR == 4) W64_LOOP(FLASH64_W64_ASM_V4);
-  else W64_LOOP(FLASH64_W64_ASM_V1);
-#undef W64_LOOP
+  else if constexpr (VAR == 4) asm volatile(FLASH64_W64_ASM_V4 : : FLASH64_W64_OPERANDS : FLASH64_W64_CLOBBERS);
+  else asm volatile(FLASH64_W64_ASM_V1 : : FLASH64_W64_OPERANDS : FLASH64_W64_CLOBBERS);
 
-  // ---- epilogue: O[q][d] = O^T[d][q] / l ; lane holds d = 32dt + (r&3) + 8(r>>2) + 4hi; 16-byte stores through v_permlane32_swap
+  // ---- epilogue: O / l of the two blocks; l = row 72 (hi = 0) / 76 (hi = 1) of the Vt image: sum_k P[k][q]
 #pragma unroll
   for (int blk = 0; blk < 2; ++blk) {
     float o[2][16], lsum;
-#define RDO(dt_, r_, reg_) asm volatile("v_accvgpr_read_b32 %0, " reg_ : "=v"(o[dt_][r_]))
-    if (blk == 0) {
-      RDO(0, 0, "a0"); RDO(0, 1, "a1"); RDO(0, 2, "a2"); RDO(0, 3, "a3"); RDO(0, 4, "a4"); RDO(0, 5, "a5"); RDO(0, 6, "a6"); RDO(0, 7, "a7");
-      RDO(0, 8, "a8"); RDO(0, 9, "a9"); RDO(0, 10, "a10"); RDO(0, 11, "a11"); RDO(0, 12, "a12"); RDO(0, 13, "a13"); RDO(0, 14, "a14"); RDO(0, 15, "a15");
-      RDO(1, 0, "a16"); RDO(1, 1, "a17"); RDO(1, 2, "a18"); RDO(1, 3, "a19"); RDO(1, 4, "a20"); RDO(1, 5, "a21"); RDO(1, 6, "a22"); RDO(1, 7, "a23");
-      RDO(1, 8, "a24"); RDO(1, 9, "a25"); RDO(1, 10, "a26"); RDO(1, 11, "a27"); RDO(1, 12, "a28"); RDO(1, 13, "a29"); RDO(1, 14, "a30"); RDO(1, 15, "a31");
-      asm volatile("v_accvgpr_read_b32 %0, a36" : "=v"(lsum));
-    } else {
-      RDO(0, 0, "a48"); RDO(0, 1, "a49"); RDO(0, 2, "a50"); RDO(0, 3, "a51"); RDO(0, 4, "a52"); RDO(0, 5, "a53"); RDO(0, 6, "a54"); RDO(0, 7, "a55");
-      RDO(0, 8, "a56"); RDO(0, 9, "a57"); RDO(0, 10, "a58"); RDO(0, 11, "a59"); RDO(0, 12, "a60"); RDO(0, 13, "a61"); RDO(0, 14, "a62"); RDO(0, 15, "a63");
-      RDO(1, 0, "a64"); RDO(1, 1, "a65"); RDO(1, 2, "a66"); RDO(1, 3, "a67"); RDO(1, 4, "a68"); RDO(1, 5, "a69"); RDO(1, 6, "a70"); RDO(1, 7, "a71");
-      RDO(1, 8, "a72"); RDO(1, 9, "a73"); RDO(1, 10, "a74"); RDO(1, 11, "a75"); RDO(1, 12, "a76"); RDO(1, 13, "a77"); RDO(1, 14, "a78"); RDO(1, 15, "a79");
-      asm volatile("v_accvgpr_read_b32 %0, a84" : "=v"(lsum));
-    }
-#undef RDO
-    const float inv = 1.0f / lsum;   // row 72 (hi = 0) / 76 (hi = 1) of the Vt image: sum_k P[k][q]
+    if (blk == 0) FLASH64_W64_READ_O_A(o, lsum);
+    else FLASH64_W64_READ_O_B(o, lsum);
+    const float inv = 1.0f / lsum;
     const int qs = q0 + 32 * blk + l31;
     bf16_t* orow = p.out + ((int64_t)b * p.q_len + (qs < p.q_len ? qs : p.q_len - 1)) * p.out_stride + h * HD + 8 * hi;
 #pragma unroll
@@ -263,18 +199,11 @@ int launch_flash_attn_d64_w64(const bf16_t* q, int64_t q_stride, const bf16_t* l
   const int64_t nblk = (int64_t)p.nqb * batch * heads;
   if (nblk > 0x7fffffff || (int64_t)kv_pad * HD * 2 >= 0x7fffffff) return VSYS_ERR_SHAPE;
   const size_t lds = (size_t)W64_STAGES * KV_STAGE;   // 81920
-  static std::atomic<unsigned long long> attr_seen{0};
-  for (DeviceOnce once(attr_seen); once.todo(); once.done()) {
-    (void)hipFuncSetAttribute((const void*)flash_attn_d64_w64_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)flash_attn_d64_w64_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)flash_attn_d64_w64_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  switch (var) {   // (named in the order 1, 4, 5 they have always been instantiated in: the statements' labels count the functions)
+    default: return w64::launch<flash_attn_d64_w64_kernel<1>>((unsigned)nblk, lds, stream, p);
+    case 4: return w64::launch<flash_attn_d64_w64_kernel<4>>((unsigned)nblk, lds, stream, p);
+    case 5: return k_bound > 0.f ? w64::launch<flash_attn_d64_w64_kernel<5>>((unsigned)nblk, lds, stream, p) : VSYS_ERR_ARG;
   }
-  if (var == 5) {
-    if (!(k_bound > 0.f)) return VSYS_ERR_ARG;
-    hipLaunchKernelGGL(flash_attn_d64_w64_kernel<5>, dim3((unsigned)nblk), dim3(256), lds, stream, p);
-  } else if (var == 4) hipLaunchKernelGGL(flash_attn_d64_w64_kernel<4>, dim3((unsigned)nblk), dim3(256), lds, stream, p);
-  else hipLaunchKernelGGL(flash_attn_d64_w64_kernel<1>, dim3((unsigned)nblk), dim3(256), lds, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
 }
 
 }  // namespace vsys

@@ -10,19 +10,25 @@
 // allocation and instruction placement (csrc/gen/flash72_gen.py -> flash72_w64_asm.inc): O, Q and the K / Vt fragments live in
 // a[0:223], S / P / the running max in v[0:209]; the C++ around it only computes addresses and the Q fragments (prologue) and
 // normalises / stores O (epilogue).  The statement lists every register it owns as a clobber; nothing else in this kernel uses
-// the accumulator file (tests/test_build_resources.py: no v_accvgpr outside the asm statements, no scratch).
-#include "common.h"
-#include "vsys_internal.h"
-
-#include "flash72_w64_asm.inc"
+// the accumulator file (tests/test_build_resources.py: no accumulator-file move outside the asm statements, no scratch).
+//
+// The register map (Q into / O out of the accumulator file, the statements' operand names) comes from the generator with the
+// streams: FLASH72_W64_WRITE_Q_*, _READ_O_* and FLASH72_W64[P]_OPERANDS[_S] in flash72_w64_map.inc.  The variables a statement
+// reads carry its operand names (the operand lists bind by name).  Descriptors, fragment addressing, the row bound and the launch
+// are flash_w64.h, shared with attention64_w64.hip.  The LDS-DMA lane addressing, the RMS-norm Q fragments and the O store stand
+// in each kernel: as shared inline functions they did not compile to the instruction stream they have here (flash_w64.h).
+#include "flash_w64.h"
 
 namespace vsys {
 namespace {
 
-constexpr int HD = 72, HD_ROWS = 96, KROW = 144, VROW = 128;
+using w64::VROW;
+using w64::make_rsrc;
+using w64::u32x4;
+constexpr int HD = 72, HD_ROWS = 96, KROW = 144;
 constexpr int K_TILE_BYTES = 64 * KROW;                   // 9216
 constexpr int KV_STAGE = K_TILE_BYTES + HD_ROWS * VROW;   // 21504
-constexpr int W64_STAGES = 4;
+constexpr int W64_STAGES = w64::STAGES;
 
 struct FlashW64Params {
   const bf16_t* q; int64_t q_stride;
@@ -38,18 +44,6 @@ struct FlashW64Params {
   float k_bound;
   unsigned long long* dbg;   // lab variant 7: per wave 8 s_memtime stamps
 };
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ u32x4 make_rsrc(const void* base, unsigned bytes) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-  u32x4 r;
-  r.x = __builtin_amdgcn_readfirstlane((unsigned)a);
-  r.y = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);
-  r.z = __builtin_amdgcn_readfirstlane(bytes);
-  r.w = 0x00020000u;
-  return r;
-}
 
 // VAR: placement variant of the LDS-DMA pieces inside the tile loop (flash72_gen.py body()); same arithmetic, same bits
 template <int VAR>
@@ -71,34 +65,33 @@ __global__ __launch_bounds__(256, 1) void flash_attn_d72_w64_kernel(FlashW64Para
   const bf16_t* kbase = p.kp + (int64_t)bh * p.kv_pad * HD;
   const bf16_t* vbase = p.vt + (int64_t)bh * HD_ROWS * p.kv_pad;
   const unsigned kbytes = (unsigned)(p.kv_pad * HD * 2), vbytes = (unsigned)(HD_ROWS * p.kv_pad * 2);
-  const u32x4 rsrc_k = make_rsrc(kbase, kbytes), rsrc_v = make_rsrc(vbase, vbytes);
+  const u32x4 rk = make_rsrc(kbase, kbytes), rv = make_rsrc(vbase, vbytes);
   const bool s4k = wave_u == 0;
   const int s4j = wave_u == 1 ? 8 : 9;
-  const u32x4 rsrc_4 = make_rsrc(s4k ? (const void*)kbase : (const void*)vbase, s4k ? kbytes : vbytes);
-  const int k_voff = lane * 16;
+  const u32x4 r4 = make_rsrc(s4k ? (const void*)kbase : (const void*)vbase, s4k ? kbytes : vbytes);
+  const int kvo = lane * 16;
   const int v_voff0 = (lane >> 3) * p.kv_pad * 2 + (((lane & 7) ^ (lane >> 4)) << 4);
-  const int v_voff = v_voff0 ^ ((wave_u & 1) << 6);
-  const int voff_4 = s4k ? k_voff : (v_voff0 ^ ((s4j & 1) << 6));
+  const int vvo = v_voff0 ^ ((wave_u & 1) << 6);
+  const int v4o = s4k ? kvo : (v_voff0 ^ ((s4j & 1) << 6));
   const int wl = wave_u * 1024;
   const int sv0 = wave_u * 8 * p.kv_pad * 2, sv1 = (wave_u + 4) * 8 * p.kv_pad * 2;
   const int s4 = s4k ? 8 * 1024 : s4j * 8 * p.kv_pad * 2, st4 = s4k ? K_TILE_BYTES : 128;
   const int l4 = s4k ? 8 * 1024 : K_TILE_BYTES + s4j * 1024;
-  const int lb = (int)(unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)smem;   // LDS address of the ring
-  const int ntiles = (p.kv_len + 63) >> 6;
-  const int lim = p.kv_len - (ntiles - 1) * 64 - 16 * hi;
+  const int lb = w64::lds_base(smem);   // LDS address of the ring
+  const int nt = (p.kv_len + 63) >> 6;
+  const int lim = p.kv_len - (nt - 1) * 64 - 16 * hi;
 
   // rows 80..95 of every stage's Vt image: MFMA padding the DMA never writes
   for (int u = tid; u < W64_STAGES * 128; u += 256)
     *reinterpret_cast<uint4*>(smem + (u >> 7) * KV_STAGE + K_TILE_BYTES + 80 * VROW + (u & 127) * 16) = make_uint4(0, 0, 0, 0);
 
   // ---- fragment read offsets inside a stage
-  const int krow = 16 * ((l31 >> 2) & 1) + 4 * (l31 >> 3) + (l31 & 3);   // MFMA row i <-> key: a lane's 16 accumulators are 16 consecutive keys
-  const int kfa = krow * KROW + 16 * hi;
-  const int v_roff = K_TILE_BYTES + l31 * VROW + (((2 * hi) ^ ((l31 >> 1) & 7)) << 4);
-  const int vfa0 = v_roff ^ (0 << 4), vfa1 = v_roff ^ (1 << 4), vfa2 = v_roff ^ (4 << 4), vfa3 = v_roff ^ (5 << 4);
+  const int kfa = w64::frag_krow(l31) * KROW + 16 * hi;
+  const w64::VtFrag vf = w64::vt_frag<K_TILE_BYTES>(l31, hi);
+  const int vfa0 = vf.vfa0, vfa1 = vf.vfa1, vfa2 = vf.vfa2, vfa3 = vf.vfa3;
 
   // ---- Q fragments of the two 32-row blocks (B operand: lane holds Q[row][16c + 8hi .. +8], c = 0..4, d >= 72 -> 0), RMS-normed
-  unsigned qw[2][20];
+  uint4 qw[2][5];
   float nmv[2] = {0.f, 0.f};   // VAR 5: -(row bound) of this lane's query row in block A / B
 #pragma unroll
   for (int blk = 0; blk < 2; ++blk) {
@@ -133,89 +126,33 @@ __global__ __launch_bounds__(256, 1) void flash_attn_d72_w64_kernel(FlashW64Para
         }
       }
     }
-    if constexpr (VAR == 5) {
-      float qn2 = 0.f;
+    if constexpr (VAR == 5) nmv[blk] = w64::neg_row_bound<5>(x, p.k_bound);
 #pragma unroll
-      for (int c = 0; c < 5; ++c)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) qn2 += x[c][e] * x[c][e];
-      qn2 += __shfl_xor(qn2, 32, 64);
-      nmv[blk] = -(sqrtf(qn2) * p.k_bound * 1.015625f);
-    }
-#pragma unroll
-    for (int c = 0; c < 5; ++c) {
-      const uint4 pk = pack8(x[c]);
-      qw[blk][4 * c + 0] = pk.x; qw[blk][4 * c + 1] = pk.y; qw[blk][4 * c + 2] = pk.z; qw[blk][4 * c + 3] = pk.w;
-    }
+    for (int c = 0; c < 5; ++c) qw[blk][c] = pack8(x[c]);
   }
-  // Q -> a[96:135]
-#define QW(b_, i_) "v"(qw[b_][i_])
-  asm volatile(
-      "v_accvgpr_write_b32 a96, %0\n\tv_accvgpr_write_b32 a97, %1\n\tv_accvgpr_write_b32 a98, %2\n\tv_accvgpr_write_b32 a99, %3\n\t"
-      "v_accvgpr_write_b32 a100, %4\n\tv_accvgpr_write_b32 a101, %5\n\tv_accvgpr_write_b32 a102, %6\n\tv_accvgpr_write_b32 a103, %7\n\t"
-      "v_accvgpr_write_b32 a104, %8\n\tv_accvgpr_write_b32 a105, %9\n\tv_accvgpr_write_b32 a106, %10\n\tv_accvgpr_write_b32 a107, %11\n\t"
-      "v_accvgpr_write_b32 a108, %12\n\tv_accvgpr_write_b32 a109, %13\n\tv_accvgpr_write_b32 a110, %14\n\tv_accvgpr_write_b32 a111, %15\n\t"
-      "v_accvgpr_write_b32 a112, %16\n\tv_accvgpr_write_b32 a113, %17\n\tv_accvgpr_write_b32 a114, %18\n\tv_accvgpr_write_b32 a115, %19\n\t"
-      :
-      : QW(0, 0), QW(0, 1), QW(0, 2), QW(0, 3), QW(0, 4), QW(0, 5), QW(0, 6), QW(0, 7), QW(0, 8), QW(0, 9), QW(0, 10), QW(0, 11),
-        QW(0, 12), QW(0, 13), QW(0, 14), QW(0, 15), QW(0, 16), QW(0, 17), QW(0, 18), QW(0, 19)
-      : "a96", "a97", "a98", "a99", "a100", "a101", "a102", "a103", "a104", "a105", "a106", "a107", "a108", "a109", "a110", "a111",
-        "a112", "a113", "a114", "a115");
-  asm volatile(
-      "v_accvgpr_write_b32 a116, %0\n\tv_accvgpr_write_b32 a117, %1\n\tv_accvgpr_write_b32 a118, %2\n\tv_accvgpr_write_b32 a119, %3\n\t"
-      "v_accvgpr_write_b32 a120, %4\n\tv_accvgpr_write_b32 a121, %5\n\tv_accvgpr_write_b32 a122, %6\n\tv_accvgpr_write_b32 a123, %7\n\t"
-      "v_accvgpr_write_b32 a124, %8\n\tv_accvgpr_write_b32 a125, %9\n\tv_accvgpr_write_b32 a126, %10\n\tv_accvgpr_write_b32 a127, %11\n\t"
-      "v_accvgpr_write_b32 a128, %12\n\tv_accvgpr_write_b32 a129, %13\n\tv_accvgpr_write_b32 a130, %14\n\tv_accvgpr_write_b32 a131, %15\n\t"
-      "v_accvgpr_write_b32 a132, %16\n\tv_accvgpr_write_b32 a133, %17\n\tv_accvgpr_write_b32 a134, %18\n\tv_accvgpr_write_b32 a135, %19\n\t"
-      "s_nop 1\n\t"
-      :
-      : QW(1, 0), QW(1, 1), QW(1, 2), QW(1, 3), QW(1, 4), QW(1, 5), QW(1, 6), QW(1, 7), QW(1, 8), QW(1, 9), QW(1, 10), QW(1, 11),
-        QW(1, 12), QW(1, 13), QW(1, 14), QW(1, 15), QW(1, 16), QW(1, 17), QW(1, 18), QW(1, 19)
-      : "a116", "a117", "a118", "a119", "a120", "a121", "a122", "a123", "a124", "a125", "a126", "a127", "a128", "a129", "a130", "a131",
-        "a132", "a133", "a134", "a135");
-#undef QW
+  FLASH72_W64_WRITE_Q_A(qw[0]);
+  FLASH72_W64_WRITE_Q_B(qw[1]);
+  const float nma = nmv[0], nmb = nmv[1];
 
   // ---- the tile loop
-#define W64_LOOP(TEXT_)                                                                                                          \
-  asm volatile(TEXT_                                                                                                             \
-               :                                                                                                                 \
-               : [rk] "s"(rsrc_k), [rv] "s"(rsrc_v), [r4] "s"(rsrc_4), [wl] "s"(wl), [sv0] "s"(sv0), [sv1] "s"(sv1), [s4] "s"(s4), \
-                 [st4] "s"(st4), [l4] "s"(l4), [lb] "s"(lb), [nt] "s"(ntiles), [lim] "v"(lim), [kvo] "v"(k_voff), [vvo] "v"(v_voff), \
-                 [v4o] "v"(voff_4), [kfa] "v"(kfa), [vfa0] "v"(vfa0), [vfa1] "v"(vfa1), [vfa2] "v"(vfa2), [vfa3] "v"(vfa3)       \
-               : FLASH72_W64_CLOBBERS)
+#define W64_LOOP(TEXT_) asm volatile(TEXT_ : : FLASH72_W64_OPERANDS : FLASH72_W64_CLOBBERS)
+#define W64_STAMPS [t0] "=s"(stamp[1]), [t1] "=s"(stamp[2]), [t2] "=s"(stamp[3])
   if constexpr (VAR == 0) W64_LOOP(FLASH72_W64_ASM_V0);
-  else if constexpr (VAR == 5) {   // no running max: the row bounds ride in as the -m splat
-    asm volatile(FLASH72_W64_ASM_V5
-                 :
-                 : [rk] "s"(rsrc_k), [rv] "s"(rsrc_v), [r4] "s"(rsrc_4), [wl] "s"(wl), [sv0] "s"(sv0), [sv1] "s"(sv1), [s4] "s"(s4),
-                   [st4] "s"(st4), [l4] "s"(l4), [lb] "s"(lb), [nt] "s"(ntiles), [lim] "v"(lim), [kvo] "v"(k_voff), [vvo] "v"(v_voff),
-                   [v4o] "v"(voff_4), [kfa] "v"(kfa), [vfa0] "v"(vfa0), [vfa1] "v"(vfa1), [vfa2] "v"(vfa2), [vfa3] "v"(vfa3),
-                   [nma] "v"(nmv[0]), [nmb] "v"(nmv[1])
-                 : FLASH72_W64_CLOBBERS);
-  }
+  else if constexpr (VAR == 5)   // no running max: the row bounds ride in as the -m splat
+    asm volatile(FLASH72_W64_ASM_V5 : : FLASH72_W64_OPERANDS_S : FLASH72_W64_CLOBBERS);
   else if constexpr (VAR == 1) W64_LOOP(FLASH72_W64_ASM_V1);
   else if constexpr (VAR == 3) W64_LOOP(FLASH72_W64_ASM_V3);
 #ifdef VSYS_LAB
   else if constexpr (VAR == 7) {
-    asm volatile(FLASH72_W64_ASM_V7
-                 : [t0] "=s"(stamp[1]), [t1] "=s"(stamp[2]), [t2] "=s"(stamp[3])
-                 : [rk] "s"(rsrc_k), [rv] "s"(rsrc_v), [r4] "s"(rsrc_4), [wl] "s"(wl), [sv0] "s"(sv0), [sv1] "s"(sv1), [s4] "s"(s4),
-                   [st4] "s"(st4), [l4] "s"(l4), [lb] "s"(lb), [nt] "s"(ntiles), [lim] "v"(lim), [kvo] "v"(k_voff), [vvo] "v"(v_voff),
-                   [v4o] "v"(voff_4), [kfa] "v"(kfa), [vfa0] "v"(vfa0), [vfa1] "v"(vfa1), [vfa2] "v"(vfa2), [vfa3] "v"(vfa3)
-                 : FLASH72_W64_CLOBBERS);
+    asm volatile(FLASH72_W64_ASM_V7 : W64_STAMPS : FLASH72_W64_OPERANDS : FLASH72_W64_CLOBBERS);
     stamp[4] = __builtin_amdgcn_s_memtime();
   }
-  else if constexpr (VAR == 10) {   // per-phase cycle sums of the loop tiles: X, wait + barrier, Y
-    asm volatile(FLASH72_W64_ASM_V10
-                 : [t0] "=s"(stamp[1]), [t1] "=s"(stamp[2]), [t2] "=s"(stamp[3])
-                 : [rk] "s"(rsrc_k), [rv] "s"(rsrc_v), [r4] "s"(rsrc_4), [wl] "s"(wl), [sv0] "s"(sv0), [sv1] "s"(sv1), [s4] "s"(s4),
-                   [st4] "s"(st4), [l4] "s"(l4), [lb] "s"(lb), [nt] "s"(ntiles), [lim] "v"(lim), [kvo] "v"(k_voff), [vvo] "v"(v_voff),
-                   [v4o] "v"(voff_4), [kfa] "v"(kfa), [vfa0] "v"(vfa0), [vfa1] "v"(vfa1), [vfa2] "v"(vfa2), [vfa3] "v"(vfa3)
-                 : FLASH72_W64_CLOBBERS_PHASE);
-  }
+  else if constexpr (VAR == 10)   // per-phase cycle sums of the loop tiles: X, wait + barrier, Y
+    asm volatile(FLASH72_W64_ASM_V10 : W64_STAMPS : FLASH72_W64_OPERANDS : FLASH72_W64_CLOBBERS_PHASE);
   else if constexpr (VAR == 8) W64_LOOP(FLASH72_W64_ASM_V8);
   else if constexpr (VAR == 9) W64_LOOP(FLASH72_W64_ASM_V9);
 #endif
+#undef W64_STAMPS
 #undef W64_LOOP
 
   // ---- epilogue: O[q][d] = O^T[d][q] / l ; lane holds d = 32dt + (r&3) + 8(r>>2) + 4hi; 16-byte stores through
@@ -223,23 +160,8 @@ __global__ __launch_bounds__(256, 1) void flash_attn_d72_w64_kernel(FlashW64Para
 #pragma unroll
   for (int blk = 0; blk < 2; ++blk) {
     float o[3][16];
-#define RDO(dt_, r_, reg_) asm volatile("v_accvgpr_read_b32 %0, " reg_ : "=v"(o[dt_][r_]))
-    if (blk == 0) {
-      RDO(0, 0, "a0"); RDO(0, 1, "a1"); RDO(0, 2, "a2"); RDO(0, 3, "a3"); RDO(0, 4, "a4"); RDO(0, 5, "a5"); RDO(0, 6, "a6"); RDO(0, 7, "a7");
-      RDO(0, 8, "a8"); RDO(0, 9, "a9"); RDO(0, 10, "a10"); RDO(0, 11, "a11"); RDO(0, 12, "a12"); RDO(0, 13, "a13"); RDO(0, 14, "a14"); RDO(0, 15, "a15");
-      RDO(1, 0, "a16"); RDO(1, 1, "a17"); RDO(1, 2, "a18"); RDO(1, 3, "a19"); RDO(1, 4, "a20"); RDO(1, 5, "a21"); RDO(1, 6, "a22"); RDO(1, 7, "a23");
-      RDO(1, 8, "a24"); RDO(1, 9, "a25"); RDO(1, 10, "a26"); RDO(1, 11, "a27"); RDO(1, 12, "a28"); RDO(1, 13, "a29"); RDO(1, 14, "a30"); RDO(1, 15, "a31");
-      RDO(2, 0, "a32"); RDO(2, 1, "a33"); RDO(2, 2, "a34"); RDO(2, 3, "a35"); RDO(2, 4, "a36"); RDO(2, 5, "a37"); RDO(2, 6, "a38"); RDO(2, 7, "a39");
-      RDO(2, 8, "a40"); RDO(2, 9, "a41"); RDO(2, 10, "a42"); RDO(2, 11, "a43"); RDO(2, 12, "a44"); RDO(2, 13, "a45"); RDO(2, 14, "a46"); RDO(2, 15, "a47");
-    } else {
-      RDO(0, 0, "a48"); RDO(0, 1, "a49"); RDO(0, 2, "a50"); RDO(0, 3, "a51"); RDO(0, 4, "a52"); RDO(0, 5, "a53"); RDO(0, 6, "a54"); RDO(0, 7, "a55");
-      RDO(0, 8, "a56"); RDO(0, 9, "a57"); RDO(0, 10, "a58"); RDO(0, 11, "a59"); RDO(0, 12, "a60"); RDO(0, 13, "a61"); RDO(0, 14, "a62"); RDO(0, 15, "a63");
-      RDO(1, 0, "a64"); RDO(1, 1, "a65"); RDO(1, 2, "a66"); RDO(1, 3, "a67"); RDO(1, 4, "a68"); RDO(1, 5, "a69"); RDO(1, 6, "a70"); RDO(1, 7, "a71");
-      RDO(1, 8, "a72"); RDO(1, 9, "a73"); RDO(1, 10, "a74"); RDO(1, 11, "a75"); RDO(1, 12, "a76"); RDO(1, 13, "a77"); RDO(1, 14, "a78"); RDO(1, 15, "a79");
-      RDO(2, 0, "a80"); RDO(2, 1, "a81"); RDO(2, 2, "a82"); RDO(2, 3, "a83"); RDO(2, 4, "a84"); RDO(2, 5, "a85"); RDO(2, 6, "a86"); RDO(2, 7, "a87");
-      RDO(2, 8, "a88"); RDO(2, 9, "a89"); RDO(2, 10, "a90"); RDO(2, 11, "a91"); RDO(2, 12, "a92"); RDO(2, 13, "a93"); RDO(2, 14, "a94"); RDO(2, 15, "a95");
-    }
-#undef RDO
+    if (blk == 0) FLASH72_W64_READ_O_A(o);
+    else FLASH72_W64_READ_O_B(o);
     const float inv = 1.0f / o[2][4];   // d = 72 (hi = 0) / 76 (hi = 1): the ones rows of Vt, i.e. sum_k P[k][q]
     const int qs = q0 + 32 * blk + l31;
     bf16_t* orow = p.out + ((int64_t)b * p.q_len + (qs < p.q_len ? qs : p.q_len - 1)) * p.out_stride + h * HD + 8 * hi;
@@ -309,22 +231,21 @@ __global__ __launch_bounds__(256, 1) void flash_attn_d72_w64p_kernel(FlashW64Par
   const unsigned kbytes = (unsigned)(p.kv_pad * HD * 2), vbytes = (unsigned)(HD_ROWS * p.kv_pad * 2);
   const bool s4k = wave_u == 0;
   const int s4j = wave_u == 1 ? 8 : 9;
-  const int k_voff = lane * 16;
+  const int kvo = lane * 16;
   const int v_voff0 = (lane >> 3) * p.kv_pad * 2 + (((lane & 7) ^ (lane >> 4)) << 4);
-  const int v_voff = v_voff0 ^ ((wave_u & 1) << 6);
-  const int voff_4 = s4k ? k_voff : (v_voff0 ^ ((s4j & 1) << 6));
+  const int vvo = v_voff0 ^ ((wave_u & 1) << 6);
+  const int v4o = s4k ? kvo : (v_voff0 ^ ((s4j & 1) << 6));
   const int wl = wave_u * 1024, kvp2 = p.kv_pad * 2;
   const int s4 = s4k ? 8 * 1024 : s4j * 8 * p.kv_pad * 2, st4 = s4k ? K_TILE_BYTES : 128;
   const int l4 = s4k ? 8 * 1024 : K_TILE_BYTES + s4j * 1024;
-  const int lb = (int)(unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)smem;
+  const int lb = w64::lds_base(smem);
   const int qlds = lb + W64_STAGES * KV_STAGE + wave_u * W64P_QIMG;
-  const int ntiles = p.kv_len >> 6;   // whole tiles (flash_w64p_supports)
+  const int nt = p.kv_len >> 6;   // whole tiles (flash_w64p_supports)
   for (int u = tid; u < W64_STAGES * 128; u += 256)
     *reinterpret_cast<uint4*>(smem + (u >> 7) * KV_STAGE + K_TILE_BYTES + 80 * VROW + (u & 127) * 16) = make_uint4(0, 0, 0, 0);
-  const int krow = 16 * ((l31 >> 2) & 1) + 4 * (l31 >> 3) + (l31 & 3);
-  const int kfa = krow * KROW + 16 * hi;
-  const int v_roff = K_TILE_BYTES + l31 * VROW + (((2 * hi) ^ ((l31 >> 1) & 7)) << 4);
-  const int vfa0 = v_roff ^ (0 << 4), vfa1 = v_roff ^ (1 << 4), vfa2 = v_roff ^ (4 << 4), vfa3 = v_roff ^ (5 << 4);
+  const int kfa = w64::frag_krow(l31) * KROW + 16 * hi;
+  const w64::VtFrag vf = w64::vt_frag<K_TILE_BYTES>(l31, hi);
+  const int vfa0 = vf.vfa0, vfa1 = vf.vfa1, vfa2 = vf.vfa2, vfa3 = vf.vfa3;
 
   // what an item needs from the outside: K / Vt of its (batch, head), its Q rows (descriptor over the batch's rows of head h + the
   // lane's row offset), its output rows
@@ -333,7 +254,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_d72_w64p_kernel(FlashW64Par
     const int bh = item_bh(it), b = bh / p.heads, h = bh - b * p.heads;
     return make_rsrc(p.q + (int64_t)b * p.q_len * p.q_stride + h * HD, (unsigned)((int64_t)p.q_len * p.q_stride * 2));
   };
-  auto q_voff = [&](int it) {   // this lane's row of the wave's 64 (clamped at the end of the sequence)
+  auto q_row_voff = [&](int it) {   // this lane's row of the wave's 64 (clamped at the end of the sequence)
     const int qb = it - item_bh(it) * p.nqb;
     int r = qb * 256 + wave * 64 + lane;
     r = r < p.q_len ? r : p.q_len - 1;
@@ -351,19 +272,19 @@ __global__ __launch_bounds__(256, 1) void flash_attn_d72_w64p_kernel(FlashW64Par
     const int bq = bh / p.heads, hq = bh - bq * p.heads;
     const auto rq = __builtin_amdgcn_make_buffer_rsrc((void*)(p.q + (int64_t)bq * p.q_len * p.q_stride + hq * HD), 0,
                                                       (int)((int64_t)p.q_len * p.q_stride * 2), 0x00020000);
-    const int qv = q_voff(i0);
+    const int qv = q_row_voff(i0);
 #pragma unroll
     for (int pc = 0; pc < 9; ++pc)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rq, (lds_ptr_t)(smem + W64_STAGES * KV_STAGE + wave_u * W64P_QIMG + pc * 1024), 16, qv, pc * 16, 0, 0);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       char* st = smem + t * KV_STAGE;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_ptr_t)(st + wl), 16, k_voff, t * K_TILE_BYTES + wl, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_ptr_t)(st + wl + 4096), 16, k_voff, t * K_TILE_BYTES + wl + 4096, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_ptr_t)(st + K_TILE_BYTES + wl), 16, v_voff, wave_u * 8 * kvp2 + t * 128, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_ptr_t)(st + K_TILE_BYTES + wl + 4096), 16, v_voff, (wave_u + 4) * 8 * kvp2 + t * 128, 0, 0);
-      if (s4k) __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_ptr_t)(st + l4), 16, voff_4, s4 + t * st4, 0, 0);
-      else __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_ptr_t)(st + l4), 16, voff_4, s4 + t * st4, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_ptr_t)(st + wl), 16, kvo, t * K_TILE_BYTES + wl, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_ptr_t)(st + wl + 4096), 16, kvo, t * K_TILE_BYTES + wl + 4096, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_ptr_t)(st + K_TILE_BYTES + wl), 16, vvo, wave_u * 8 * kvp2 + t * 128, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_ptr_t)(st + K_TILE_BYTES + wl + 4096), 16, vvo, (wave_u + 4) * 8 * kvp2 + t * 128, 0, 0);
+      if (s4k) __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_ptr_t)(st + l4), 16, v4o, s4 + t * st4, 0, 0);
+      else __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_ptr_t)(st + l4), 16, v4o, s4 + t * st4, 0, 0);
     }
   }
 
@@ -386,7 +307,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_d72_w64p_kernel(FlashW64Par
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's Q image has landed (nobody else touches it)
     if constexpr (STAMP) t1 = __builtin_amdgcn_s_memtime();
     // ---- Q fragments from the image [chunk][row]: lane holds Q[row][16c + 8hi .. +8] = chunk 2c + hi of row 32 blk + l31
-    unsigned qw[2][20];
+    uint4 qw[2][5];
     float nmv[2] = {0.f, 0.f};
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
@@ -419,47 +340,14 @@ __global__ __launch_bounds__(256, 1) void flash_attn_d72_w64p_kernel(FlashW64Par
           }
         }
       }
-      if constexpr (SM) {
-        float qn2 = 0.f;
+      if constexpr (SM) nmv[blk] = w64::neg_row_bound<5>(x, p.k_bound);
 #pragma unroll
-        for (int c = 0; c < 5; ++c)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) qn2 += x[c][e] * x[c][e];
-        qn2 += __shfl_xor(qn2, 32, 64);
-        nmv[blk] = -(sqrtf(qn2) * p.k_bound * 1.015625f);
-      }
-#pragma unroll
-      for (int c = 0; c < 5; ++c) {
-        const uint4 pk = pack8(x[c]);
-        qw[blk][4 * c + 0] = pk.x; qw[blk][4 * c + 1] = pk.y; qw[blk][4 * c + 2] = pk.z; qw[blk][4 * c + 3] = pk.w;
-      }
+      for (int c = 0; c < 5; ++c) qw[blk][c] = pack8(x[c]);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the image reads are done before the tile loop overwrites it with the next item's rows
-#define QW(b_, i_) "v"(qw[b_][i_])
-    asm volatile(
-        "v_accvgpr_write_b32 a96, %0\n\tv_accvgpr_write_b32 a97, %1\n\tv_accvgpr_write_b32 a98, %2\n\tv_accvgpr_write_b32 a99, %3\n\t"
-        "v_accvgpr_write_b32 a100, %4\n\tv_accvgpr_write_b32 a101, %5\n\tv_accvgpr_write_b32 a102, %6\n\tv_accvgpr_write_b32 a103, %7\n\t"
-        "v_accvgpr_write_b32 a104, %8\n\tv_accvgpr_write_b32 a105, %9\n\tv_accvgpr_write_b32 a106, %10\n\tv_accvgpr_write_b32 a107, %11\n\t"
-        "v_accvgpr_write_b32 a108, %12\n\tv_accvgpr_write_b32 a109, %13\n\tv_accvgpr_write_b32 a110, %14\n\tv_accvgpr_write_b32 a111, %15\n\t"
-        "v_accvgpr_write_b32 a112, %16\n\tv_accvgpr_write_b32 a113, %17\n\tv_accvgpr_write_b32 a114, %18\n\tv_accvgpr_write_b32 a115, %19\n\t"
-        :
-        : QW(0, 0), QW(0, 1), QW(0, 2), QW(0, 3), QW(0, 4), QW(0, 5), QW(0, 6), QW(0, 7), QW(0, 8), QW(0, 9), QW(0, 10), QW(0, 11),
-          QW(0, 12), QW(0, 13), QW(0, 14), QW(0, 15), QW(0, 16), QW(0, 17), QW(0, 18), QW(0, 19)
-        : "a96", "a97", "a98", "a99", "a100", "a101", "a102", "a103", "a104", "a105", "a106", "a107", "a108", "a109", "a110", "a111",
-          "a112", "a113", "a114", "a115");
-    asm volatile(
-        "v_accvgpr_write_b32 a116, %0\n\tv_accvgpr_write_b32 a117, %1\n\tv_accvgpr_write_b32 a118, %2\n\tv_accvgpr_write_b32 a119, %3\n\t"
-        "v_accvgpr_write_b32 a120, %4\n\tv_accvgpr_write_b32 a121, %5\n\tv_accvgpr_write_b32 a122, %6\n\tv_accvgpr_write_b32 a123, %7\n\t"
-        "v_accvgpr_write_b32 a124, %8\n\tv_accvgpr_write_b32 a125, %9\n\tv_accvgpr_write_b32 a126, %10\n\tv_accvgpr_write_b32 a127, %11\n\t"
-        "v_accvgpr_write_b32 a128, %12\n\tv_accvgpr_write_b32 a129, %13\n\tv_accvgpr_write_b32 a130, %14\n\tv_accvgpr_write_b32 a131, %15\n\t"
-        "v_accvgpr_write_b32 a132, %16\n\tv_accvgpr_write_b32 a133, %17\n\tv_accvgpr_write_b32 a134, %18\n\tv_accvgpr_write_b32 a135, %19\n\t"
-        "s_nop 1\n\t"
-        :
-        : QW(1, 0), QW(1, 1), QW(1, 2), QW(1, 3), QW(1, 4), QW(1, 5), QW(1, 6), QW(1, 7), QW(1, 8), QW(1, 9), QW(1, 10), QW(1, 11),
-          QW(1, 12), QW(1, 13), QW(1, 14), QW(1, 15), QW(1, 16), QW(1, 17), QW(1, 18), QW(1, 19)
-        : "a116", "a117", "a118", "a119", "a120", "a121", "a122", "a123", "a124", "a125", "a126", "a127", "a128", "a129", "a130", "a131",
-          "a132", "a133", "a134", "a135");
-#undef QW
+    FLASH72_W64_WRITE_Q_A(qw[0]);
+    FLASH72_W64_WRITE_Q_B(qw[1]);
+    const float nma = nmv[0], nmb = nmv[1];
 
     // ---- this item's K / Vt, and what the tail of the loop prefetches for the next one
     const bool has_next = it + istep < i1;
@@ -468,61 +356,28 @@ __global__ __launch_bounds__(256, 1) void flash_attn_d72_w64p_kernel(FlashW64Par
     const unsigned long long kb = uniform_addr(p.kp + (int64_t)bh * p.kv_pad * HD), vb = uniform_addr(p.vt + (int64_t)bh * HD_ROWS * p.kv_pad);
     const unsigned long long kbn = uniform_addr(p.kp + (int64_t)nbh * p.kv_pad * HD), vbn = uniform_addr(p.vt + (int64_t)nbh * HD_ROWS * p.kv_pad);
     const u32x4 rqn = q_rsrc(nit);
-    const int qvo = q_voff(nit);
+    const int qvo = q_row_voff(nit);
     const int hn = __builtin_amdgcn_readfirstlane(has_next ? 1 : 0);
     const int st0 = lb + ring * KV_STAGE, st1 = lb + ((ring + 1) & 3) * KV_STAGE, st2 = lb + ((ring + 2) & 3) * KV_STAGE;
-    ring = (ring + ntiles) & 3;
+    ring = (ring + nt) & 3;
     if constexpr (STAMP) {
       t2 = __builtin_amdgcn_s_memtime();
 #ifdef VSYS_LAB
-      asm volatile(FLASH72_W64P_ASM_STAMP
-                   : [t0] "=s"(ta), [t1] "=s"(tb)
-                   : [kb] "s"(kb), [vb] "s"(vb), [kbn] "s"(kbn), [vbn] "s"(vbn), [rqn] "s"(rqn), [wl] "s"(wl), [kvp2] "s"(kvp2), [hn] "s"(hn),
-                     [s4] "s"(s4), [st4] "s"(st4), [l4] "s"(l4), [lb] "s"(lb), [nt] "s"(ntiles), [qlds] "s"(qlds), [kvo] "v"(k_voff),
-                     [vvo] "v"(v_voff), [v4o] "v"(voff_4), [kfa] "v"(kfa), [vfa0] "v"(vfa0), [vfa1] "v"(vfa1), [vfa2] "v"(vfa2),
-                     [vfa3] "v"(vfa3), [qvo] "v"(qvo), [st0] "s"(st0), [st1] "s"(st1), [st2] "s"(st2)
-                   : FLASH72_W64_CLOBBERS);
+      asm volatile(FLASH72_W64P_ASM_STAMP : [t0] "=s"(ta), [t1] "=s"(tb) : FLASH72_W64P_OPERANDS : FLASH72_W64_CLOBBERS);
 #endif
       t3 = __builtin_amdgcn_s_memtime();
     } else if constexpr (SM)
-    asm volatile(FLASH72_W64P_ASM_S
-                 :
-                 : [kb] "s"(kb), [vb] "s"(vb), [kbn] "s"(kbn), [vbn] "s"(vbn), [rqn] "s"(rqn), [wl] "s"(wl), [kvp2] "s"(kvp2), [hn] "s"(hn),
-                   [s4] "s"(s4), [st4] "s"(st4), [l4] "s"(l4), [lb] "s"(lb), [nt] "s"(ntiles), [qlds] "s"(qlds), [kvo] "v"(k_voff),
-                   [vvo] "v"(v_voff), [v4o] "v"(voff_4), [kfa] "v"(kfa), [vfa0] "v"(vfa0), [vfa1] "v"(vfa1), [vfa2] "v"(vfa2),
-                   [vfa3] "v"(vfa3), [qvo] "v"(qvo), [nma] "v"(nmv[0]), [nmb] "v"(nmv[1]), [st0] "s"(st0), [st1] "s"(st1), [st2] "s"(st2)
-                 : FLASH72_W64_CLOBBERS);
+      asm volatile(FLASH72_W64P_ASM_S : : FLASH72_W64P_OPERANDS_S : FLASH72_W64_CLOBBERS);
     else
-    asm volatile(FLASH72_W64P_ASM
-                 :
-                 : [kb] "s"(kb), [vb] "s"(vb), [kbn] "s"(kbn), [vbn] "s"(vbn), [rqn] "s"(rqn), [wl] "s"(wl), [kvp2] "s"(kvp2), [hn] "s"(hn),
-                   [s4] "s"(s4), [st4] "s"(st4), [l4] "s"(l4), [lb] "s"(lb), [nt] "s"(ntiles), [qlds] "s"(qlds), [kvo] "v"(k_voff),
-                   [vvo] "v"(v_voff), [v4o] "v"(voff_4), [kfa] "v"(kfa), [vfa0] "v"(vfa0), [vfa1] "v"(vfa1), [vfa2] "v"(vfa2),
-                   [vfa3] "v"(vfa3), [qvo] "v"(qvo), [st0] "s"(st0), [st1] "s"(st1), [st2] "s"(st2)
-                 : FLASH72_W64_CLOBBERS);
+      asm volatile(FLASH72_W64P_ASM : : FLASH72_W64P_OPERANDS : FLASH72_W64_CLOBBERS);
 
     // ---- epilogue (as the one-item kernel)
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
       float o[3][16];
-#define RDO(dt_, r_, reg_) asm volatile("v_accvgpr_read_b32 %0, " reg_ : "=v"(o[dt_][r_]))
-      if (blk == 0) {
-        RDO(0, 0, "a0"); RDO(0, 1, "a1"); RDO(0, 2, "a2"); RDO(0, 3, "a3"); RDO(0, 4, "a4"); RDO(0, 5, "a5"); RDO(0, 6, "a6"); RDO(0, 7, "a7");
-        RDO(0, 8, "a8"); RDO(0, 9, "a9"); RDO(0, 10, "a10"); RDO(0, 11, "a11"); RDO(0, 12, "a12"); RDO(0, 13, "a13"); RDO(0, 14, "a14"); RDO(0, 15, "a15");
-        RDO(1, 0, "a16"); RDO(1, 1, "a17"); RDO(1, 2, "a18"); RDO(1, 3, "a19"); RDO(1, 4, "a20"); RDO(1, 5, "a21"); RDO(1, 6, "a22"); RDO(1, 7, "a23");
-        RDO(1, 8, "a24"); RDO(1, 9, "a25"); RDO(1, 10, "a26"); RDO(1, 11, "a27"); RDO(1, 12, "a28"); RDO(1, 13, "a29"); RDO(1, 14, "a30"); RDO(1, 15, "a31");
-        RDO(2, 0, "a32"); RDO(2, 1, "a33"); RDO(2, 2, "a34"); RDO(2, 3, "a35"); RDO(2, 4, "a36"); RDO(2, 5, "a37"); RDO(2, 6, "a38"); RDO(2, 7, "a39");
-        RDO(2, 8, "a40"); RDO(2, 9, "a41"); RDO(2, 10, "a42"); RDO(2, 11, "a43"); RDO(2, 12, "a44"); RDO(2, 13, "a45"); RDO(2, 14, "a46"); RDO(2, 15, "a47");
-      } else {
-        RDO(0, 0, "a48"); RDO(0, 1, "a49"); RDO(0, 2, "a50"); RDO(0, 3, "a51"); RDO(0, 4, "a52"); RDO(0, 5, "a53"); RDO(0, 6, "a54"); RDO(0, 7, "a55");
-        RDO(0, 8, "a56"); RDO(0, 9, "a57"); RDO(0, 10, "a58"); RDO(0, 11, "a59"); RDO(0, 12, "a60"); RDO(0, 13, "a61"); RDO(0, 14, "a62"); RDO(0, 15, "a63");
-        RDO(1, 0, "a64"); RDO(1, 1, "a65"); RDO(1, 2, "a66"); RDO(1, 3, "a67"); RDO(1, 4, "a68"); RDO(1, 5, "a69"); RDO(1, 6, "a70"); RDO(1, 7, "a71");
-        RDO(1, 8, "a72"); RDO(1, 9, "a73"); RDO(1, 10, "a74"); RDO(1, 11, "a75"); RDO(1, 12, "a76"); RDO(1, 13, "a77"); RDO(1, 14, "a78"); RDO(1, 15, "a79");
-        RDO(2, 0, "a80"); RDO(2, 1, "a81"); RDO(2, 2, "a82"); RDO(2, 3, "a83"); RDO(2, 4, "a84"); RDO(2, 5, "a85"); RDO(2, 6, "a86"); RDO(2, 7, "a87");
-        RDO(2, 8, "a88"); RDO(2, 9, "a89"); RDO(2, 10, "a90"); RDO(2, 11, "a91"); RDO(2, 12, "a92"); RDO(2, 13, "a93"); RDO(2, 14, "a94"); RDO(2, 15, "a95");
-      }
-#undef RDO
-      const float inv = 1.0f / o[2][4];
+      if (blk == 0) FLASH72_W64_READ_O_A(o);
+      else FLASH72_W64_READ_O_B(o);
+      const float inv = 1.0f / o[2][4];   // d = 72 (hi = 0) / 76 (hi = 1): the ones rows of Vt, i.e. sum_k P[k][q]
       const int qs = q0 + 32 * blk + l31;
       bf16_t* orow = p.out + ((int64_t)b * p.q_len + (qs < p.q_len ? qs : p.q_len - 1)) * p.out_stride + h * HD + 8 * hi;
 #pragma unroll
@@ -572,13 +427,16 @@ bool flash_w64_supports(int q_len, int kv_len, int kv_pad) {
   return kv_len >= 256 && q_len >= 256;   // >= 4 tiles of 64 keys, at least one full 256-row workgroup
 }
 
-template <int VAR>
-static int launch_w64_t(const FlashW64Params& p, unsigned nblk, size_t lds, hipStream_t stream) {
-  static std::atomic<unsigned long long> attr_seen{0};
-  for (DeviceOnce once(attr_seen); once.todo(); once.done())
-    (void)hipFuncSetAttribute((const void*)flash_attn_d72_w64_kernel<VAR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(flash_attn_d72_w64_kernel<VAR>, dim3(nblk), dim3(256), lds, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
+// what both launchers hand to their kernels (dbg: the lab stamp buffer, or null)
+static FlashW64Params w64_params(const bf16_t* q, int64_t q_stride, const bf16_t* q_norm_w, const bf16_t* kp, const bf16_t* vt, bf16_t* out,
+                                 int64_t out_stride, int heads, int q_len, int kv_len, int kv_pad, float eps, float k_bound,
+                                 unsigned long long* dbg) {
+  FlashW64Params p;
+  p.q = q; p.q_stride = q_stride; p.q_norm_w = q_norm_w; p.kp = kp; p.vt = vt; p.out = out; p.out_stride = out_stride;
+  p.heads = heads; p.q_len = q_len; p.kv_len = kv_len; p.kv_pad = kv_pad; p.eps = eps; p.k_bound = k_bound;
+  p.dbg = dbg;
+  p.nqb = (q_len + 255) / 256;
+  return p;
 }
 
 // persistent form: >= 4 tiles of tile-padded keys, 32-bit Q row offsets
@@ -591,63 +449,49 @@ bool flash_w64p_supports(int q_len, int kv_len, int kv_pad, int64_t q_stride) {
 int launch_flash_attn_d72_w64p(const bf16_t* q, int64_t q_stride, const bf16_t* q_norm_w, const bf16_t* kp, const bf16_t* vt, bf16_t* out,
                                int64_t out_stride, int batch, int heads, int q_len, int kv_len, int kv_pad, float eps, bool stamp,
                                float k_bound, hipStream_t stream) {
-  FlashW64Params p;
-  p.q = q; p.q_stride = q_stride; p.q_norm_w = q_norm_w; p.kp = kp; p.vt = vt; p.out = out; p.out_stride = out_stride;
-  p.heads = heads; p.q_len = q_len; p.kv_len = kv_len; p.kv_pad = kv_pad; p.eps = eps; p.k_bound = k_bound;
-  p.dbg = nullptr;
-  p.nqb = (q_len + 255) / 256;
+  FlashW64Params p = w64_params(q, q_stride, q_norm_w, kp, vt, out, out_stride, heads, q_len, kv_len, kv_pad, eps, k_bound, nullptr);
   const int64_t total = (int64_t)p.nqb * batch * heads;
   if (total > 0x7fffffff) return VSYS_ERR_SHAPE;
   const int ncu = cu_count_this_device();
   const unsigned grid = (unsigned)(total < ncu ? total : ncu);
   const size_t lds = (size_t)W64_STAGES * KV_STAGE + 4 * W64P_QIMG;
-  static std::atomic<unsigned long long> attr_seen{0};
-  for (DeviceOnce once(attr_seen); once.todo(); once.done()) {
-    (void)hipFuncSetAttribute((const void*)flash_attn_d72_w64p_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)flash_attn_d72_w64p_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-#ifdef VSYS_LAB
-    (void)hipFuncSetAttribute((const void*)flash_attn_d72_w64p_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-#endif
-  }
-#ifdef VSYS_LAB
-  if (stamp) {
-    p.dbg = reinterpret_cast<unsigned long long*>(get_lab_debug_buffer());
-    hipLaunchKernelGGL(flash_attn_d72_w64p_kernel<true>, dim3(grid), dim3(256), lds, stream, p, (int)total);
-    return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
-  }
-#endif
+  // (the three forms are named in the order they have always been instantiated in — plain, SM, STAMP: the labels inside the
+  // statements carry the number of the function they are expanded in)
   (void)stamp;
-  if (k_bound > 0.f && q_norm_w != nullptr)
-    hipLaunchKernelGGL((flash_attn_d72_w64p_kernel<false, true>), dim3(grid), dim3(256), lds, stream, p, (int)total);
-  else
-    hipLaunchKernelGGL(flash_attn_d72_w64p_kernel<false>, dim3(grid), dim3(256), lds, stream, p, (int)total);
-  return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
+#ifdef VSYS_LAB
+  if (!stamp)
+#endif
+    return !(k_bound > 0.f && q_norm_w != nullptr) ? w64::launch<flash_attn_d72_w64p_kernel<false>>(grid, lds, stream, p, (int)total)
+                                                    : w64::launch<flash_attn_d72_w64p_kernel<false, true>>(grid, lds, stream, p, (int)total);
+#ifdef VSYS_LAB
+  p.dbg = reinterpret_cast<unsigned long long*>(get_lab_debug_buffer());
+  return w64::launch<flash_attn_d72_w64p_kernel<true>>(grid, lds, stream, p, (int)total);
+#endif
 }
 
 int launch_flash_attn_d72_w64(const bf16_t* q, int64_t q_stride, const bf16_t* q_norm_w, const bf16_t* kp, const bf16_t* vt, bf16_t* out,
                               int64_t out_stride, int batch, int heads, int q_len, int kv_len, int kv_pad, float eps, int var,
                               float k_bound, hipStream_t stream) {
-  FlashW64Params p;
-  p.q = q; p.q_stride = q_stride; p.q_norm_w = q_norm_w; p.kp = kp; p.vt = vt; p.out = out; p.out_stride = out_stride;
-  p.heads = heads; p.q_len = q_len; p.kv_len = kv_len; p.kv_pad = kv_pad; p.eps = eps; p.k_bound = k_bound;
-  p.dbg = reinterpret_cast<unsigned long long*>(get_lab_debug_buffer());
-  p.nqb = (q_len + 255) / 256;
+  const FlashW64Params p = w64_params(q, q_stride, q_norm_w, kp, vt, out, out_stride, heads, q_len, kv_len, kv_pad, eps, k_bound,
+                                      reinterpret_cast<unsigned long long*>(get_lab_debug_buffer()));
   const int64_t nblk = (int64_t)p.nqb * batch * heads;
   if (nblk > 0x7fffffff) return VSYS_ERR_SHAPE;
   const size_t lds = (size_t)W64_STAGES * KV_STAGE;
+#define W64_CASE(VAR_) w64::launch<flash_attn_d72_w64_kernel<VAR_>>((unsigned)nblk, lds, stream, p)
   switch (var) {
-    case 0: return launch_w64_t<0>(p, (unsigned)nblk, lds, stream);
-    case 1: return launch_w64_t<1>(p, (unsigned)nblk, lds, stream);
-    case 3: return launch_w64_t<3>(p, (unsigned)nblk, lds, stream);
-    case 5: return k_bound > 0.f && q_norm_w != nullptr ? launch_w64_t<5>(p, (unsigned)nblk, lds, stream) : VSYS_ERR_ARG;
+    case 0: return W64_CASE(0);
+    case 1: return W64_CASE(1);
+    case 3: return W64_CASE(3);
+    case 5: return k_bound > 0.f && q_norm_w != nullptr ? W64_CASE(5) : VSYS_ERR_ARG;
 #ifdef VSYS_LAB
-    case 7: return launch_w64_t<7>(p, (unsigned)nblk, lds, stream);
-    case 10: return launch_w64_t<10>(p, (unsigned)nblk, lds, stream);
-    case 8: return launch_w64_t<8>(p, (unsigned)nblk, lds, stream);
-    case 9: return launch_w64_t<9>(p, (unsigned)nblk, lds, stream);
+    case 7: return W64_CASE(7);
+    case 10: return W64_CASE(10);
+    case 8: return W64_CASE(8);
+    case 9: return W64_CASE(9);
 #endif
     default: return VSYS_ERR_ARG;
   }
+#undef W64_CASE
 }
 
 }  // namespace vsys

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Generator of the hand-allocated gfx950 instruction stream of flash_attn_d72_w64 (csrc/attention_w64.hip).
 
-    python videosys_amd/csrc/gen/flash72_gen.py            -> videosys_amd/csrc/flash72_w64_asm.inc  (committed; build() does not run this)
+    python videosys_amd/csrc/gen/flash72_gen.py            -> videosys_amd/csrc/flash72_w64_asm.inc, flash72_w64_map.inc  (committed; build() does not run this)
 
 One wave = 64 query rows (two 32-row blocks A, B) of one (batch, head), ONE wave per SIMD (512 registers), 4 waves per workgroup.
 Replaces the tile loop of flash_attn_d72_kernel (attention.hip; reference: modules/attentions.py:80-120 SDPA of OpenSoraAttention)
@@ -18,7 +18,9 @@ Software pipeline per 64-key tile i (two phases, one s_barrier):
 with every non-MFMA instruction PLACED in a gap behind an MFMA (<= 5 per gap where the counts allow: MI355X_MICROARCH.md "one wave
 per SIMD" row).  K/V tiles travel HBM -> LDS by LDS-DMA into a ring of 4 stages, two tiles ahead of their first reader.
 tools/gcn_emu.py executes the text this file emits (all four waves, LDS-DMA / ds_read completion as late and as early as the
-counters allow) and checks the software-visible hazards; tests/test_flash72_asm_cpu.py runs it against numpy attention."""
+counters allow) and checks the software-visible hazards; tests/test_flash72_asm_cpu.py runs it against numpy attention.
+A second, small include (flash72_w64_map.inc) carries the register map for the C++ around the statements (write_register_map:
+Q write, O read-out, operand lists): csrc/attention_w64.hip, attention64_w64.hip and flash_w64.h name no accumulation register and no operand themselves."""
 import os
 import sys
 
@@ -679,6 +681,53 @@ def _generate(variant):
 
 OPERANDS = ["rk", "rv", "r4", "wl", "sv0", "sv1", "s4", "st4", "l4", "lb", "nt", "lim", "kvo", "vvo", "v4o", "kfa", "vfa0", "vfa1",
             "vfa2", "vfa3"]
+# the input operands of the other forms, in the order the C++ lists them (the order is part of what the compiler allocates from)
+OPERANDS_STATIC = ["nma", "nmb"]        # variant 5: the -m splats of blocks A / B
+OPERANDS_PERSIST = ["kb", "vb", "kbn", "vbn", "rqn", "wl", "kvp2", "hn", "s4", "st4", "l4", "lb", "nt", "qlds", "kvo", "vvo", "v4o", "kfa",
+                    "vfa0", "vfa1", "vfa2", "vfa3", "qvo"]
+OPERANDS_PERSIST_RING = ["st0", "st1", "st2"]      # (behind nma / nmb in the persistent static form)
+OPERANDS_D64 = ["rk", "rv", "wl", "sv0", "sv1", "lb", "nt", "lim", "kvo", "vvo", "kfa0", "kfa1", "kfa2", "kfa3", "vfa0", "vfa1", "vfa2",
+                "vfa3"]
+VECTOR_OPERANDS = {"lim", "kvo", "vvo", "v4o", "kfa", "kfa0", "kfa1", "kfa2", "kfa3", "vfa0", "vfa1", "vfa2", "vfa3", "qvo", "nma", "nmb"}
+
+
+def operand_list(names):
+    """The input-operand list of an asm statement: every operand is bound to the C++ variable of the same name."""
+    return ", ".join(f'[{n}] "{"v" if n in VECTOR_OPERANDS else "s"}"({n})' for n in names)
+
+
+def q_write(blk, ncc):
+    """(text, clobbers) of the statement that moves the 4 * ncc packed words of block blk's Q fragments into a[Q[blk] ...]; the
+    s_nop behind block B covers v_accvgpr_write -> MFMA read for the statement that follows."""
+    regs = [Q[blk] + i for i in range(4 * ncc)]
+    text = "".join(f"v_accvgpr_write_b32 a{r}, %{i}\\n\\t" for i, r in enumerate(regs)) + ("s_nop 1\\n\\t" if blk == "B" else "")
+    return text, [f"a{r}" for r in regs]
+
+
+def o_read(blk, ndt):
+    """(dt, r, register) of block blk's O^T accumulators in the first ndt 32-dim blocks.  head_dim 72 reads all three (the row sum is
+    o[2][4]: the ones rows 72 / 76 of Vt); head_dim 64 reads two and, of the third, only that row sum (write_register_map)."""
+    return [(dt, r, O[blk] + 16 * dt + r) for dt in range(ndt) for r in range(16)]
+
+
+def write_register_map(f):
+    """What the C++ around the statements needs of the allocation above, so that it is typed nowhere else: the Q write, the O read-out
+    and the operand lists, for head_dim 72 and 64 (4 chunks, two 32-dim blocks of O + the row sum: generate(d64=True))."""
+    for name, ncc, ndt in (("FLASH72_W64", NCC, 3), ("FLASH64_W64", 4, 2)):
+        for blk in "AB":
+            text, clob = q_write(blk, ncc)
+            f.write(f"#define {name}_WRITE_Q_{blk}(qw_) asm volatile(\"{text}\" : : "
+                    + ", ".join(f'"v"((qw_)[{i // 4}].{"xyzw"[i % 4]})' for i in range(4 * ncc)) + " : " + ", ".join(f'"{c}"' for c in clob) + ")\n")
+            reads = [f'asm volatile("v_accvgpr_read_b32 %0, a{reg}" : "=v"((o_)[{dt}][{r}]));' for dt, r, reg in o_read(blk, ndt)]
+            if ndt == 2:
+                reads.append(f'asm volatile("v_accvgpr_read_b32 %0, a{O[blk] + 36}" : "=v"(lsum_));')
+            f.write(f"#define {name}_READ_O_{blk}(o_{', lsum_' if ndt == 2 else ''}) do {{ " + " ".join(reads) + " } while (0)\n")
+    f.write("#define FLASH72_W64_OPERANDS " + operand_list(OPERANDS) + "\n")
+    f.write("#define FLASH72_W64_OPERANDS_S " + operand_list(OPERANDS + OPERANDS_STATIC) + "\n")
+    f.write("#define FLASH72_W64P_OPERANDS " + operand_list(OPERANDS_PERSIST + OPERANDS_PERSIST_RING) + "\n")
+    f.write("#define FLASH72_W64P_OPERANDS_S " + operand_list(OPERANDS_PERSIST + OPERANDS_STATIC + OPERANDS_PERSIST_RING) + "\n")
+    f.write("#define FLASH64_W64_OPERANDS " + operand_list(OPERANDS_D64) + "\n")
+    f.write("#define FLASH64_W64_OPERANDS_S " + operand_list(OPERANDS_D64 + OPERANDS_STATIC) + "\n")
 
 
 def clobbers(d64=False, phase=False):
@@ -691,7 +740,10 @@ def clobbers(d64=False, phase=False):
 VARIANTS = (0, 1, 3, 5, 7, 8, 9, 10)   # 5: no running max (the caller's row bound); 7, 10: lab stamps; 8, 9: lab ablations (results not valid), compiled under VSYS_LAB only
 
 
-def write_inc(path):
+MAP_NAME = "flash72_w64_map.inc"
+
+
+def write_inc(path, map_path=None):
     with open(path, "w") as f:
         f.write("// GENERATED by csrc/gen/flash72_gen.py — do not edit (tests/test_flash72_asm_cpu.py regenerates and compares).\n")
         f.write("// The tile loop of flash_attn_d72_w64_kernel as ONE asm statement; register map and schedule: see the generator.\n")
@@ -725,6 +777,14 @@ def write_inc(path):
                 f.write('  "' + ln + '\\n\\t" \\\n')
             f.write('  ""\n')
         f.write("#define FLASH64_W64_CLOBBERS " + ", ".join('"' + c + '"' for c in clobbers(True)) + "\n")
+    # the register map goes into a small file of its own beside the statements (MAP_NAME)
+    with open(map_path or os.path.join(os.path.dirname(path), MAP_NAME), "w") as f:
+        f.write("// GENERATED by csrc/gen/flash72_gen.py — do not edit (tests/test_flash72_asm_cpu.py regenerates and compares).\n")
+        f.write("// The register map of the statements in flash72_w64_asm.inc as the C++ around them needs it (csrc/flash_w64.h and the kernels\n")
+        f.write("// name no register themselves): <F>_WRITE_Q_<blk>(qw): a block's packed Q fragments -> a[Q]; <F>_READ_O_<blk>(o[, lsum]):\n")
+        f.write("// a[O] -> o[dt][r], one asm statement per register; <F>_OPERANDS[_S]: the input operands of the tile-loop statements (_S:\n")
+        f.write("// without the running max), each bound to the C++ variable of the operand's name.\n")
+        write_register_map(f)
     return generate(0)
 
 
