@@ -592,6 +592,30 @@ int vsys_pixels_to_u8(const void* x, const int64_t* grid, int64_t N, int64_t ldx
  * keys padded to the 128-column tile; n % 4 == 0, ld % 4 == 0, ld <= 8192). */
 int vsys_softmax_rows(const void* s_f32, void* p, int64_t rows, int64_t n, int64_t ld, void* stream);
 
+/* Open-Sora-Plan v1.2 CausalVAE decode and sampler (csrc/vae_osp.hip).  None of the three has a VSYS_OP code: the decode is not part
+ * of a recorded step, and the step kernel is launched by the host after each replay. */
+/* Spatial2xTime2x3DUpsample.forward up to its conv (autoencoder_kl_open_sora_plan_v120.py:349-357): F.interpolate(mode="trilinear",
+ * align_corners=False) of frame 0 by (1, 2, 2) and of frames 1..T-1 by (2, 2, 2) among themselves (source indices clamp at the ends
+ * of THAT range), concatenated: grid_dst has T == 1 ? 1 : 2T - 1 frames of (2H, 2W).  x: bf16 channels-last rows over grid_src; y:
+ * rows over grid_dst, interior rows written only (the causal conv that follows reads the padded grid as it is).  Per axis the weights
+ * are 1/4 and 3/4 with edge clamping; the eight taps are accumulated in fp32 and rounded to bf16 once.  C % 8 == 0, C <= 2048,
+ * x and y 16-byte aligned. */
+int vsys_upsample_trilinear2x(const void* x, const int64_t* grid_src, void* y, const int64_t* grid_dst, int64_t N, int64_t C,
+                              void* stream);
+/* One sampler step of OpenSoraPlanPipeline (pipeline_open_sora_plan.py): the CFG combine and the drop of the learned-sigma half
+ * (:1149-1156), EulerAncestralDiscreteScheduler.step (:1161) and the scale_model_input of the NEXT step (:1109-1110).  z fp32
+ * [Bz, Cin, thw] in place; model_out fp32 [2 Bz, Cout, thw], Cout == 2 Cin, negative prompt first (uncond = model_out[b], cond =
+ * model_out[b + Bz]); noise fp32 [Bz, Cin, thw], may be NULL when sigma_up == 0; model_in bf16 [2 Bz, Cin, thw].
+ * z' = z + dt (u + guidance (c - u)) + sigma_up noise, evaluated in fp64 on the fp32 operands and rounded once;
+ * model_in[b] = model_in[b + Bz] = bf16(z' * in_scale), in_scale = 1 / sqrt(sigma_next^2 + 1). */
+int vsys_cfg_ancestral_step(void* z_f32, const void* model_out_f32, const void* noise_f32, void* model_in, int64_t Bz, int64_t Cin,
+                            int64_t Cout, int64_t thw, float guidance, float dt, float sigma_up, float in_scale, void* stream);
+/* OpenSoraPlanPipeline.decode_latents' post-process (pipeline_open_sora_plan.py:1186-1188) on the bf16 video: grid descriptor, ldx and
+ * the uint8 layout out[Ftot][H][W][3] as vsys_pixels_to_u8.  Value, every tensor op of the reference rounding to bf16:
+ * d = clamp(bf16(bf16(x / 2) + 0.5), 0, 1), m = bf16(d * 255), byte = trunc(m) (vsys_pixels_to_u8 rounds float(d) * 255 half-even). */
+int vsys_pixels_to_u8_trunc(const void* x, const int64_t* grid, int64_t N, int64_t ldx, void* out_u8, int64_t Ftot, int64_t f0,
+                            void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------------------
  * Launch programs.  A denoise step is ~450 launches of the entry points above with arguments that do not change from step to
  * step (workspaces, weights and PAB slabs are resident; per-step values live in device buffers).  The host mirror records the

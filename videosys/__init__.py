@@ -37,9 +37,10 @@ _MODULES = {
     "models.transformers.latte_transformer_3d": "latte",            # LatteT2V
     "models.transformers.cogvideox_transformer_3d": "cogvideox",    # CogVideoXTransformer3DModel
     "models.transformers.vchitect_transformer_3d": "vchitect",      # VchitectXLTransformerModel, JointTransformerBlock
-    "models.transformers.open_sora_plan_v120_transformer_3d": "open_sora_plan",   # OpenSoraT2V, OpenSoraT2V_ROPE_L_122 (transformer only)
+    "models.transformers.open_sora_plan_v120_transformer_3d": "open_sora_plan",   # OpenSoraT2V, OpenSoraT2V_ROPE_L_122
     "models.autoencoders.autoencoder_kl_open_sora": "vae_open_sora",    # OpenSoraVAE_V1_2
     "models.autoencoders.autoencoder_kl_cogvideox": "vae_cogvideox",    # AutoencoderKLCogVideoX
+    "models.autoencoders.autoencoder_kl_open_sora_plan_v120": "vae_open_sora_plan",   # CausalVAEModelWrapper, CausalVAEModel (decode side)
     "pipelines.open_sora": "pipeline_open_sora",              # OpenSoraConfig, OpenSoraPABConfig, OpenSoraPipeline
     "pipelines.open_sora.pipeline_open_sora": "pipeline_open_sora",
     "pipelines.latte": "pipeline_latte",
@@ -48,6 +49,8 @@ _MODULES = {
     "pipelines.cogvideox.pipeline_cogvideox": "pipeline_cogvideox",
     "pipelines.vchitect": "pipeline_vchitect",                # VchitectConfig, VchitectPABConfig, VchitectXLPipeline
     "pipelines.vchitect.pipeline_vchitect": "pipeline_vchitect",
+    "pipelines.open_sora_plan": "pipeline_open_sora_plan",    # OpenSoraPlanConfig, OpenSoraPlanV120PABConfig, OpenSoraPlanPipeline (v1.2)
+    "pipelines.open_sora_plan.pipeline_open_sora_plan": "pipeline_open_sora_plan",
 }
 
 

@@ -760,4 +760,29 @@ int vsys_softmax_rows(const void* s_f32, void* p, int64_t rows, int64_t n, int64
   return launch_softmax_rows(reinterpret_cast<const float*>(s_f32), B16(p), rows, (int)n, (int)ld, S(stream));
 }
 
+int vsys_upsample_trilinear2x(const void* x, const int64_t* grid_src, void* y, const int64_t* grid_dst, int64_t N, int64_t C,
+                              void* stream) {
+  VaeGrid gs, gd;
+  if (!x || !y || !to_grid(grid_src, gs) || !to_grid(grid_dst, gd)) return VSYS_ERR_ARG;
+  if (!fits_int(N, C)) return VSYS_ERR_SHAPE;
+  return launch_upsample_trilinear2x(B16(x), gs, B16(y), gd, (int)N, (int)C, S(stream));
+}
+
+int vsys_cfg_ancestral_step(void* z_f32, const void* model_out_f32, const void* noise_f32, void* model_in, int64_t Bz, int64_t Cin,
+                            int64_t Cout, int64_t thw, float guidance, float dt, float sigma_up, float in_scale, void* stream) {
+  if (!z_f32 || !model_out_f32 || !model_in) return VSYS_ERR_ARG;
+  if (!fits_int(Bz, Cin, Cout) || thw < 0) return VSYS_ERR_SHAPE;
+  return launch_cfg_ancestral_step(reinterpret_cast<float*>(z_f32), reinterpret_cast<const float*>(model_out_f32),
+                                   reinterpret_cast<const float*>(noise_f32), B16(model_in), (int)Bz, (int)Cin, (int)Cout, thw, guidance,
+                                   dt, sigma_up, in_scale, S(stream));
+}
+
+int vsys_pixels_to_u8_trunc(const void* x, const int64_t* grid, int64_t N, int64_t ldx, void* out_u8, int64_t Ftot, int64_t f0,
+                            void* stream) {
+  VaeGrid g;
+  if (!x || !out_u8 || !to_grid(grid, g)) return VSYS_ERR_ARG;
+  if (!fits_int(N, ldx)) return VSYS_ERR_SHAPE;
+  return launch_pixels_to_u8_trunc(B16(x), g, (int)N, ldx, reinterpret_cast<uint8_t*>(out_u8), Ftot, f0, S(stream));
+}
+
 }  // extern "C"

@@ -156,6 +156,12 @@ int launch_vae_first_im2col_nc(const float* z, int F, int Cz, int H, int W, int 
                                hipStream_t stream);
 int launch_pixels_to_u8(const bf16_t* x, const VaeGrid& g, int N, int64_t ldx, uint8_t* out, int64_t Ftot, int64_t f0,
                         hipStream_t stream);
+// Open-Sora-Plan v1.2 CausalVAE decode and sampler (vae_osp.hip)
+int launch_upsample_trilinear2x(const bf16_t* x, const VaeGrid& gs, bf16_t* y, const VaeGrid& gd, int N, int C, hipStream_t stream);
+int launch_cfg_ancestral_step(float* z, const float* model_out, const float* noise, bf16_t* model_in, int Bz, int Cin, int Cout,
+                              int64_t thw, float guidance, float dt, float sigma_up, float in_scale, hipStream_t stream);
+int launch_pixels_to_u8_trunc(const bf16_t* x, const VaeGrid& g, int N, int64_t ldx, uint8_t* out, int64_t Ftot, int64_t f0,
+                              hipStream_t stream);
 
 // T5 encoder pieces (t5_ops.hip)
 int launch_gather_rows(const bf16_t* table, const int64_t* ids, bf16_t* out, int64_t n, int C, int64_t vocab, hipStream_t stream);

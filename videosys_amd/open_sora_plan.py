@@ -15,8 +15,9 @@ instead of 16 at the production geometry, about 0.1 ms of a 154 ms step, and was
 
 Built: norm_type="ada_norm_single", use_rope=True, downsampler=None, patch_size_t=1, activation_fn="gelu-approximate",
 attention_head_dim=96, biased projections, LayerNorms without affine, out_channels in {in_channels, 2 in_channels},
-use_image_num=0.  Anything else raises NotImplementedError at construction — nothing is approximated.  Not here (follow-ups): the
-CausalVAE, mT5, the sampler, the pipeline / config classes, v1.1, sequence parallelism.
+use_image_num=0.  Anything else raises NotImplementedError at construction — nothing is approximated.  The CausalVAE decode, mT5, the
+sampler and the pipeline / config classes are vae_open_sora_plan.py and pipeline_open_sora_plan.py; not built (follow-ups): v1.1,
+sequence parallelism.
 
 Differences that do not change results:
   * attn1's to_q / to_k / to_v are one [3C, C] GEMM; attn2's to_k / to_v run once per (prompt, mask) — the text is constant over the

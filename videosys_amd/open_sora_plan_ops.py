@@ -1,7 +1,8 @@
-"""Tensor-level wrappers of the head-dim-96 attention entry points of Open-Sora-Plan v1.2 (include/videosys_amd.h:
-vsys_attn_prep_kv96, vsys_flash_attn_d96).  HIP device tensors only, no eager fallback.
+"""Tensor-level wrappers of the entry points that exist for Open-Sora-Plan v1.2 (include/videosys_amd.h): the head-dim-96 attention
+(vsys_attn_prep_kv96, vsys_flash_attn_d96) and, at the end of the file, the CausalVAE decode and sampler kernels
+(vsys_upsample_trilinear2x, vsys_cfg_ancestral_step, vsys_pixels_to_u8_trunc).  HIP device tensors only, no eager fallback.
 
-Neither entry point has an op code (the op table is pinned, csrc/gen/program_gen.py NO_OP), so the launch goes through ctypes on
+Neither attention entry point has an op code (the op table is pinned, csrc/gen/program_gen.py NO_OP), so the launch goes through ctypes on
 torch's current stream, and under a launch-program recorder it is a ``program.host_call`` closure: the program keeps the tensors
 alive and re-issues the same call, with the same addresses, at the same position of every replay.  The per-sample key counts of the
 cross-attention are read by the kernel from device memory, so a replay carries no count.
@@ -11,7 +12,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib, program
-from .ops import _bf16, _chk, kv_pad_len
+from .ops import VaeGrid, _bf16, _call, _chk, _p, kv_pad_len
 
 HEAD_DIM = 96
 
@@ -76,4 +77,53 @@ def flash_attn96(q, rope_cos, rope_sin, kp, vt, kv_lens, out, batch, heads, q_le
     _issue("vsys_flash_attn_d96", (q, rope_cos, rope_sin, kp, vt, kv_lens, out),
            (dp(q), q.stride(0), dp(rope_cos), dp(rope_sin), dp(kp), dp(vt), dp(kv_lens), dp(out), out.stride(0), batch, heads, q_len,
             kv_len, kv_pad))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ CausalVAE decode and sampler
+# (csrc/vae_osp.hip; no op codes either: the decode is not part of a recorded step and the sampler step is launched by the host
+#  after each replay, so these three go through ctypes on torch's current stream and refuse to run under a recorder.
+#  Element-wise tests: tests/test_gpu_osp_vae_kernels.py; guard bands: tests/test_gpu_isolation_osp_pipeline.py)
+def upsample_trilinear2x(x, gs: VaeGrid, y, gd: VaeGrid, C):
+    """Spatial2xTime2x3DUpsample up to its conv: x rows over gs -> the interior rows of gd ((1 if T == 1 else 2T - 1) frames of
+    (2H, 2W)); F.interpolate(mode="trilinear") of frame 0 by (1, 2, 2) and of the later frames by (2, 2, 2) among themselves, the eight
+    taps accumulated in fp32 and rounded once (include/videosys_amd.h)."""
+    _chk(x, y)
+    _bf16(x, y)
+    assert program.active() is None, "vsys_upsample_trilinear2x has no op code"
+    assert x.shape == (gs.rows, C) and y.shape == (gd.rows, C) and x.is_contiguous() and y.is_contiguous()
+    _call("vsys_upsample_trilinear2x", _p(x), gs._c, _p(y), gd._c, gs.n, C)
+    return y
+
+
+def cfg_ancestral_step(z, model_out, noise, model_in, guidance, dt, sigma_up, in_scale):
+    """z fp32 [Bz, Cin, ...] in place: z + dt (u + guidance (c - u)) + sigma_up noise with u = model_out[b], c = model_out[b + Bz] on
+    the first Cin of the 2 Cin channels of model_out fp32 [2 Bz, 2 Cin, ...]; model_in bf16 [2 Bz, Cin, ...]: both halves
+    bf16(z' * in_scale).  ``noise``: fp32 like z, or None when sigma_up == 0."""
+    _chk(z, model_out, noise, model_in)
+    _bf16(model_in)
+    assert program.active() is None, "vsys_cfg_ancestral_step has no op code: launch it after the replay"
+    Bz, Cin = z.shape[:2]
+    thw = z[0, 0].numel()
+    assert z.dtype == torch.float32 and model_out.dtype == torch.float32 and z.is_contiguous() and model_out.is_contiguous()
+    assert tuple(model_out.shape) == (2 * Bz, 2 * Cin) + tuple(z.shape[2:]), (tuple(model_out.shape), tuple(z.shape))
+    assert model_in.is_contiguous() and tuple(model_in.shape) == (2 * Bz,) + tuple(z.shape[1:])
+    if noise is not None:
+        assert noise.dtype == torch.float32 and noise.is_contiguous() and noise.shape == z.shape
+    else:
+        assert sigma_up == 0.0, "no noise tensor, but sigma_up != 0"
+    _call("vsys_cfg_ancestral_step", _p(z), _p(model_out), _p(noise), _p(model_in), Bz, Cin, 2 * Cin, thw, float(guidance), float(dt),
+          float(sigma_up), float(in_scale))
+    return z, model_in
+
+
+def pixels_to_u8_trunc(x, g: VaeGrid, out, f0):
+    """first 3 channels of the interior rows of grid g (x [g.rows, ldx] bf16, row-strided) -> out uint8 [Ftot, H, W, 3], frames
+    f0 .. f0 + g.n * g.T - 1: trunc(bf16(clamp(bf16(bf16(x / 2) + 0.5), 0, 1) * 255)), the reference pipeline's own post-process."""
+    _chk(x, out)
+    _bf16(x)
+    assert program.active() is None, "vsys_pixels_to_u8_trunc has no op code"
+    assert x.dim() == 2 and x.shape[0] == g.rows and x.stride(1) == 1 and x.shape[1] >= 3
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 4 and tuple(out.shape[1:]) == (g.H, g.W, 3)
+    _call("vsys_pixels_to_u8_trunc", _p(x), g._c, g.n, x.stride(0), _p(out), out.shape[0], f0)
     return out
