@@ -152,3 +152,53 @@ def test_tiled_decode_with_tiles_shared_out_over_ranks_host_bookkeeping():
                     assert o.shape == want.shape and torch.equal(o, want), (H, W, P, r)
     finally:
         ops.blend_edge = saved
+
+
+def test_stitch_tiles_is_the_references_blend_and_crop_loop():
+    """vae_blocks.stitch_tiles (CogVideoXVAE._tiled, CausalVAEDecoder._tiled2d) against the stitching loops of the references' tiled
+    decodes (autoencoder_kl_cogvideox.py:1221-1234, autoencoder_kl_open_sora_plan_v120.py tiled_decode2d) restated here, with
+    ``ops.blend_edge`` replaced by a torch restatement of their blend_v / blend_h: a 3 x 3 grid of tiles of 8 x 10 pixels whose last
+    row is 3 high and last column 4 wide, under CogVideoX's separate height / width extents and limits and the plan's square ones.
+    Bit-equal; and the same loops with the two blends swapped give another result, so the in-place order is seen."""
+    from videosys_amd import ops
+    from videosys_amd.vae_blocks import stitch_tiles
+
+    def blend_v(a, b, ext):
+        ext = min(a.shape[-2], b.shape[-2], ext)
+        for y in range(ext):
+            b[..., y, :] = a[..., -ext + y, :] * (1 - y / ext) + b[..., y, :] * (y / ext)
+        return b
+
+    def blend_h(a, b, ext):
+        ext = min(a.shape[-1], b.shape[-1], ext)
+        for x in range(ext):
+            b[..., x] = a[..., -ext + x] * (1 - x / ext) + b[..., x] * (x / ext)
+        return b
+
+    def reference(rows, ext_h, ext_w, lim_h, lim_w, swapped=False):
+        result_rows = []
+        for i, row in enumerate(rows):
+            result_row = []
+            for j, tile in enumerate(row):
+                steps = [(i > 0, lambda t: blend_v(rows[i - 1][j], t, ext_h)), (j > 0, lambda t: blend_h(row[j - 1], t, ext_w))]
+                for on, blend in (reversed(steps) if swapped else steps):
+                    if on:
+                        tile = blend(tile)
+                result_row.append(tile[..., :lim_h, :lim_w])
+            result_rows.append(torch.cat(result_row, dim=-1))
+        return torch.cat(result_rows, dim=-2)
+
+    g = torch.Generator().manual_seed(21)
+    tiles = [[torch.randn(3, 2, h, w, generator=g) for w in (10, 10, 4)] for h in (8, 8, 3)]
+    fresh = lambda: [[t.clone() for t in row] for row in tiles]
+    saved = ops.blend_edge
+    ops.blend_edge = lambda a, b, ext, axis: (blend_v if axis == 0 else blend_h)(a, b, ext)
+    try:
+        for ext_h, ext_w, lim_h, lim_w in ((4, 5, 6, 7), (4, 4, 6, 6)):     # CogVideoX: per axis (the last row / column clamp the extent); plan: square
+            got = stitch_tiles(fresh(), ext_h, ext_w, lim_h, lim_w)
+            want = reference(fresh(), ext_h, ext_w, lim_h, lim_w)
+            assert tuple(got.shape) == (3, 2, 2 * lim_h + 3, 2 * lim_w + 4)
+            assert torch.equal(got, want), (ext_h, ext_w, lim_h, lim_w)
+            assert not torch.equal(got, reference(fresh(), ext_h, ext_w, lim_h, lim_w, swapped=True))
+    finally:
+        ops.blend_edge = saved

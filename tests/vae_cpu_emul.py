@@ -99,19 +99,19 @@ def extract_planar(x, g, nc, tskip, out, f0):
 
 
 def attention_2d(x, g, A):
-    """OpenSoraVAE._attention (the batched-GEMM / softmax composition is the decode path's, checked on the GPU): plain torch."""
+    """VaeBlocks._attention with ``A`` an AttnWeights (the batched-GEMM / softmax composition is the decode path's, checked on the GPU): plain torch."""
     from videosys_amd.ops import VaeGrid
 
     C, L, n = 512, g.H * g.W, g.n
     t = _interior(x, g, C).reshape(n, L, C).float()
-    hn = F.group_norm(t.transpose(1, 2), 32, A.a_norm.g.float(), A.a_norm.b.float(), A.a_norm.eps).transpose(1, 2)
+    hn = F.group_norm(t.transpose(1, 2), 32, A.norm.g.float(), A.norm.b.float(), A.norm.eps).transpose(1, 2)
     hn = hn.to(torch.bfloat16).float()
-    q = (hn @ A.a_wq.float().t() + A.a_bq.float()).to(torch.bfloat16).float()
-    k = (hn @ A.a_wk.float().t() + A.a_bk.float()).to(torch.bfloat16).float()
-    v = (hn @ A.a_wv.float().t()).to(torch.bfloat16).float()
+    q = (hn @ A.wq.float().t() + A.bq.float()).to(torch.bfloat16).float()
+    k = (hn @ A.wk.float().t() + A.bk.float()).to(torch.bfloat16).float()
+    v = (hn @ A.wv.float().t()).to(torch.bfloat16).float()
     p = torch.softmax(q @ k.transpose(1, 2) / (C ** 0.5), dim=-1).to(torch.bfloat16).float()
     o = (p @ v).to(torch.bfloat16).float()
-    y = (o @ A.a_wo.float().t() + A.a_bo.float() + t).to(torch.bfloat16)
+    y = (o @ A.wo.float().t() + A.bo.float() + t).to(torch.bfloat16)
     gd = VaeGrid(n, 1, g.H, g.W, 0, 0)
     return y.reshape(n * L, C), gd
 
@@ -119,21 +119,21 @@ def attention_2d(x, g, A):
 @contextlib.contextmanager
 def emulated_vae_ops():
     from videosys_amd import ops
-    from videosys_amd.vae_open_sora import OpenSoraVAE
+    from videosys_amd.vae_blocks import VaeBlocks
 
     mine = dict(vae_first_im2col=vae_first_im2col, gemm128=gemm128, conv=conv, group_norm=group_norm, regrid=regrid,
                 subsample=subsample, extract_planar=extract_planar)
     saved = {k: getattr(ops, k) for k in mine}
-    saved_attn = OpenSoraVAE._attention
+    saved_attn = VaeBlocks._attention
     for k, v in mine.items():
         setattr(ops, k, v)
-    OpenSoraVAE._attention = lambda self, x, g, aw=None: attention_2d(x, g, aw if aw is not None else self)
+    VaeBlocks._attention = lambda self, x, g, aw: attention_2d(x, g, aw)
     try:
         yield
     finally:
         for k, v in saved.items():
             setattr(ops, k, v)
-        OpenSoraVAE._attention = saved_attn
+        VaeBlocks._attention = saved_attn
 
 
 def cpu_vae(state_dict, encoder=True):

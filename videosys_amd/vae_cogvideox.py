@@ -10,17 +10,19 @@ reference's (``decoder.*``), so the published ``vae/diffusion_pytorch_model.safe
 Every convolution is the tap-shifted implicit-GEMM kernel of csrc/conv_bf16.hip (causal padding = two extra frames in front of
 the conv-input buffer, filled from the layer's cache or with copies of the first frame); the spatially conditioned norm computes
 conv_y(zq) | conv_b(zq) ONCE per norm at latent resolution (a 32-wide GEMM) and applies them inside the GroupNorm/SiLU kernel with
-the nearest-neighbour index map of F.interpolate.  No CPU path.
+the nearest-neighbour index map of F.interpolate.  The staging cache, the conv weight holder, the tile stitching and the weight
+synthesiser are the shared ones of vae_blocks.py; the spatial-norm residual block with its conv cache is this module's own.  No CPU path.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+import math
+from typing import Dict
 
 import torch
 
 from . import ops
 from .ops import VaeGrid
-from .vae_open_sora import _conv_w, _vec
+from .vae_blocks import StagingCache, _Conv, conv3, stitch_tiles, synth_weights
 
 
 class _SNorm:
@@ -37,30 +39,14 @@ class _SNorm:
         self.C = C
 
 
-class _CConv:
-    """CogVideoXCausalConv3d 3x3x3 (or the 1x1x1 shortcut / the per-frame 3x3 upsampler conv)."""
-
-    def __init__(self, sd, key, dev, cin_pad=None, n_pad=None):
-        w = sd[key + ".weight"].to(dev)
-        if cin_pad is not None and w.shape[1] < cin_pad:
-            w = torch.cat([w, torch.zeros(w.shape[0], cin_pad - w.shape[1], *w.shape[2:], dtype=w.dtype, device=dev)], 1)
-        self.key = key
-        self.kt = w.shape[2] if w.dim() == 5 else 1
-        self.ks = w.shape[-1]
-        self.cin, self.cout = w.shape[1], w.shape[0]
-        self.w = _conv_w(w, n_pad)
-        b = sd.get(key + ".bias")
-        self.b = _vec(b.to(dev), n_pad) if b is not None else None
-
-
 class _CRes:
     def __init__(self, sd, p, dev):
         self.n1, self.n2 = _SNorm(sd, p + ".norm1", dev), _SNorm(sd, p + ".norm2", dev)
-        self.c1, self.c2 = _CConv(sd, p + ".conv1.conv", dev), _CConv(sd, p + ".conv2.conv", dev)
-        self.sc = _CConv(sd, p + ".conv_shortcut", dev) if (p + ".conv_shortcut.weight") in sd else None
+        self.c1, self.c2 = _Conv(sd, p + ".conv1.conv", dev), _Conv(sd, p + ".conv2.conv", dev)   # CogVideoXCausalConv3d 3x3x3
+        self.sc = _Conv(sd, p + ".conv_shortcut", dev) if (p + ".conv_shortcut.weight") in sd else None
 
 
-class CogVideoXVAE:
+class CogVideoXVAE(StagingCache):
     """Decode side of AutoencoderKLCogVideoX.  ``decode(z)``: z [B, 16, T, H, W] -> [B, 3, T_out, 8H, 8W] bf16."""
 
     num_latent_frames_batch_size = 2
@@ -69,10 +55,8 @@ class CogVideoXVAE:
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", sample_height: int = 480, sample_width: int = 720,
                  scaling_factor: float = 1.15258426, temporal_compression_ratio: int = 4, use_tiling: bool = True):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("videosys_amd.CogVideoXVAE needs a HIP device (no CPU path)")
-        self.device = dev
+        super().__init__(device)
+        dev = self.device
         self.config = type("Cfg", (), dict(scaling_factor=scaling_factor, temporal_compression_ratio=temporal_compression_ratio,
                                            block_out_channels=(128, 256, 256, 512), sample_height=sample_height,
                                            sample_width=sample_width, latent_channels=16))()
@@ -82,7 +66,7 @@ class CogVideoXVAE:
         self.tile_latent_min_height = int(self.tile_sample_min_height / 8)
         self.tile_latent_min_width = int(self.tile_sample_min_width / 8)
         sd, d = state_dict, "decoder."
-        self.conv_in = _CConv(sd, d + "conv_in.conv", dev, cin_pad=32)
+        self.conv_in = _Conv(sd, d + "conv_in.conv", dev, cin_pad=32)
         self.mid = [_CRes(sd, f"{d}mid_block.resnets.{i}", dev) for i in range(2)]
         self.ups = []
         level = 0
@@ -94,10 +78,9 @@ class CogVideoXVAE:
             while f"{d}up_blocks.{i}.resnets.{len(res)}.conv1.conv.weight" in sd:
                 res.append(_CRes(sd, f"{d}up_blocks.{i}.resnets.{len(res)}", dev))
             uk = f"{d}up_blocks.{i}.upsamplers.0.conv"
-            self.ups.append((res, _CConv(sd, uk, dev) if (uk + ".weight") in sd else None, i < level))
+            self.ups.append((res, _Conv(sd, uk, dev) if (uk + ".weight") in sd else None, i < level))
         self.norm_out = _SNorm(sd, d + "norm_out", dev)
-        self.conv_out = _CConv(sd, d + "conv_out.conv", dev, n_pad=128)
-        self._padded: Dict[tuple, tuple] = {}
+        self.conv_out = _Conv(sd, d + "conv_out.conv", dev, n_pad=128)
 
     def enable_tiling(self):
         self.use_tiling = True
@@ -106,18 +89,6 @@ class CogVideoXVAE:
         self.use_tiling = False
 
     # ------------------------------------------------------------------------------------------------ building blocks
-    def clear_cache(self):
-        """Drop the zero-bordered staging buffers (they are kept per geometry; call after changing resolution to free HBM)."""
-        self._padded.clear()
-
-    def _padded_buf(self, g: VaeGrid, C: int):
-        key = (g.n, g.T, g.H, g.W, g.tf, C)
-        hit = self._padded.get(key)
-        if hit is None:
-            hit = g.alloc(C, self.device, zero=True)
-            self._padded[key] = hit
-        return hit[1]
-
     def _front(self, rows, g: VaeGrid, key, cache):
         """The two frames in front of a causal conv's input (CogVideoXCausalConv3d.fake_context_parallel_forward :112-117): the
         cached tail of the previous frame batch, or copies of this batch's first frame; then remember this batch's tail."""
@@ -136,7 +107,7 @@ class CogVideoXVAE:
         ops.spatial_norm_silu(x, gx, y, gd, norm.C, norm.g, norm.b, yb, zdims)
         return y, gd
 
-    def _cconv(self, h, gh: VaeGrid, cv: _CConv, cache, res=None):
+    def _cconv(self, h, gh: VaeGrid, cv: _Conv, cache, res=None):
         self._front(h, gh, cv.key, cache)
         return ops.conv(h, gh, cv.w, cv.b, cv.cin, 3, 3, res=res)
 
@@ -285,19 +256,7 @@ class CogVideoXVAE:
             rows = [flat[k * ncol:(k + 1) * ncol] for k in range(len(flat) // ncol)]
         else:
             rows = [[self._decode_tile(zb[:, :, i:i + tl_h, j:j + tl_w].contiguous()) for j in range(0, W, ov_w)] for i in range(0, H, ov_h)]
-        out_rows = []
-        for i, row in enumerate(rows):
-            res = []
-            for j, tile in enumerate(row):
-                if i > 0:   # blend_v / blend_h modify the tile in place, so later tiles see the blended neighbours (:1227-1231)
-                    a = rows[i - 1][j]
-                    ops.blend_edge(a, tile, min(a.shape[-2], tile.shape[-2], be_h), 0)
-                if j > 0:
-                    a = row[j - 1]
-                    ops.blend_edge(a, tile, min(a.shape[-1], tile.shape[-1], be_w), 1)
-                res.append(tile[:, :, :lim_h, :lim_w])
-            out_rows.append(torch.cat(res, dim=3))
-        return torch.cat(out_rows, dim=2).contiguous()
+        return stitch_tiles(rows, be_h, be_w, lim_h, lim_w).contiguous()
 
     def decode_latents(self, latents: torch.Tensor, group=None) -> torch.Tensor:
         """pipeline_cogvideox.py:359-364: latents [B, T, 16, H, W] -> frames [B, 3, T_out, 8H, 8W] (``group``: see decode)."""
@@ -316,27 +275,23 @@ def decoder_param_shapes() -> Dict[str, tuple]:
     """Decode-side parameters of the reference AutoencoderKLCogVideoX (checked against its state_dict in the CPU tests)."""
     p: Dict[str, tuple] = {}
 
-    def cconv(name, ci, co, k):
-        p[name + ".conv.weight"] = (co, ci, k, k, k)
-        p[name + ".conv.bias"] = (co,)
-
     def snorm(name, c):
         p[name + ".norm_layer.weight"] = (c,)
         p[name + ".norm_layer.bias"] = (c,)
-        cconv(name + ".conv_y", 16, c, 1)
-        cconv(name + ".conv_b", 16, c, 1)
+        conv3(p, name + ".conv_y", 16, c, 1)
+        conv3(p, name + ".conv_b", 16, c, 1)
 
     def res(name, ci, co):
         snorm(name + ".norm1", ci)
         snorm(name + ".norm2", co)
-        cconv(name + ".conv1", ci, co, 3)
-        cconv(name + ".conv2", co, co, 3)
+        conv3(p, name + ".conv1", ci, co, 3)
+        conv3(p, name + ".conv2", co, co, 3)
         if ci != co:
             p[name + ".conv_shortcut.weight"] = (co, ci, 1, 1, 1)
             p[name + ".conv_shortcut.bias"] = (co,)
 
     d = "decoder."
-    cconv(d + "conv_in", 16, 512, 3)
+    conv3(p, d + "conv_in", 16, 512, 3)
     for i in range(2):
         res(f"{d}mid_block.resnets.{i}", 512, 512)
     prev = 512
@@ -348,32 +303,18 @@ def decoder_param_shapes() -> Dict[str, tuple]:
             p[f"{d}up_blocks.{i}.upsamplers.0.conv.weight"] = (co, co, 3, 3)
             p[f"{d}up_blocks.{i}.upsamplers.0.conv.bias"] = (co,)
     snorm(d + "norm_out", 128)
-    cconv(d + "conv_out", 128, 3, 3)
+    conv3(p, d + "conv_out", 128, 3, 3)
     return p
 
 
-def synth_state_dict(seed: int = 0) -> Dict[str, torch.Tensor]:
-    """Deterministic random decode-side weights (bf16-representable fp32).  conv_y starts around 1 and conv_b around 0 so the
-    spatially conditioned norm behaves like a norm at initialisation."""
-    import math
+# the spatially conditioned norm behaves like a norm at initialisation: conv_y around 1 and conv_b around 0 (small weights, conv_y's
+# bias 1 + N(0, 0.1), conv_b's N(0, 0.02)); everything else by the shared table (``norm_layer`` counts as a norm there)
+_SYNTH_RULES = ((".conv_y.conv.weight", lambda r, fan_in: r / math.sqrt(fan_in) * 0.3),
+                (".conv_b.conv.weight", lambda r, fan_in: r / math.sqrt(fan_in) * 0.3),
+                (".conv_y.conv.bias", lambda r, fan_in: 1.0 + 0.1 * r),
+                (".conv_b.conv.bias", lambda r, fan_in: 0.02 * r))
 
-    g = torch.Generator().manual_seed(seed)
-    sd = {}
-    for k, shp in decoder_param_shapes().items():
-        if k.endswith(".weight") and len(shp) >= 2:
-            fan_in = 1
-            for s in shp[1:]:
-                fan_in *= s
-            v = torch.randn(shp, generator=g) / math.sqrt(fan_in)
-            if ".conv_y." in k or ".conv_b." in k:
-                v = v * 0.3
-        elif k.endswith("norm_layer.weight"):
-            v = 1.0 + 0.1 * torch.randn(shp, generator=g)
-        elif k.endswith("norm_layer.bias"):
-            v = 0.1 * torch.randn(shp, generator=g)
-        elif ".conv_y.conv.bias" in k:
-            v = 1.0 + 0.1 * torch.randn(shp, generator=g)
-        else:
-            v = 0.02 * torch.randn(shp, generator=g)
-        sd[k] = v.to(torch.bfloat16).float()
-    return sd
+
+def synth_state_dict(seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Deterministic random decode-side weights (vae_blocks.synth_weights with the rules above; bf16-representable fp32)."""
+    return synth_weights(decoder_param_shapes(), torch.Generator().manual_seed(seed), rules=_SYNTH_RULES)

@@ -22,81 +22,47 @@ convolution sampled at the odd positions (vsys_subsample) — 4x / 2x the arithm
 a path that runs once per conditioning clip, in exchange for no new convolution kernel.  Encoder weights are optional: a
 checkpoint without ``*.encoder.*`` keys gives a decode-only object.
 
+The weight holders, the staging cache, the residual block, the attention and the diffusers 2-D decoder body are the shared ones of
+vae_blocks.py (``VaeBlocks``); this module holds the temporal VAE, the encoders, the two ends of the 2-D decoder and the chunking.
+
 There is no CPU path: without the HIP library / a GPU every call raises.
 """
 from __future__ import annotations
 
-import math
-from types import SimpleNamespace
-from typing import Callable, Dict, List, Optional
+from typing import Callable, Dict, Optional
 
 import torch
 
 from . import ops
 from .ops import VaeGrid
+from .vae_blocks import (AttnWeights, Decoder2DWeights, VaeBlocks, _Conv, _Norm, _Res, _conv_w, _vec, conv2, conv3,
+                         diffusers_decoder_shapes, norm, res2, res3, synth_weights)
 
 _SD_SCALE = 0.18215  # autoencoder_kl_open_sora.py:527,533
 
 
-def _conv_w(w: torch.Tensor, n_pad: Optional[int] = None, k_pad: Optional[int] = None) -> torch.Tensor:
-    """[Cout, Cin, (kt,) kh, kw] -> bf16 [Cout(+pad), taps*Cin(+pad)] with k = tap*Cin + c."""
-    co = w.shape[0]
-    if w.dim() == 5:
-        m = w.permute(0, 2, 3, 4, 1).reshape(co, -1)
-    else:
-        m = w.permute(0, 2, 3, 1).reshape(co, -1)
-    n_pad = n_pad or co
-    k_pad = k_pad or m.shape[1]
-    out = torch.zeros(n_pad, k_pad, dtype=torch.bfloat16, device=w.device)
-    out[:co, :m.shape[1]] = m.to(torch.bfloat16)
-    return out.contiguous()
+class _SpatialDecoder(VaeBlocks):
+    """The 2-D SD / SDXL decoder (diffusers AutoencoderKL decode side: post_quant_conv + vae.Decoder) both classes below run per frame."""
+
+    def _init_spatial(self, sd, dev, s):
+        """Weights under key prefix ``s``; the body between conv_in and the pixels is vae_blocks.Decoder2DWeights."""
+        self.s_pq = (sd[s + "post_quant_conv.weight"].float().reshape(4, 4).cpu(), sd[s + "post_quant_conv.bias"].float().cpu())
+        d = s + "decoder."
+        self.s_conv_in_w = _conv_w(sd[d + "conv_in.weight"].to(dev), None, 64)   # K = 9 * 4 = 36 -> 64
+        self.s_conv_in_b = _vec(sd[d + "conv_in.bias"].to(dev))
+        self.s_dec = Decoder2DWeights(sd, d, dev)
+
+    def _spatial_decode(self, xz: torch.Tensor, out: torch.Tensor, f0: int, in_scale: float = 1.0 / _SD_SCALE):
+        """xz planar bf16 [4, F, H, W] -> out[3, f0:f0+F, 8H, 8W].  VideoAutoencoderKL.decode :522-538 + diffusers Decoder."""
+        _, F, H, W = xz.shape
+        params = [in_scale] * 4 + [0.0] * 4 + self.s_pq[0].flatten().tolist() + self.s_pq[1].tolist()
+        a = ops.vae_first_im2col(xz, 1, 64, params)
+        x = ops.gemm128(a, self.s_conv_in_w, self.s_conv_in_b)
+        y, g = self._decoder2d(x, VaeGrid(F, 1, H, W, 0, 0), self.s_dec)
+        ops.extract_planar(y, g, 3, 0, out, f0)
 
 
-def _vec(v: Optional[torch.Tensor], n_pad: Optional[int] = None) -> Optional[torch.Tensor]:
-    if v is None:
-        return None
-    n_pad = n_pad or v.numel()
-    out = torch.zeros(n_pad, dtype=torch.bfloat16, device=v.device)
-    out[:v.numel()] = v.to(torch.bfloat16)
-    return out
-
-
-class _Conv:
-    """One convolution: weight matrix, bias, geometry (cin, temporal taps, spatial kernel)."""
-
-    def __init__(self, sd, prefix, dev, n_pad=None):
-        w = sd[prefix + ".weight"].to(dev)
-        self.kt = w.shape[2] if w.dim() == 5 else 1
-        self.ks = w.shape[-1]
-        self.cin, self.cout = w.shape[1], w.shape[0]
-        self.w = _conv_w(w, n_pad)
-        b = sd.get(prefix + ".bias")
-        self.b = _vec(b.to(dev), n_pad) if b is not None else None
-
-
-class _Norm:
-    def __init__(self, sd, prefix, dev, eps):
-        self.g = sd[prefix + ".weight"].to(dev).to(torch.bfloat16).contiguous()
-        self.b = sd[prefix + ".bias"].to(dev).to(torch.bfloat16).contiguous()
-        self.eps = eps
-
-
-class _Res:
-    """norm1 -> SiLU -> conv1 -> norm2 -> SiLU -> conv2 (+ shortcut): ResBlock (autoencoder_kl_open_sora.py:127-164, GroupNorm
-    eps 1e-5, bias-free causal 3x3x3 convs, ``conv3``) and diffusers ResnetBlock2D (eps 1e-6, ``conv_shortcut``)."""
-
-    def __init__(self, sd, prefix, dev, three_d):
-        sub = ".conv" if three_d else ""
-        eps = 1e-5 if three_d else 1e-6
-        self.n1 = _Norm(sd, prefix + ".norm1", dev, eps)
-        self.c1 = _Conv(sd, prefix + ".conv1" + sub, dev)
-        self.n2 = _Norm(sd, prefix + ".norm2", dev, eps)
-        self.c2 = _Conv(sd, prefix + ".conv2" + sub, dev)
-        sk = prefix + (".conv3.conv" if three_d else ".conv_shortcut")
-        self.sc = _Conv(sd, sk, dev) if (sk + ".weight") in sd else None
-
-
-class OpenSoraVAE:
+class OpenSoraVAE(_SpatialDecoder):
     """Decode side of VideoAutoencoderPipeline; ``decode(z, num_frames)`` as autoencoder_kl_open_sora.py:672-695."""
 
     micro_frame_size = 17
@@ -109,15 +75,12 @@ class OpenSoraVAE:
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", micro_frame_size: int = 17, micro_batch_size: int = 4,
                  frames_per_launch: int = 16):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("videosys_amd.OpenSoraVAE needs a HIP device (no CPU path)")
-        self.device = dev
+        super().__init__(device)
+        dev = self.device
         self.micro_frame_size = micro_frame_size
         self.micro_batch_size = micro_batch_size   # kept for API parity; frames are independent in the 2-D decoder
         self.frames_per_launch = frames_per_launch
         self.micro_z_frame_size = self.get_temporal_latent_size(micro_frame_size)
-        self._padded: Dict[tuple, tuple] = {}
         self._init_temporal(state_dict, dev)
         self._init_spatial(state_dict, dev, "spatial_vae.module.")
         self.has_encoder = "temporal_vae.encoder.conv_in.conv.weight" in state_dict and \
@@ -139,32 +102,6 @@ class OpenSoraVAE:
         self.t_norm = _Norm(sd, d + "norm1", dev, 1e-5)
         self.t_out = _Conv(sd, d + "conv_out.conv", dev, n_pad=128)
 
-    def _init_spatial(self, sd, dev, s):
-        """2-D SD / SDXL decoder (diffusers AutoencoderKL decode side) under key prefix ``s``."""
-        self.s_pq = (sd[s + "post_quant_conv.weight"].float().reshape(4, 4).cpu(), sd[s + "post_quant_conv.bias"].float().cpu())
-        d = s + "decoder."
-        self.s_conv_in_w = _conv_w(sd[d + "conv_in.weight"].to(dev), None, 64)   # K = 9 * 4 = 36 -> 64
-        self.s_conv_in_b = _vec(sd[d + "conv_in.bias"].to(dev))
-        self.s_mid = [_Res(sd, f"{d}mid_block.resnets.{i}", dev, False) for i in range(2)]
-        a = d + "mid_block.attentions.0."
-        self.a_norm = _Norm(sd, a + "group_norm", dev, 1e-6)
-        bf = lambda k: sd[k].to(dev).to(torch.bfloat16).contiguous()
-        self.a_wq, self.a_bq = bf(a + "to_q.weight"), bf(a + "to_q.bias")
-        self.a_wk, self.a_bk = bf(a + "to_k.weight"), bf(a + "to_k.bias")
-        self.a_wv = bf(a + "to_v.weight")
-        self.a_wo = bf(a + "to_out.0.weight")
-        # softmax rows sum to 1, so the value bias passes through the attention: P (V + 1 b_v^T) = P V + b_v; fold it into the
-        # output projection's bias (the transposed V^T = W_v X^T product has no per-column bias slot)
-        bo = sd[a + "to_out.0.bias"].to(dev).float() + self.a_wo.float() @ bf(a + "to_v.bias").float()
-        self.a_bo = bo.to(torch.bfloat16)
-        self.s_up = []
-        for i in range(4):
-            res = [_Res(sd, f"{d}up_blocks.{i}.resnets.{j}", dev, False) for j in range(3)]
-            upk = f"{d}up_blocks.{i}.upsamplers.0.conv"
-            self.s_up.append((res, _Conv(sd, upk, dev) if (upk + ".weight") in sd else None))
-        self.s_norm = _Norm(sd, d + "conv_norm_out", dev, 1e-6)
-        self.s_out = _Conv(sd, d + "conv_out", dev, n_pad=128)
-
     def _init_encoders(self, sd, dev):
         """Encode side: diffusers vae.Encoder + quant_conv under ``spatial_vae.module.`` and Encoder (:177-272) + quant_conv under
         ``temporal_vae.``.  The two 8-channel heads (conv_out / conv2, then the 1x1 quant convs) are padded to the 128-column tile."""
@@ -179,7 +116,7 @@ class OpenSoraVAE:
             dk = f"{e}down_blocks.{i}.downsamplers.0.conv"
             self.e_down.append((res, _Conv(sd, dk, dev) if (dk + ".weight") in sd else None))
         self.e_mid = [_Res(sd, f"{e}mid_block.resnets.{i}", dev, False) for i in range(2)]
-        self.e_attn = self._attn_weights(sd, e + "mid_block.attentions.0.", dev)
+        self.e_attn = AttnWeights.from_linear(sd, e + "mid_block.attentions.0.", dev)
         self.e_norm = _Norm(sd, e + "conv_norm_out", dev, 1e-6)
         self.e_out = _Conv(sd, e + "conv_out", dev, n_pad=128)
         q = "spatial_vae.module.quant_conv"
@@ -196,17 +133,6 @@ class OpenSoraVAE:
         self.te_quant_w = _conv_w(sd[q + ".weight"].to(dev), 128, 128)
         self.te_quant_b = _vec(sd[q + ".bias"].to(dev), 128)
 
-    @staticmethod
-    def _attn_weights(sd, a, dev):
-        """The single-head mid-block attention of the 2-D VAE: (norm, wq, bq, wk, bk, wv, wo, bo') with the value bias folded
-        into the output bias (softmax rows sum to 1: P (V + 1 b_v^T) = P V + b_v)."""
-        bf = lambda k: sd[k].to(dev).to(torch.bfloat16).contiguous()
-        wo = bf(a + "to_out.0.weight")
-        bo = sd[a + "to_out.0.bias"].to(dev).float() + wo.float() @ bf(a + "to_v.bias").float()
-        return SimpleNamespace(a_norm=_Norm(sd, a + "group_norm", dev, 1e-6), a_wq=bf(a + "to_q.weight"), a_bq=bf(a + "to_q.bias"),
-                               a_wk=bf(a + "to_k.weight"), a_bk=bf(a + "to_k.bias"), a_wv=bf(a + "to_v.weight"), a_wo=wo,
-                               a_bo=bo.to(torch.bfloat16))
-
     # ------------------------------------------------------------------------------------------------ sizes
     def get_temporal_latent_size(self, t: int) -> int:
         pad = 0 if t % self.time_downsample_factor == 0 else self.time_downsample_factor - t % self.time_downsample_factor
@@ -222,43 +148,6 @@ class OpenSoraVAE:
         if T % self.micro_frame_size > 0:
             t += self.get_temporal_latent_size(T % self.micro_frame_size)
         return [t, h, w]
-
-    # ------------------------------------------------------------------------------------------------ building blocks
-    def clear_cache(self):
-        """Drop the zero-bordered staging buffers (they are kept per geometry; call after changing resolution to free HBM)."""
-        self._padded.clear()
-
-    def _padded_buf(self, g: VaeGrid, C: int):
-        """Zero-bordered conv-input buffer for grid g, allocated once per geometry (kernels only ever write its interior)."""
-        key = (g.n, g.T, g.H, g.W, g.tf, C)
-        hit = self._padded.get(key)
-        if hit is None:
-            hit = g.alloc(C, self.device, zero=True)
-            self._padded[key] = hit
-        return hit[1]
-
-    def _norm_act(self, x, gx: VaeGrid, norm: _Norm, C: int, tf: int, silu=True, dense=False):
-        gd = VaeGrid(gx.n, gx.T, gx.H, gx.W, 0 if dense else 1, 0 if dense else tf)
-        y = torch.empty(gd.rows, C, dtype=torch.bfloat16, device=self.device) if dense else self._padded_buf(gd, C)
-        ops.group_norm(x, gx, y, gd, C, norm.g, norm.b, norm.eps, silu)
-        return y, gd
-
-    def _resblock(self, x, gx: VaeGrid, r: _Res):
-        """x rows over gx (any layout) -> rows over the conv-output grid (pad 1, tf 0)."""
-        tf = r.c1.kt - 1
-        h, gh = self._norm_act(x, gx, r.n1, r.c1.cin, tf)
-        y = ops.conv(h, gh, r.c1.w, r.c1.b, r.c1.cin, r.c1.kt, r.c1.ks)
-        go = gh.conv_out()
-        h2, gh2 = self._norm_act(y, go, r.n2, r.c2.cin, tf)
-        if gx.pad != 1 or gx.tf != 0:   # the residual is added row-for-row in the conv-output layout
-            xr = torch.empty(go.rows, x.shape[1], dtype=torch.bfloat16, device=self.device)
-            ops.regrid(x, gx, xr, go, x.shape[1])
-            x = xr
-        res = x
-        if r.sc is not None:
-            res = ops.gemm128(x, r.sc.w, r.sc.b)
-        out = ops.conv(h2, gh2, r.c2.w, r.c2.b, r.c2.cin, r.c2.kt, r.c2.ks, res=res)
-        return out, go
 
     # ------------------------------------------------------------------------------------------------ temporal VAE
     def _temporal_decode(self, z4: torch.Tensor, num_frames: int, out: torch.Tensor, f0: int) -> int:
@@ -289,62 +178,6 @@ class OpenSoraVAE:
         y = ops.conv(h, gh, self.t_out.w, self.t_out.b, 128, 3, 3)
         ops.extract_planar(y, gh.conv_out(), 4, tpad, out, f0)
         return g.T - tpad
-
-    # ------------------------------------------------------------------------------------------------ 2-D decoder
-    def _attention(self, x, g: VaeGrid, aw=None):
-        """diffusers Attention (1 head, d = C = 512) with residual (``aw``: another mid block's weights, default the decoder's); x rows over g -> dense rows whose per-frame stride is the
-        token count rounded up to the 128-column GEMM tile (pad rows are zero on input, finite junk on output)."""
-        C, L, n = 512, g.H * g.W, g.n
-        Lp = (L + 127) // 128 * 128
-        gdn = VaeGrid(n, 1, g.H, g.W, 0, 0, sample_rows=Lp)
-        key = ("attn", n, g.H, g.W)
-        bufs = self._padded.get(key)
-        if bufs is None:   # pad rows must be zero (and stay zero: kernels write the L interior rows only)
-            bufs = (torch.zeros(gdn.rows, C, dtype=torch.bfloat16, device=self.device),
-                    torch.zeros(gdn.rows, C, dtype=torch.bfloat16, device=self.device))
-            self._padded[key] = bufs
-        hn, xd = bufs
-        A = aw if aw is not None else self
-        ops.group_norm(x, g, hn, gdn, C, A.a_norm.g, A.a_norm.b, A.a_norm.eps, False)
-        ops.regrid(x, g, xd, gdn, C)
-        q = ops.gemm128(hn, A.a_wq, A.a_bq)
-        k = ops.gemm128(hn, A.a_wk, A.a_bk)
-        vt = torch.empty(n, C, Lp, dtype=torch.bfloat16, device=self.device)   # V^T per frame = W_v X^T (pad columns = 0)
-        ops.gemm128(A.a_wv, hn.view(n, Lp, C), out=vt, batch=n, batch_a=0, batch_w=Lp * C, batch_o=C * Lp, M=C)
-        o = torch.empty(n * Lp, C, dtype=torch.bfloat16, device=self.device)
-        step = max(1, min(n, (1 << 28) // (Lp * Lp)))          # <= 1 GiB of fp32 scores at a time
-        for f in range(0, n, step):
-            m = min(step, n - f)
-            s = torch.empty(m, Lp, Lp, dtype=torch.float32, device=self.device)
-            ops.gemm128(q[f * Lp:(f + m) * Lp].view(m, Lp, C), k[f * Lp:(f + m) * Lp].view(m, Lp, C), out_f32=s,
-                        out_scale=1.0 / math.sqrt(C), batch=m, batch_a=Lp * C, batch_w=Lp * C, batch_o=Lp * Lp, M=Lp)
-            p = ops.softmax_rows(s, n=L)
-            ops.gemm128(p, vt[f:f + m], out=o[f * Lp:(f + m) * Lp].view(m, Lp, C), batch=m, batch_a=Lp * Lp, batch_w=C * Lp,
-                        batch_o=Lp * C, M=Lp)
-        return ops.gemm128(o, A.a_wo, A.a_bo, res=xd), gdn
-
-    def _spatial_decode(self, xz: torch.Tensor, out: torch.Tensor, f0: int, in_scale: float = 1.0 / _SD_SCALE):
-        """xz planar bf16 [4, F, H, W] -> out[3, f0:f0+F, 8H, 8W].  VideoAutoencoderKL.decode :522-538 + diffusers Decoder."""
-        _, F, H, W = xz.shape
-        params = [in_scale] * 4 + [0.0] * 4 + self.s_pq[0].flatten().tolist() + self.s_pq[1].tolist()
-        a = ops.vae_first_im2col(xz, 1, 64, params)
-        g = VaeGrid(F, 1, H, W, 0, 0)
-        x = ops.gemm128(a, self.s_conv_in_w, self.s_conv_in_b)
-        x, g = self._resblock(x, g, self.s_mid[0])
-        x, g = self._attention(x, g)
-        x, g = self._resblock(x, g, self.s_mid[1])
-        for res, up in self.s_up:
-            for r in res:
-                x, g = self._resblock(x, g, r)
-            if up is not None:
-                gp = VaeGrid(F, 1, 2 * g.H, 2 * g.W, 1, 0)
-                xp = self._padded_buf(gp, up.cin)
-                ops.regrid(x, g, xp, gp, up.cin, up=1)
-                x = ops.conv(xp, gp, up.w, up.b, up.cin, 1, 3)
-                g = gp.conv_out()
-        h, gh = self._norm_act(x, g, self.s_norm, 128, 0)
-        y = ops.conv(h, gh, self.s_out.w, self.s_out.b, 128, 1, 3)
-        ops.extract_planar(y, gh.conv_out(), 3, 0, out, f0)
 
     # ------------------------------------------------------------------------------------------------ public
     @torch.no_grad()
@@ -584,21 +417,17 @@ def OpenSoraVAE_V1_2(micro_batch_size=4, micro_frame_size=17, from_pretrained=No
     return OpenSoraVAE(sd, device=device, micro_frame_size=micro_frame_size, micro_batch_size=micro_batch_size)
 
 
-class AutoencoderKLDecoder(OpenSoraVAE):
+class AutoencoderKLDecoder(_SpatialDecoder):
     """Per-frame decode with a diffusers ``AutoencoderKL`` (SD / SDXL VAE geometry, state-dict keys ``decoder.*``,
     ``post_quant_conv.*``) — what LattePipeline.decode_latents does with ``enable_vae_temporal_decoder=False``
     (pipeline_latte.py:916-927: latents / scaling_factor, every frame through ``vae.decode``, ``(x / 2 + 0.5).clamp(0, 1) * 255``
-    as uint8 [b, f, h, w, c]).  The 2-D decoder kernels are the ones of OpenSoraVAE."""
+    as uint8 [b, f, h, w, c]).  The 2-D decoder is the one OpenSoraVAE runs after its temporal VAE."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", scaling_factor: float = 0.18215, frames_per_launch: int = 16):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("videosys_amd.AutoencoderKLDecoder needs a HIP device (no CPU path)")
-        self.device = dev
+        super().__init__(device)
         self.frames_per_launch = frames_per_launch
         self.scaling_factor = scaling_factor
-        self._padded = {}
-        self._init_spatial(state_dict, dev, "")
+        self._init_spatial(state_dict, self.device, "")
 
     @torch.no_grad()
     def decode(self, latents: torch.Tensor) -> torch.Tensor:
@@ -629,69 +458,25 @@ def decoder_param_shapes() -> Dict[str, tuple]:
     """Names and shapes of every decode-side parameter of the reference VideoAutoencoderPipeline (checked against the reference's
     own state_dict in tests/test_vae_cpu.py)."""
     p: Dict[str, tuple] = {}
-
-    def conv3(name, ci, co, k, bias):
-        p[name + ".conv.weight"] = (co, ci, k, k, k)
-        if bias:
-            p[name + ".conv.bias"] = (co,)
-
-    def norm(name, c):
-        p[name + ".weight"] = (c,)
-        p[name + ".bias"] = (c,)
-
-    def res3(name, ci, co):
-        norm(name + ".norm1", ci); conv3(name + ".conv1", ci, co, 3, False)
-        norm(name + ".norm2", co); conv3(name + ".conv2", co, co, 3, False)
-        if ci != co:
-            conv3(name + ".conv3", ci, co, 1, False)
-
     t = "temporal_vae."
-    conv3(t + "post_quant_conv", 4, 4, 1, True)
+    conv3(p, t + "post_quant_conv", 4, 4, 1)
     d = t + "decoder."
-    conv3(d + "conv1", 4, 512, 3, True)
+    conv3(p, d + "conv1", 4, 512, 3)
     for i in range(4):
-        res3(f"{d}res_blocks.{i}", 512, 512)
+        res3(p, f"{d}res_blocks.{i}", 512, 512)
     prev = 512
     for i in (3, 2, 1, 0):
         f = 128 * (1, 2, 2, 4)[i]
         for j in range(4):
-            res3(f"{d}block_res_blocks.{i}.{j}", prev, f)
+            res3(p, f"{d}block_res_blocks.{i}.{j}", prev, f)
             prev = f
         if i > 0 and (False, True, True)[i - 1]:
-            conv3(f"{d}conv_blocks.{i - 1}", prev, prev * 2, 3, True)
-    norm(d + "norm1", 128)
-    conv3(d + "conv_out", 128, 4, 3, True)
-
-    def conv2(name, ci, co, k):
-        p[name + ".weight"] = (co, ci, k, k)
-        p[name + ".bias"] = (co,)
-
-    def res2(name, ci, co):
-        norm(name + ".norm1", ci); conv2(name + ".conv1", ci, co, 3)
-        norm(name + ".norm2", co); conv2(name + ".conv2", co, co, 3)
-        if ci != co:
-            conv2(name + ".conv_shortcut", ci, co, 1)
-
+            conv3(p, f"{d}conv_blocks.{i - 1}", prev, prev * 2, 3)
+    norm(p, d + "norm1", 128)
+    conv3(p, d + "conv_out", 128, 4, 3)
     s = "spatial_vae.module."
-    conv2(s + "post_quant_conv", 4, 4, 1)
-    d = s + "decoder."
-    conv2(d + "conv_in", 4, 512, 3)
-    res2(d + "mid_block.resnets.0", 512, 512)
-    a = d + "mid_block.attentions.0."
-    norm(a + "group_norm", 512)
-    for n in ("to_q", "to_k", "to_v", "to_out.0"):
-        p[a + n + ".weight"] = (512, 512)
-        p[a + n + ".bias"] = (512,)
-    res2(d + "mid_block.resnets.1", 512, 512)
-    prev = 512
-    for i, co in enumerate((512, 512, 256, 128)):
-        for j in range(3):
-            res2(f"{d}up_blocks.{i}.resnets.{j}", prev, co)
-            prev = co
-        if i < 3:
-            conv2(f"{d}up_blocks.{i}.upsamplers.0.conv", co, co, 3)
-    norm(d + "conv_norm_out", 128)
-    conv2(d + "conv_out", 128, 3, 3)
+    conv2(p, s + "post_quant_conv", 4, 4, 1)
+    p.update(diffusers_decoder_shapes(s + "decoder.", 4))
     return p
 
 
@@ -700,96 +485,50 @@ def encoder_param_shapes() -> Dict[str, tuple]:
     own state_dict in tests/test_vae_cpu.py): the diffusers vae.Encoder + quant_conv and the temporal Encoder (:177-256) +
     quant_conv."""
     p: Dict[str, tuple] = {}
-
-    def norm(name, c):
-        p[name + ".weight"] = (c,)
-        p[name + ".bias"] = (c,)
-
-    def conv2(name, ci, co, k):
-        p[name + ".weight"] = (co, ci, k, k)
-        p[name + ".bias"] = (co,)
-
-    def res2(name, ci, co):
-        norm(name + ".norm1", ci); conv2(name + ".conv1", ci, co, 3)
-        norm(name + ".norm2", co); conv2(name + ".conv2", co, co, 3)
-        if ci != co:
-            conv2(name + ".conv_shortcut", ci, co, 1)
-
     s = "spatial_vae.module."
     e = s + "encoder."
-    conv2(e + "conv_in", 3, 128, 3)
+    conv2(p, e + "conv_in", 3, 128, 3)
     prev = 128
     for i, co in enumerate((128, 256, 512, 512)):
         for j in range(2):
-            res2(f"{e}down_blocks.{i}.resnets.{j}", prev, co)
+            res2(p, f"{e}down_blocks.{i}.resnets.{j}", prev, co)
             prev = co
         if i < 3:
-            conv2(f"{e}down_blocks.{i}.downsamplers.0.conv", co, co, 3)
-    res2(e + "mid_block.resnets.0", 512, 512)
+            conv2(p, f"{e}down_blocks.{i}.downsamplers.0.conv", co, co, 3)
+    res2(p, e + "mid_block.resnets.0", 512, 512)
     a = e + "mid_block.attentions.0."
-    norm(a + "group_norm", 512)
+    norm(p, a + "group_norm", 512)
     for n in ("to_q", "to_k", "to_v", "to_out.0"):
         p[a + n + ".weight"] = (512, 512)
         p[a + n + ".bias"] = (512,)
-    res2(e + "mid_block.resnets.1", 512, 512)
-    norm(e + "conv_norm_out", 512)
-    conv2(e + "conv_out", 512, 8, 3)
-    conv2(s + "quant_conv", 8, 8, 1)
-
-    def conv3(name, ci, co, k, bias):
-        p[name + ".conv.weight"] = (co, ci, k, k, k)
-        if bias:
-            p[name + ".conv.bias"] = (co,)
-
-    def res3(name, ci, co):
-        norm(name + ".norm1", ci); conv3(name + ".conv1", ci, co, 3, False)
-        norm(name + ".norm2", co); conv3(name + ".conv2", co, co, 3, False)
-        if ci != co:
-            conv3(name + ".conv3", ci, co, 1, False)
-
+    res2(p, e + "mid_block.resnets.1", 512, 512)
+    norm(p, e + "conv_norm_out", 512)
+    conv2(p, e + "conv_out", 512, 8, 3)
+    conv2(p, s + "quant_conv", 8, 8, 1)
     t = "temporal_vae."
     e = t + "encoder."
-    conv3(e + "conv_in", 4, 128, 3, False)
+    conv3(p, e + "conv_in", 4, 128, 3, False)
     prev = 128
     for i in range(4):
         f = 128 * (1, 2, 2, 4)[i]
         for j in range(4):
-            res3(f"{e}block_res_blocks.{i}.{j}", prev, f)
+            res3(p, f"{e}block_res_blocks.{i}.{j}", prev, f)
             prev = f
         if i < 3 and (False, True, True)[i]:
-            conv3(f"{e}conv_blocks.{i}", prev, f, 3, True)
+            conv3(p, f"{e}conv_blocks.{i}", prev, f, 3)
     for i in range(4):
-        res3(f"{e}res_blocks.{i}", 512, 512)
-    norm(e + "norm1", 512)
-    conv3(e + "conv2", 512, 8, 1, True)
-    conv3(t + "quant_conv", 8, 8, 1, True)
+        res3(p, f"{e}res_blocks.{i}", 512, 512)
+    norm(p, e + "norm1", 512)
+    conv3(p, e + "conv2", 512, 8, 1)
+    conv3(p, t + "quant_conv", 8, 8, 1)
     return p
 
 
 def synth_state_dict(seed: int = 0, encoder: bool = False) -> Dict[str, torch.Tensor]:
-    """Deterministic random weights (bf16-representable fp32): conv / linear weights N(0, 1/fan_in), biases N(0, 0.02), norm
-    scales 1 + N(0, 0.1), norm shifts N(0, 0.1).  No checkpoint can be fetched here (no network).  The decode-side values do
-    not depend on ``encoder`` (the encode-side ones come from their own generator)."""
-    sd = _synth(decoder_param_shapes(), torch.Generator().manual_seed(seed))
+    """Deterministic random weights (vae_blocks.synth_weights: bf16-representable fp32, conv / linear weights N(0, 1/fan_in), biases
+    N(0, 0.02), norm scales 1 + N(0, 0.1), norm shifts N(0, 0.1)).  No checkpoint can be fetched here (no network).  The decode-side
+    values do not depend on ``encoder`` (the encode-side ones come from their own generator)."""
+    sd = synth_weights(decoder_param_shapes(), torch.Generator().manual_seed(seed))
     if encoder:
-        sd.update(_synth(encoder_param_shapes(), torch.Generator().manual_seed(seed + 7919)))
-    return sd
-
-
-def _synth(shapes, g) -> Dict[str, torch.Tensor]:
-    sd = {}
-    for k, shp in shapes.items():
-        is_norm = ".norm" in k or "group_norm" in k or "conv_norm_out" in k
-        if k.endswith(".weight") and len(shp) >= 2:
-            fan_in = 1
-            for s in shp[1:]:
-                fan_in *= s
-            v = torch.randn(shp, generator=g) / math.sqrt(fan_in)
-        elif k.endswith(".weight") and is_norm:
-            v = 1.0 + 0.1 * torch.randn(shp, generator=g)
-        elif is_norm:
-            v = 0.1 * torch.randn(shp, generator=g)
-        else:
-            v = 0.02 * torch.randn(shp, generator=g)
-        sd[k] = v.to(torch.bfloat16).float()
+        sd.update(synth_weights(encoder_param_shapes(), torch.Generator().manual_seed(seed + 7919)))
     return sd

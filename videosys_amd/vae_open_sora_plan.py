@@ -23,10 +23,13 @@ Layout and kernels (DESIGN.md "Open-Sora-Plan CausalVAE decode"):
 Channel counts below 128 (``hidden_size`` 32 or 64 — the test geometry; the published model has 128) run in a 128-column physical
 layout in which every GroupNorm group's channels are repeated to fill four columns (``_ChanMap``): the GEMM tile is 128 columns wide
 anyway, a group of repeated channels has the mean and variance of the group itself, and a consumer's weights are zero on the copies.
-No kernel changes, no extra launches; at ``hidden_size`` 128 the map is the identity.  There is no CPU path."""
+No kernel changes, no extra launches; at ``hidden_size`` 128 the map is the identity.
+
+The residual block, the staging cache, the attention core (with the mask for key counts that are no multiple of four) and the tile
+stitching are the shared ones of vae_blocks.py; this module adds the channel map, the causal front frames (``_norm_act``), the
+whole-sample GroupNorm around the attention core and the tiling geometry.  There is no CPU path."""
 from __future__ import annotations
 
-import math
 from types import SimpleNamespace
 from typing import Dict, Optional
 
@@ -35,7 +38,7 @@ import torch
 from . import ops
 from . import open_sora_plan_ops as oops
 from .ops import VaeGrid
-from .vae_open_sora import _synth
+from .vae_blocks import AttnWeights, VaeBlocks, _vec, attention_core, conv3, norm, stitch_tiles, synth_weights
 
 SCALE = 0.18215                      # CausalVAEModelWrapper.decode :1131
 Z_CHANNELS = 4
@@ -113,15 +116,14 @@ class _CConv:
         m = w.permute(0, 2, 3, 4, 1).reshape(w.shape[0], -1)
         self.w = torch.zeros(n, m.shape[1], dtype=torch.bfloat16, device=dev)
         self.w[:m.shape[0]] = m.to(torch.bfloat16)
-        self.b = torch.zeros(n, dtype=torch.bfloat16, device=dev)
-        self.b[:b.numel()] = b.to(torch.bfloat16)
+        self.b = _vec(b, n)
 
 
 class _CNorm:
     def __init__(self, sd, key, dev, cm: _ChanMap):
         self.g = cm.out_rows(sd[key + ".weight"]).to(dev).to(torch.bfloat16).contiguous()
         self.b = cm.out_rows(sd[key + ".bias"]).to(dev).to(torch.bfloat16).contiguous()
-        self.C = cm.P
+        self.C, self.eps = cm.P, 1e-6
 
 
 class _CRes:
@@ -131,15 +133,14 @@ class _CRes:
         self.sc = _CConv(sd, p + ".nin_shortcut", dev, ci, co) if (p + ".nin_shortcut.conv.weight") in sd else None
 
 
-class CausalVAEDecoder:
+class CausalVAEDecoder(VaeBlocks):
     """Decode side of the reference ``CausalVAEModel``: ``decode(z)``, z [B, 4, T, H, W] (already divided by 0.18215 unless
     ``in_scale`` says otherwise) -> [B, 3, 4(T-1)+1, 8H, 8W] bf16, with the reference's tiling attributes."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", hidden_size: Optional[int] = None, **config):
         _check_config(config)
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("videosys_amd.CausalVAEDecoder needs a HIP device (no CPU path)")
+        super().__init__(device)
+        dev = self.device
         sd = state_dict
         hs = sd["decoder.conv_out.conv.weight"].shape[1]
         if hidden_size is not None and hidden_size != hs:
@@ -147,7 +148,7 @@ class CausalVAEDecoder:
         missing = sorted(set(decoder_param_shapes(hs)) - set(sd))
         if missing:
             raise KeyError(f"CausalVAE decoder: the state dict lacks {missing[:4]}{' ...' if len(missing) > 4 else ''}")
-        self.device, self.hidden_size = dev, hs
+        self.hidden_size = hs
         self.config = SimpleNamespace(hidden_size=hs, z_channels=Z_CHANNELS, hidden_size_mult=HIDDEN_SIZE_MULT)
         self.dtype = torch.bfloat16
         # CausalVAEModel.__init__ :798-806
@@ -157,7 +158,6 @@ class CausalVAEDecoder:
         self.tile_latent_min_size_t = 16
         self.tile_overlap_factor = 0.125
         self.use_tiling = False
-        self._padded: Dict[tuple, tuple] = {}
         self.pq = (sd["post_quant_conv.conv.weight"].float().reshape(4, 4).cpu(), sd["post_quant_conv.conv.bias"].float().cpu())
         d = "decoder."
         cm = {c: _ChanMap(c) for c in {hs * m for m in HIDDEN_SIZE_MULT}}
@@ -170,9 +170,7 @@ class CausalVAEDecoder:
         self.mid = [_CRes(sd, f"{d}mid.block_{i}", dev, top, top) for i in (1, 2)]
         a = d + "mid.attn_1."
         lin = lambda n: _CConv(sd, a + n, dev, top, top)
-        self.a_norm, self.a_q, self.a_k, self.a_v, self.a_o = _CNorm(sd, a + "norm", dev, top), lin("q"), lin("k"), lin("v"), lin("proj_out")
-        # softmax rows sum to 1, so the value bias passes through the attention: fold it into the output projection's bias
-        self.a_bo = (self.a_o.b.float() + self.a_o.w.float() @ self.a_v.b.float()).to(torch.bfloat16)
+        self.attn = AttnWeights.from_convs(_CNorm(sd, a + "norm", dev, top), lin("q"), lin("k"), lin("v"), lin("proj_out"))
         self.ups = []
         prev = top
         for lvl in (3, 2, 1, 0):
@@ -193,19 +191,7 @@ class CausalVAEDecoder:
     def disable_tiling(self):
         self.enable_tiling(False)
 
-    def clear_cache(self):
-        """Drop the zero-bordered staging buffers (they are kept per geometry; call after changing resolution to free HBM)."""
-        self._padded.clear()
-
     # ------------------------------------------------------------------------------------------------ building blocks
-    def _padded_buf(self, g: VaeGrid, C: int):
-        key = (g.n, g.T, g.H, g.W, g.tf, C)
-        hit = self._padded.get(key)
-        if hit is None:
-            hit = g.alloc(C, self.device, zero=True)
-            self._padded[key] = hit
-        return hit[1]
-
     @staticmethod
     def _front(rows, g: VaeGrid):
         """CausalConv3d.forward :94-97: the g.tf frames in front of the conv's input are copies of its first frame."""
@@ -213,66 +199,30 @@ class CausalVAEDecoder:
             v = rows.view(g.T + g.tf, g.Hp, g.Wp, rows.shape[1])
             v[:g.tf].copy_(v[g.tf:g.tf + 1].expand(g.tf, -1, -1, -1))
 
-    def _norm_act(self, x, gx: VaeGrid, nm: _CNorm, tf: int, silu=True):
-        gd = VaeGrid(1, gx.T, gx.H, gx.W, 1, tf)
-        y = self._padded_buf(gd, nm.C)
-        ops.group_norm(x, gx, y, gd, nm.C, nm.g, nm.b, 1e-6, silu)
+    def _norm_act(self, x, gx: VaeGrid, norm, C: int, tf: int, silu=True, dense=False):
+        """GroupNorm over all frames of the sample (+ SiLU) into the padded conv-input grid, then the causal front frames.
+        With it the shared ``_resblock`` is ResnetBlock3D.forward :295-315."""
+        y, gd = super()._norm_act(x, gx, norm, C, tf, silu, dense)
         self._front(y, gd)
         return y, gd
 
     def _conv(self, h, gh: VaeGrid, cv: _CConv, res=None):
         return ops.conv(h, gh, cv.w, cv.b, cv.cin, cv.kt, cv.ks, res=res)
 
-    def _resnet(self, x, gx: VaeGrid, r: _CRes):
-        """ResnetBlock3D.forward :295-315; x rows over gx (any layout) -> rows over the conv-output grid (pad 1, no front frames)."""
-        h, gh = self._norm_act(x, gx, r.n1, 2)
-        y = self._conv(h, gh, r.c1)
-        go = gh.conv_out()
-        h2, gh2 = self._norm_act(y, go, r.n2, 2)
-        if gx.pad != 1 or gx.tf != 0:          # the residual is added row-for-row in the conv-output layout
-            xr = torch.empty(go.rows, x.shape[1], dtype=torch.bfloat16, device=self.device)
-            ops.regrid(x, gx, xr, go, x.shape[1])
-            x = xr
-        res = x if r.sc is None else ops.gemm128(x, r.sc.w, r.sc.b)
-        return self._conv(h2, gh2, r.c2, res=res), go
-
-    def _attention(self, x, g: VaeGrid):
+    def _attention(self, x, g: VaeGrid, aw: AttnWeights):
         """AttnBlock3DFix.forward :375-415 with its residual: one head of width C per frame.  x rows over g (pad 1, no front frames)
         -> dense rows.  Inside, a frame takes the key count rounded up to the 128-column GEMM tile (pad rows zero on input)."""
-        C, L, n = self.a_norm.C, g.H * g.W, g.T
+        C, L, n = aw.C, g.H * g.W, g.T
         Lp = check_attention_keys(g.H, g.W)
         gf = VaeGrid(n, 1, g.H, g.W, g.pad, 0, sample_rows=g.plane)                 # the same rows, one sample per frame
         gdn = VaeGrid(n, 1, g.H, g.W, 0, 0, sample_rows=Lp)
-        key = ("attn", n, g.H, g.W)
-        bufs = self._padded.get(key)
-        if bufs is None:   # pad rows must be zero (and stay zero: kernels write the L interior rows only)
-            bufs = (torch.zeros(gdn.rows, C, dtype=torch.bfloat16, device=self.device),
-                    torch.zeros(gdn.rows, C, dtype=torch.bfloat16, device=self.device))
-            self._padded[key] = bufs
-        hn, xd = bufs
+        hn, xd = self._attn_bufs(n, g.H, g.W, C, Lp)
         gn1 = VaeGrid(1, n, g.H, g.W, 0, 0)
         stage = torch.empty(gn1.rows, C, dtype=torch.bfloat16, device=self.device)
-        ops.group_norm(x, g, stage, gn1, C, self.a_norm.g, self.a_norm.b, 1e-6, False)    # statistics over all frames of the sample
+        ops.group_norm(x, g, stage, gn1, C, aw.norm.g, aw.norm.b, aw.norm.eps, False)      # statistics over all frames of the sample
         ops.regrid(stage, VaeGrid(n, 1, g.H, g.W, 0, 0), hn, gdn, C)                       # ... then one frame per Lp rows
         ops.regrid(x, gf, xd, gdn, C)
-        q = ops.gemm128(hn, self.a_q.w, self.a_q.b)
-        k = ops.gemm128(hn, self.a_k.w, self.a_k.b)
-        vt = torch.empty(n, C, Lp, dtype=torch.bfloat16, device=self.device)       # V^T per frame = W_v X^T (pad columns = 0)
-        ops.gemm128(self.a_v.w, hn.view(n, Lp, C), out=vt, batch=n, batch_a=0, batch_w=Lp * C, batch_o=C * Lp, M=C)
-        o = torch.empty(n * Lp, C, dtype=torch.bfloat16, device=self.device)
-        L4 = (L + 3) // 4 * 4
-        step = max(1, min(n, (1 << 28) // (Lp * Lp)))                               # <= 1 GiB of fp32 scores at a time
-        for f in range(0, n, step):
-            m = min(step, n - f)
-            s = torch.empty(m, Lp, Lp, dtype=torch.float32, device=self.device)
-            ops.gemm128(q[f * Lp:(f + m) * Lp].view(m, Lp, C), k[f * Lp:(f + m) * Lp].view(m, Lp, C), out_f32=s,
-                        out_scale=1.0 / math.sqrt(C), batch=m, batch_a=Lp * C, batch_w=Lp * C, batch_o=Lp * Lp, M=Lp)
-            if L4 != L:    # the softmax kernel counts keys in fours: a key count like 3 x 2 (an edge tile) masks its last columns
-                s[:, :, L:L4] = -3.0e38
-            p = ops.softmax_rows(s, n=L4)
-            ops.gemm128(p, vt[f:f + m], out=o[f * Lp:(f + m) * Lp].view(m, Lp, C), batch=m, batch_a=Lp * Lp, batch_w=C * Lp,
-                        batch_o=Lp * C, M=Lp)
-        y = ops.gemm128(o, self.a_o.w, self.a_bo, res=xd)
+        y = attention_core(hn, xd, n, L, Lp, C, aw)
         # (a per-frame stride of Lp rows is no grid of ONE sample, and the next GroupNorm runs over the whole sample: frame-dense rows)
         out = torch.empty(gn1.rows, C, dtype=torch.bfloat16, device=self.device)
         ops.regrid(y, gdn, out, VaeGrid(n, 1, g.H, g.W, 0, 0), C)
@@ -287,12 +237,12 @@ class CausalVAEDecoder:
         a = ops.vae_first_im2col(zz, 3, _KCOLS, params)
         x = ops.gemm128(a, self.conv_in_w, self.conv_in_b)[2 * h * w:]
         g = VaeGrid(1, T, h, w, 0, 0)
-        x, g = self._resnet(x, g, self.mid[0])
-        x, g = self._attention(x, g)
-        x, g = self._resnet(x, g, self.mid[1])
+        x, g = self._resblock(x, g, self.mid[0])
+        x, g = self._attention(x, g, self.attn)
+        x, g = self._resblock(x, g, self.mid[1])
         for res, up, kind in self.ups:
             for r in res:
-                x, g = self._resnet(x, g, r)
+                x, g = self._resblock(x, g, r)
             if kind == "SpatialUpsample2x":                                          # :334-341 (a (1, 3, 3) conv: no front frames)
                 gu = VaeGrid(1, g.T, 2 * g.H, 2 * g.W, 1, 0)
                 xu = self._padded_buf(gu, up.cin)
@@ -304,7 +254,7 @@ class CausalVAEDecoder:
                 oops.upsample_trilinear2x(x, g, xu, gu, up.cin)
                 self._front(xu, gu)
                 x, g = self._conv(xu, gu, up), gu.conv_out()
-        hN, gN = self._norm_act(x, g, self.norm_out, 2)
+        hN, gN = self._norm_act(x, g, self.norm_out, self.norm_out.C, 2)
         y = self._conv(hN, gN, self.conv_out)
         out = torch.empty(3, g.T, g.H, g.W, dtype=torch.bfloat16, device=self.device)
         ops.extract_planar(y, gN.conv_out(), 3, 0, out, 0)
@@ -331,19 +281,7 @@ class CausalVAEDecoder:
         H, W = zb.shape[-2:]
         rows = [[self._decode_tile(zb[:, :, i:i + lat, j:j + lat].contiguous(), in_scale) for j in range(0, W, step)]
                 for i in range(0, H, step)]
-        out_rows = []
-        for i, row in enumerate(rows):
-            res = []
-            for j, tile in enumerate(row):
-                if i > 0:   # blend_v / blend_h modify the tile in place, so later tiles see the blended neighbours (:1035-1038)
-                    a = rows[i - 1][j]
-                    ops.blend_edge(a, tile, min(a.shape[-2], tile.shape[-2], ext), 0)
-                if j > 0:
-                    a = row[j - 1]
-                    ops.blend_edge(a, tile, min(a.shape[-1], tile.shape[-1], ext), 1)
-                res.append(tile[:, :, :lim, :lim])
-            out_rows.append(torch.cat(res, dim=3))
-        return torch.cat(out_rows, dim=2)
+        return stitch_tiles(rows, ext, ext, lim, lim)
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor, in_scale: float = 1.0) -> torch.Tensor:
@@ -415,16 +353,11 @@ def decoder_param_shapes(hidden_size: int = 128) -> Dict[str, tuple]:
     hs = hidden_size
 
     def cconv(name, ci, co, k):
-        p[name + ".conv.weight"] = (co, ci) + (k if isinstance(k, tuple) else (k, k, k))
-        p[name + ".conv.bias"] = (co,)
-
-    def norm(name, c):
-        p[name + ".weight"] = (c,)
-        p[name + ".bias"] = (c,)
+        conv3(p, name, ci, co, k)
 
     def res(name, ci, co):
-        norm(name + ".norm1", ci); cconv(name + ".conv1", ci, co, 3)
-        norm(name + ".norm2", co); cconv(name + ".conv2", co, co, 3)
+        norm(p, name + ".norm1", ci); cconv(name + ".conv1", ci, co, 3)
+        norm(p, name + ".norm2", co); cconv(name + ".conv2", co, co, 3)
         if ci != co:
             cconv(name + ".nin_shortcut", ci, co, 1)
 
@@ -432,7 +365,7 @@ def decoder_param_shapes(hidden_size: int = 128) -> Dict[str, tuple]:
     top = hs * HIDDEN_SIZE_MULT[-1]
     cconv(d + "conv_in", Z_CHANNELS, top, 3)
     res(d + "mid.block_1", top, top)
-    norm(d + "mid.attn_1.norm", top)
+    norm(p, d + "mid.attn_1.norm", top)
     for n in ("q", "k", "v", "proj_out"):
         cconv(f"{d}mid.attn_1.{n}", top, top, 1)
     res(d + "mid.block_2", top, top)
@@ -444,13 +377,13 @@ def decoder_param_shapes(hidden_size: int = 128) -> Dict[str, tuple]:
             prev = co
         if SPATIAL_UPSAMPLE[lvl]:
             cconv(f"{d}up.{lvl}.upsample.conv", co, co, (1, 3, 3) if SPATIAL_UPSAMPLE[lvl] == "SpatialUpsample2x" else 3)
-    norm(d + "norm_out", prev)
+    norm(p, d + "norm_out", prev)
     cconv(d + "conv_out", prev, 3, 3)
     cconv("post_quant_conv", Z_CHANNELS, Z_CHANNELS, 1)
     return p
 
 
 def synth_state_dict(seed: int = 0, hidden_size: int = 128) -> Dict[str, torch.Tensor]:
-    """Deterministic random decoder weights with the reference's names (bf16-representable fp32, the distributions of
-    vae_open_sora.synth_state_dict: norm scales 1 + N(0, 0.1), norm shifts N(0, 0.1)): no checkpoint can be fetched here."""
-    return _synth(decoder_param_shapes(hidden_size), torch.Generator().manual_seed(seed))
+    """Deterministic random decoder weights with the reference's names (vae_blocks.synth_weights: bf16-representable fp32, norm
+    scales 1 + N(0, 0.1), norm shifts N(0, 0.1)): no checkpoint can be fetched here."""
+    return synth_weights(decoder_param_shapes(hidden_size), torch.Generator().manual_seed(seed))

@@ -2,8 +2,9 @@
 ``AutoencoderKL`` at the Stable Diffusion 3 config — 16 latent channels, block_out_channels (128, 256, 512, 512), layers_per_block 2,
 scaling_factor 1.5305, shift_factor 0.0609, NO quant convs — decode side only.
 
-The decoder between its two ends is the 2-D decoder of vae_open_sora.py, reused unchanged (mid block with the 512-wide attention,
-four up blocks, GroupNorm + SiLU, conv_out on the implicit-GEMM convolution).  The two ends are their own kernels (csrc/vae_sd3.hip):
+The decoder between its two ends is the shared diffusers 2-D decoder body of vae_blocks.py (``Decoder2DWeights`` / ``_decoder2d``: mid
+block with the 512-wide attention, four up blocks, GroupNorm + SiLU, conv_out on the implicit-GEMM convolution), the one the Open-Sora
+and SVD decoders run as well.  The two ends are their own kernels (csrc/vae_sd3.hip):
 
   * ``vsys_vae_first_im2col_nc``: fp32 latents [F, 16, h, w] -> ``latents / scaling_factor + shift_factor`` with the reference's bf16
     roundings (:980 runs on bf16 latents) -> im2col rows of conv_in (16 -> 512, 3 x 3), which then is a plain GEMM over 160 columns;
@@ -21,7 +22,7 @@ import torch
 
 from . import ops, vchitect_ops as vops
 from .ops import VaeGrid
-from .vae_open_sora import OpenSoraVAE, _Conv, _Norm, _Res, _conv_w, _synth, _vec
+from .vae_blocks import Decoder2DWeights, VaeBlocks, _conv_w, _vec, diffusers_decoder_shapes, synth_weights
 
 LATENT_CHANNELS = 16
 BLOCK_OUT_CHANNELS = (128, 256, 512, 512)
@@ -29,14 +30,12 @@ SCALING_FACTOR, SHIFT_FACTOR = 1.5305, 0.0609
 _KCOLS = 160          # 9 taps x 16 channels = 144 -> the next multiple of the GEMM's 32-column K step
 
 
-class AutoencoderKLSD3Decoder(OpenSoraVAE):
+class AutoencoderKLSD3Decoder(VaeBlocks):
     """Decode side of diffusers ``AutoencoderKL`` at the SD3 config, state-dict keys ``decoder.*`` (diffusers' names)."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", scaling_factor: float = SCALING_FACTOR,
                  shift_factor: float = SHIFT_FACTOR, frames_per_launch: int = 8):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("videosys_amd.AutoencoderKLSD3Decoder needs a HIP device (no CPU path)")
+        super().__init__(device)
         quant = sorted(k for k in state_dict if k.startswith(("post_quant_conv.", "quant_conv.")))
         if quant:
             raise ValueError(f"the SD3 VAE has no quant convs (use_quant_conv / use_post_quant_conv are False), but the state dict holds "
@@ -44,52 +43,21 @@ class AutoencoderKLSD3Decoder(OpenSoraVAE):
         w_in = state_dict["decoder.conv_in.weight"]
         if tuple(w_in.shape[1:]) != (LATENT_CHANNELS, 3, 3) or w_in.shape[0] != BLOCK_OUT_CHANNELS[-1]:
             raise ValueError(f"decoder.conv_in.weight {tuple(w_in.shape)}: expected ({BLOCK_OUT_CHANNELS[-1]}, {LATENT_CHANNELS}, 3, 3)")
-        self.device = dev
         self.frames_per_launch = frames_per_launch
         self.config = SimpleNamespace(latent_channels=LATENT_CHANNELS, block_out_channels=BLOCK_OUT_CHANNELS, layers_per_block=2,
                                       scaling_factor=scaling_factor, shift_factor=shift_factor, use_quant_conv=False,
                                       use_post_quant_conv=False)
-        self._padded = {}
-        self._init_decoder(state_dict, dev)
-
-    def _init_decoder(self, sd, dev):
-        """OpenSoraVAE._init_spatial without the post_quant_conv and with the 16-channel conv_in (K = 144 -> 160)."""
-        d = "decoder."
-        self.s_conv_in_w = _conv_w(sd[d + "conv_in.weight"].to(dev), None, _KCOLS)
-        self.s_conv_in_b = _vec(sd[d + "conv_in.bias"].to(dev))
-        self.s_mid = [_Res(sd, f"{d}mid_block.resnets.{i}", dev, False) for i in range(2)]
-        a = self._attn_weights(sd, d + "mid_block.attentions.0.", dev)
-        self.a_norm, self.a_wq, self.a_bq, self.a_wk, self.a_bk = a.a_norm, a.a_wq, a.a_bq, a.a_wk, a.a_bk
-        self.a_wv, self.a_wo, self.a_bo = a.a_wv, a.a_wo, a.a_bo
-        self.s_up = []
-        for i in range(4):
-            res = [_Res(sd, f"{d}up_blocks.{i}.resnets.{j}", dev, False) for j in range(3)]
-            upk = f"{d}up_blocks.{i}.upsamplers.0.conv"
-            self.s_up.append((res, _Conv(sd, upk, dev) if (upk + ".weight") in sd else None))
-        self.s_norm = _Norm(sd, d + "conv_norm_out", dev, 1e-6)
-        self.s_out = _Conv(sd, d + "conv_out", dev, n_pad=128)
+        self.conv_in_w = _conv_w(w_in.to(self.device), None, _KCOLS)       # 16-channel conv_in: K = 144 -> 160
+        self.conv_in_b = _vec(state_dict["decoder.conv_in.bias"].to(self.device))
+        self.dec = Decoder2DWeights(state_dict, "decoder.", self.device)
 
     def _decode_rows(self, z: torch.Tensor, scaling: float, shift: float):
         """z fp32 [m, 16, h, w] -> (conv_out rows [rows, 128] whose first 3 columns are the pixel, their grid).  ``scaling`` / ``shift``:
         the pipeline's `latents / scaling_factor + shift_factor` (:980), or 1 / 0 when the caller hands over decoder inputs."""
         m, _, H, W = z.shape
         a = vops.vae_first_im2col_nc(z, _KCOLS, scaling, shift)
-        g = VaeGrid(m, 1, H, W, 0, 0)
-        x = ops.gemm128(a, self.s_conv_in_w, self.s_conv_in_b)
-        x, g = self._resblock(x, g, self.s_mid[0])
-        x, g = self._attention(x, g)
-        x, g = self._resblock(x, g, self.s_mid[1])
-        for res, up in self.s_up:
-            for r in res:
-                x, g = self._resblock(x, g, r)
-            if up is not None:
-                gp = VaeGrid(m, 1, 2 * g.H, 2 * g.W, 1, 0)
-                xp = self._padded_buf(gp, up.cin)
-                ops.regrid(x, g, xp, gp, up.cin, up=1)
-                x = ops.conv(xp, gp, up.w, up.b, up.cin, 1, 3)
-                g = gp.conv_out()
-        h, gh = self._norm_act(x, g, self.s_norm, 128, 0)
-        return ops.conv(h, gh, self.s_out.w, self.s_out.b, 128, 1, 3), gh.conv_out()
+        x = ops.gemm128(a, self.conv_in_w, self.conv_in_b)
+        return self._decoder2d(x, VaeGrid(m, 1, H, W, 0, 0), self.dec)
 
     def _check(self, z):
         if not z.is_cuda:
@@ -133,44 +101,10 @@ class AutoencoderKLSD3Decoder(OpenSoraVAE):
 
 def decoder_param_shapes() -> Dict[str, tuple]:
     """Names and shapes of the decode-side parameters of diffusers' AutoencoderKL at the SD3 config."""
-    p: Dict[str, tuple] = {}
-
-    def norm(name, c):
-        p[name + ".weight"] = (c,)
-        p[name + ".bias"] = (c,)
-
-    def conv2(name, ci, co, k):
-        p[name + ".weight"] = (co, ci, k, k)
-        p[name + ".bias"] = (co,)
-
-    def res2(name, ci, co):
-        norm(name + ".norm1", ci); conv2(name + ".conv1", ci, co, 3)
-        norm(name + ".norm2", co); conv2(name + ".conv2", co, co, 3)
-        if ci != co:
-            conv2(name + ".conv_shortcut", ci, co, 1)
-
-    d = "decoder."
-    conv2(d + "conv_in", LATENT_CHANNELS, 512, 3)
-    res2(d + "mid_block.resnets.0", 512, 512)
-    a = d + "mid_block.attentions.0."
-    norm(a + "group_norm", 512)
-    for n in ("to_q", "to_k", "to_v", "to_out.0"):
-        p[a + n + ".weight"] = (512, 512)
-        p[a + n + ".bias"] = (512,)
-    res2(d + "mid_block.resnets.1", 512, 512)
-    prev = 512
-    for i, co in enumerate(reversed(BLOCK_OUT_CHANNELS)):
-        for j in range(3):
-            res2(f"{d}up_blocks.{i}.resnets.{j}", prev, co)
-            prev = co
-        if i < 3:
-            conv2(f"{d}up_blocks.{i}.upsamplers.0.conv", co, co, 3)
-    norm(d + "conv_norm_out", 128)
-    conv2(d + "conv_out", 128, 3, 3)
-    return p
+    return diffusers_decoder_shapes("decoder.", LATENT_CHANNELS, BLOCK_OUT_CHANNELS)
 
 
 def synth_state_dict(seed: int = 0) -> Dict[str, torch.Tensor]:
-    """Deterministic random decoder weights with diffusers' names (bf16-representable fp32, the distributions of
-    vae_open_sora.synth_state_dict): no pretrained SD3 VAE is available offline."""
-    return _synth(decoder_param_shapes(), torch.Generator().manual_seed(seed))
+    """Deterministic random decoder weights with diffusers' names (vae_blocks.synth_weights: bf16-representable fp32, the distributions
+    of vae_open_sora.synth_state_dict): no pretrained SD3 VAE is available offline."""
+    return synth_weights(decoder_param_shapes(), torch.Generator().manual_seed(seed))

@@ -5,7 +5,9 @@ latents / scaling_factor, chunks of 14 frames through ``vae.decode(x, num_frames
 ``b f h w c``).  SURVEY.md §8a row a15; state-dict keys are the checkpoint's (``decoder.mid_block.resnets.N.spatial_res_block.*``,
 ``...temporal_res_block.*``, ``...time_mixer.mix_factor``, ``decoder.time_conv_out.*``), so the real weights drop in.
 
-Everything runs on the kernels of the Open-Sora VAE (csrc/conv_bf16.hip, csrc/vae_ops.hip); what this decoder adds is TIME:
+Everything runs on the kernels of the Open-Sora VAE (csrc/conv_bf16.hip, csrc/vae_ops.hip), and the decoder's body is the shared
+diffusers 2-D decoder of vae_blocks.py (``Decoder2DWeights`` / ``VaeBlocks._decoder2d``) with a (spatial, temporal) pair for every
+residual block; what this decoder adds is TIME:
   * ``TemporalResnetBlock``: GroupNorm over (channels of a group, all frames of the chunk, H, W), SiLU, Conv3d (3, 1, 1) with
     SYMMETRIC zero padding, twice, plus the input.  Frames are consecutive planes of the channels-last row matrix, so a frame
     shift is a constant row shift: the (3, 1, 1) convolution is the tap-shifted implicit GEMM with three taps one plane apart,
@@ -19,14 +21,13 @@ No CPU path: without the HIP library / a GPU every call raises.
 """
 from __future__ import annotations
 
-import math
 from typing import Dict
 
 import torch
 
 from . import ops
 from .ops import VaeGrid
-from .vae_open_sora import OpenSoraVAE, _Conv, _Norm, _Res, _conv_w, _vec
+from .vae_blocks import Decoder2DWeights, VaeBlocks, _Conv, _Norm, _Res, _conv_w, _vec, diffusers_decoder_shapes, norm, res2, synth_weights
 
 BLOCK_OUT = (128, 256, 512, 512)
 
@@ -48,42 +49,21 @@ class _TemporalRes:
         assert self.c1.kt == 3 and self.c1.ks == 1 and self.c1.cout == self.C
 
 
-class AutoencoderKLTemporalDecoder(OpenSoraVAE):
+class AutoencoderKLTemporalDecoder(VaeBlocks):
     """``decode(latents [B, 4, F, H, W]) -> [B, 3, F, 8H, 8W]`` bf16 and ``decode_latents`` -> uint8 [b, f, h, w, c] on the CPU."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", scaling_factor: float = 0.18215, decode_chunk_size: int = 14):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("videosys_amd.AutoencoderKLTemporalDecoder needs a HIP device (no CPU path)")
-        self.device = dev
+        super().__init__(device)
+        dev = self.device
         self.scaling_factor = scaling_factor
         self.decode_chunk_size = decode_chunk_size
-        self._padded = {}
         sd, d = state_dict, "decoder."
         self.s_conv_in_w = _conv_w(sd[d + "conv_in.weight"].to(dev), None, 64)   # K = 9 * 4 = 36 -> 64
         self.s_conv_in_b = _vec(sd[d + "conv_in.bias"].to(dev))
-
-        def st(prefix):
-            return (_Res(sd, prefix + ".spatial_res_block", dev, False),
-                    _TemporalRes(sd, prefix + ".temporal_res_block", prefix + ".time_mixer.mix_factor", dev))
-
-        self.mid = [st(f"{d}mid_block.resnets.{i}") for i in range(2)]
-        a = d + "mid_block.attentions.0."
-        self.a_norm = _Norm(sd, a + "group_norm", dev, 1e-6)
-        bf = lambda k: sd[k].to(dev).to(torch.bfloat16).contiguous()
-        self.a_wq, self.a_bq = bf(a + "to_q.weight"), bf(a + "to_q.bias")
-        self.a_wk, self.a_bk = bf(a + "to_k.weight"), bf(a + "to_k.bias")
-        self.a_wv = bf(a + "to_v.weight")
-        self.a_wo = bf(a + "to_out.0.weight")
-        bo = sd[a + "to_out.0.bias"].to(dev).float() + self.a_wo.float() @ bf(a + "to_v.bias").float()   # P (V + 1 b^T) = P V + b
-        self.a_bo = bo.to(torch.bfloat16)
-        self.up = []
-        for i in range(4):
-            res = [st(f"{d}up_blocks.{i}.resnets.{j}") for j in range(3)]
-            upk = f"{d}up_blocks.{i}.upsamplers.0.conv"
-            self.up.append((res, _Conv(sd, upk, dev) if (upk + ".weight") in sd else None))
-        self.s_norm = _Norm(sd, d + "conv_norm_out", dev, 1e-6)
-        self.s_out = _Conv(sd, d + "conv_out", dev, n_pad=128)
+        # the diffusers 2-D decoder with every residual block a (spatial, temporal) pair
+        self.dec = Decoder2DWeights(sd, d, dev, res=lambda key: (
+            _Res(sd, key + ".spatial_res_block", dev, False),
+            _TemporalRes(sd, key + ".temporal_res_block", key + ".time_mixer.mix_factor", dev)))
         # time_conv_out on the 128-column rows conv_out produces (columns 3.. are zero): W[co, tap * 128 + ci]
         wt = sd[d + "time_conv_out.weight"].to(dev).float()          # [3, 3, 3, 1, 1]
         m = torch.zeros(128, 3 * 128, dtype=torch.bfloat16, device=dev)
@@ -137,21 +117,8 @@ class AutoencoderKLTemporalDecoder(OpenSoraVAE):
         a = ops.vae_first_im2col(xz, 1, 64, params)
         g = VaeGrid(Fr, 1, H, W, 0, 0)
         x = ops.gemm128(a, self.s_conv_in_w, self.s_conv_in_b)
-        x, g = self._st_res(x, g, self.mid[0])
-        x, g = self._attention(x, g)
-        x, g = self._st_res(x, g, self.mid[1])
-        for res, up in self.up:
-            for pair in res:
-                x, g = self._st_res(x, g, pair)
-            if up is not None:
-                gp = VaeGrid(Fr, 1, 2 * g.H, 2 * g.W, 1, 0)
-                xp = self._padded_buf(gp, up.cin)
-                ops.regrid(x, g, xp, gp, up.cin, up=1)
-                x = ops.conv(xp, gp, up.w, up.b, up.cin, 1, 3)
-                g = gp.conv_out()
-        h, gh = self._norm_act(x, g, self.s_norm, 128, 0)
-        y = ops.conv(h, gh, self.s_out.w, self.s_out.b, 128, 1, 3)        # rows over (F, 1, 8H, 8W, pad 1), 128 columns (3 real)
-        Ho, Wo = gh.H, gh.W
+        y, go = self._decoder2d(x, g, self.dec, self._st_res)             # rows over (F, 1, 8H, 8W, pad 1), 128 columns (3 real)
+        Ho, Wo = go.H, go.W
         buf, gw, gc = self._time_buf(Fr, Ho, Wo, 128)
         ops.regrid(y, VaeGrid(1, Fr, Ho, Wo, 1, 0), buf, gw, 128)
         y2 = ops.conv(buf, gc, self.t_out_w, self.t_out_b, 128, 3, 1)
@@ -184,72 +151,23 @@ class AutoencoderKLTemporalDecoder(OpenSoraVAE):
 def temporal_decoder_param_shapes() -> Dict[str, tuple]:
     """Names and shapes of the decode-side parameters of the ``vae_temporal_decoder`` checkpoint (block_out_channels
     (128, 256, 512, 512), layers_per_block 2, latent_channels 4)."""
-    p: Dict[str, tuple] = {}
 
-    def norm(n, c):
-        p[n + ".weight"] = (c,)
-        p[n + ".bias"] = (c,)
-
-    def conv2(n, ci, co, k):
-        p[n + ".weight"] = (co, ci, k, k)
-        p[n + ".bias"] = (co,)
-
-    def st_res(n, ci, co):
-        s = n + ".spatial_res_block"
-        norm(s + ".norm1", ci)
-        conv2(s + ".conv1", ci, co, 3)
-        norm(s + ".norm2", co)
-        conv2(s + ".conv2", co, co, 3)
-        if ci != co:
-            conv2(s + ".conv_shortcut", ci, co, 1)
+    def st_res(p, n, ci, co):
+        res2(p, n + ".spatial_res_block", ci, co)
         t = n + ".temporal_res_block"
         for k in ("1", "2"):
-            norm(t + ".norm" + k, co)
+            norm(p, t + ".norm" + k, co)
             p[t + ".conv" + k + ".weight"] = (co, co, 3, 1, 1)
             p[t + ".conv" + k + ".bias"] = (co,)
         p[n + ".time_mixer.mix_factor"] = (1,)
 
-    d = "decoder."
-    conv2(d + "conv_in", 4, 512, 3)
-    st_res(d + "mid_block.resnets.0", 512, 512)
-    a = d + "mid_block.attentions.0."
-    norm(a + "group_norm", 512)
-    for n in ("to_q", "to_k", "to_v", "to_out.0"):
-        p[a + n + ".weight"] = (512, 512)
-        p[a + n + ".bias"] = (512,)
-    st_res(d + "mid_block.resnets.1", 512, 512)
-    prev = 512
-    for i, co in enumerate(reversed(BLOCK_OUT)):
-        for j in range(3):
-            st_res(f"{d}up_blocks.{i}.resnets.{j}", prev, co)
-            prev = co
-        if i < 3:
-            conv2(f"{d}up_blocks.{i}.upsamplers.0.conv", co, co, 3)
-    norm(d + "conv_norm_out", 128)
-    conv2(d + "conv_out", 128, 3, 3)
-    p[d + "time_conv_out.weight"] = (3, 3, 3, 1, 1)
-    p[d + "time_conv_out.bias"] = (3,)
+    p = diffusers_decoder_shapes("decoder.", 4, BLOCK_OUT, res=st_res)
+    p["decoder.time_conv_out.weight"] = (3, 3, 3, 1, 1)
+    p["decoder.time_conv_out.bias"] = (3,)
     return p
 
 
 def synth_state_dict(seed: int = 0) -> Dict[str, torch.Tensor]:
-    """Deterministic random decode-side weights (bf16-representable fp32); no checkpoint can be fetched here (no network)."""
-    g = torch.Generator().manual_seed(seed)
-    sd = {}
-    for k, shp in temporal_decoder_param_shapes().items():
-        is_norm = ".norm" in k or "group_norm" in k or "conv_norm_out" in k
-        if k.endswith("mix_factor"):
-            v = torch.randn(shp, generator=g) * 0.5
-        elif k.endswith(".weight") and len(shp) >= 2:
-            fan_in = 1
-            for s in shp[1:]:
-                fan_in *= s
-            v = torch.randn(shp, generator=g) / math.sqrt(fan_in)
-        elif k.endswith(".weight") and is_norm:
-            v = 1.0 + 0.1 * torch.randn(shp, generator=g)
-        elif is_norm:
-            v = 0.1 * torch.randn(shp, generator=g)
-        else:
-            v = 0.02 * torch.randn(shp, generator=g)
-        sd[k] = v.to(torch.bfloat16).float()
-    return sd
+    """Deterministic random decode-side weights (vae_blocks.synth_weights; the AlphaBlender factors N(0, 0.5)); no checkpoint can be
+    fetched here (no network)."""
+    return synth_weights(temporal_decoder_param_shapes(), torch.Generator().manual_seed(seed), rules=(("mix_factor", lambda r, fan_in: r * 0.5),))
