@@ -376,6 +376,35 @@ int vsys_flash_attn_d96(const void* q, int64_t q_stride, const void* rope_cos_f3
                         const void* vt, const void* kv_lens_i32, void* out, int64_t out_stride, int64_t batch, int64_t heads,
                         int64_t q_len, int64_t kv_len, int64_t kv_pad, void* stream);
 
+/* vsys_attn_prep_kv96 on a sequence-parallel exchange image (the receive image [P (source)][B][Nl][...] of the Ulysses all-to-all,
+ * open_sora_plan_v120_transformer_3d.py:916-941 all_to_all_comm): the same arithmetic, tile walk, LDS use and rounding, RoPE tables
+ * indexed by the global token s, the same Kp / Vt layouts, hence the same bits; only the row of token s differs.  The kv_len tokens of
+ * a sample lie in slabs of seg_len tokens (slab = the rank the tokens came from): token s of sample b is row
+ *     (s / seg_len) * slab_rows + b * seg_len + s % seg_len
+ * of k and of v, each with its own row stride.  Tokens past kv_len in the last slab are neither read nor written, nor are the rows
+ * between batch * seg_len and slab_rows of a slab.  seg_len >= 1.  seg_len >= kv_len is one slab (slab_rows is then unused) whose
+ * samples lie seg_len rows apart: seg_len == kv_len is exactly vsys_attn_prep_kv96's call.  With more than one slab, slab_rows below
+ * batch * seg_len is VSYS_ERR_SHAPE.  Alignment and stride checks as vsys_attn_prep_kv96.  Not in the op table: a recorded step
+ * issues it from a host closure (program.host_call). */
+int vsys_attn_prep_kv96_img(const void* k, int64_t k_stride, const void* v, int64_t v_stride, const void* rope_cos_f32,
+                            const void* rope_sin_f32, void* kp, void* vt, int64_t batch, int64_t heads, int64_t kv_len, int64_t kv_pad,
+                            int64_t seg_len, int64_t slab_rows, void* stream);
+
+/* vsys_flash_attn_d96 with q and out as exchange images (the attention between the two all_to_all_comm calls of
+ * open_sora_plan_v120_transformer_3d.py:916-941): token s of sample b is row
+ *     (s / seg_len) * q_slab_rows + b * seg_len + s % seg_len            of q    (the receive image of the way there)
+ *     (s / seg_len) * out_slab_rows + b * seg_len + s % seg_len          of out  (the send image of the way back)
+ * each with its own row stride; the RoPE tables are indexed by the global token s and (kp, vt, kv_lens) are vsys_flash_attn_d96's.
+ * Same arithmetic, tile walk and rounding, hence the same bits as vsys_flash_attn_d96 on the gathered rows.  Query tokens past q_len
+ * in the last slab are neither read nor written, nor are the rows between batch * seg_len and the slab stride.  seg_len >= 1;
+ * seg_len >= q_len is one slab (the slab strides are then unused), seg_len == q_len exactly vsys_flash_attn_d96's call; with more
+ * than one slab a slab stride below batch * seg_len is VSYS_ERR_SHAPE.  Alignment and stride checks as vsys_flash_attn_d96.  Not in
+ * the op table: a recorded step issues it from the host closure of the collective it feeds (program.host_call). */
+int vsys_flash_attn_d96_img(const void* q, int64_t q_stride, const void* rope_cos_f32, const void* rope_sin_f32, const void* kp,
+                            const void* vt, const void* kv_lens_i32, void* out, int64_t out_stride, int64_t batch, int64_t heads,
+                            int64_t q_len, int64_t kv_len, int64_t kv_pad, int64_t seg_len, int64_t q_slab_rows, int64_t out_slab_rows,
+                            void* stream);
+
 /* Temporal self-attention over the T frames of every (b, s) token: RMS qk-norm, RoPE (cos/sin fp32 [T, 72], NULL =
  * none), fp32 softmax (attentions.py:75-78,95-97,111-120; open_sora_transformer_3d.py:203-206).
  * q_norm_w == k_norm_w == NULL: no qk-norm (Latte temporal blocks, latte_transformer_3d.py:680-760).

@@ -3,10 +3,17 @@
 tokens; CFG batch 2; 512 text keys) on RANDOM weights, and the head-dim-96 flash kernel beside the head-dim-64 one.
 
     python tools/osp_bench.py [--reps 30] [--layers 32] [--out profiles/osp_v120_timing.json] [--skip-step] [--skip-kernels]
+    python tools/osp_bench.py --ranks 4 --ranks 8 [--out profiles/osp_sp_timing.json]      one rank of a sequence-parallel group
 
   step     one denoise step of OpenSoraT2V, recorded once (program.Recorder) and replayed
   kernels  vsys_flash_attn_d96 and, in the same process and in turn, vsys_flash_attn_d64 at batch 2, 24 heads, 9 600 x 9 600 keys, no
            rotation tables: TFLOP/s on the algorithmic 4 * batch * heads * Lq * Lk * head_dim flops
+
+  --ranks  the recorded step of ONE rank (rank 0) of a P-way Ulysses group with the wire stubbed (tools/local_group.StubGroup: a collective
+           is a device copy of the same bytes, the one-kernel exchange writes into the rank's own tensors): per P the three routes —
+           peer-to-peer + rows, all_to_all_single + rows, all_to_all_single + image — recorded once each and replayed IN TURN, 20
+           replays each, median and min..max, launches and host actions per step; and the single-rank step of the same run beside
+           them.  What a rank computes and launches is real; what the wire costs is NOT measured (no multi-GPU run exists).
 
 Every figure is the median of ``reps`` (>= 30) repetitions, each timed on the host between two stream synchronisations, after a
 warm-up.  Writes one JSON record: box (host name), device, date, and the measurements."""
@@ -47,8 +54,9 @@ def random_state_dict(model, dev, seed=0):
     return sd
 
 
-def step_time(args, dev):
-    from videosys_amd import pab, program
+def build_step(args, dev):
+    """(model, call): the 29x480p transformer on random weights and one CFG-pair forward of it."""
+    from videosys_amd import pab
     from videosys_amd.open_sora_plan import OpenSoraT2V, OpenSoraT2V_ROPE_L_122
 
     pab.set_pab_manager(None)
@@ -67,15 +75,74 @@ def step_time(args, dev):
     mask = torch.ones(2, 1, Lk)
     mask[1, 0, 300:] = 0
     call = lambda: model(x, timestep=torch.tensor([500, 500]), encoder_hidden_states=enc, encoder_attention_mask=mask)
+    shape = dict(layers=model.L, heads=model.H, head_dim=96, tokens=T * (H // 2) * (W // 2), batch=2, text_keys=Lk, visible=[Lk, 300])
+    return model, call, shape
+
+
+def record(call):
+    from videosys_amd import program
+
     call()
     with program.Recorder() as rec:
         call()
     prog = rec.finish()
     assert prog is not None, rec.invalid
+    return prog
+
+
+def counts(prog):
+    return dict(recorded_launches=prog.n_launches, host_actions=sum(1 for s in prog.segments if not isinstance(s, tuple)))
+
+
+def step_time(args, dev):
+    model, call, shape = build_step(args, dev)
+    prog = record(call)
     res = median_ms(prog.run, args.reps)
-    res.update(layers=model.L, heads=model.H, head_dim=96, tokens=T * (H // 2) * (W // 2), batch=2, text_keys=Lk, visible=[Lk, 300],
-               recorded_launches=prog.n_launches, host_actions=sum(1 for s in prog.segments if not isinstance(s, tuple)))
+    res.update(shape, **counts(prog))
     return res
+
+
+def in_turn(progs, reps, warm=3):
+    """name -> {median, min, max} of ``reps`` replays of every program, the programs replayed in turn so that drift hits them alike."""
+    for prog in progs.values():
+        for _ in range(warm):
+            prog.run()
+    ts = {k: [] for k in progs}
+    for _ in range(reps):
+        for k, prog in progs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            prog.run()
+            torch.cuda.synchronize()
+            ts[k].append((time.perf_counter() - t0) * 1e3)
+    return {k: dict(median_ms=round(statistics.median(v), 4), min_ms=round(min(v), 4), max_ms=round(max(v), 4), reps=reps, **counts(progs[k]))
+            for k, v in ts.items()}
+
+
+def sp_step_times(args, dev, reps=20):
+    """The per-rank step of a P-way group, wire stubbed, for every P of --ranks, and the single-rank step of the same run."""
+    from types import SimpleNamespace
+
+    from tools.local_group import StubGroup
+
+    model, call, shape = build_step(args, dev)
+    out = dict(shape, single_rank=in_turn({"step": record(call)}, reps)["step"], ranks={})
+    for P in args.ranks:
+        progs = {}
+        for name, p2p, route in (("p2p_rows", True, "rows"), ("a2a_rows", False, "rows"), ("a2a_image", False, "image")):
+            mgr = SimpleNamespace(sp_size=P, cp_size=1, dp_size=1, dp_rank=0, sp_rank=0, cp_rank=0, sp_group=StubGroup(P, 0), cp_group=None)
+            model.enable_parallel(parallel_mgr=mgr)
+            if not p2p:
+                model._sp.p2p = None
+            model.attn_route = route
+            progs[name] = record(call)
+        res = in_turn(progs, reps)
+        rows, img = res["a2a_rows"], res["a2a_image"]
+        res["image_beats_rows"] = bool(img["median_ms"] < rows["median_ms"] and img["max_ms"] < rows["min_ms"])   # the default's rule
+        res["local_tokens"] = shape["tokens"] // P
+        out["ranks"][str(P)] = res
+    model.enable_parallel(parallel_mgr=SimpleNamespace(sp_size=1, cp_size=1))
+    return out
 
 
 def kernel_times(args, dev):
@@ -127,6 +194,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-step", action="store_true")
     ap.add_argument("--skip-kernels", action="store_true")
+    ap.add_argument("--ranks", type=int, action="append", default=None,
+                    help="time one rank of a sequence-parallel group of this size, wire stubbed (repeatable); nothing else is timed then")
     args = ap.parse_args()
     args.reps = max(args.reps, 30)
     dev = torch.device("cuda:0")
@@ -134,10 +203,15 @@ def main():
            "date": datetime.datetime.now(datetime.timezone.utc).strftime("%Y-%m-%dT%H:%M:%SZ"),
            "note": "random weights (no checkpoint offline): times are valid, outputs are not a video; median of host-timed repetitions "
                    "between two stream synchronisations, after warm-up"}
-    if not args.skip_kernels:
-        res["attention_kernels"] = kernel_times(args, dev)
-    if not args.skip_step:
-        res["replayed_step_29x480p"] = step_time(args, dev)
+    if args.ranks:
+        res["note"] += "; --ranks: ONE rank of the group with the wire stubbed (a collective is a device copy of the same bytes): the wire is " \
+                       "unmeasured, no multi-GPU run exists"
+        res["sequence_parallel_step_29x480p"] = sp_step_times(args, dev)
+    else:
+        if not args.skip_kernels:
+            res["attention_kernels"] = kernel_times(args, dev)
+        if not args.skip_step:
+            res["replayed_step_29x480p"] = step_time(args, dev)
     line = json.dumps(res)
     print(line)
     if args.out:

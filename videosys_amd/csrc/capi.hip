@@ -298,6 +298,28 @@ int vsys_flash_attn_d96(const void* q, int64_t q_stride, const void* rope_cos_f3
                                B16(out), out_stride, (int)batch, (int)heads, (int)q_len, (int)kv_len, (int)kv_pad, S(stream));
 }
 
+int vsys_attn_prep_kv96_img(const void* k, int64_t k_stride, const void* v, int64_t v_stride, const void* rope_cos_f32,
+                            const void* rope_sin_f32, void* kp, void* vt, int64_t batch, int64_t heads, int64_t kv_len, int64_t kv_pad,
+                            int64_t seg_len, int64_t slab_rows, void* stream) {
+  if (!k || !v || !kp || !vt) return VSYS_ERR_ARG;
+  if (!fits_int(batch, heads, kv_len, kv_pad, seg_len)) return VSYS_ERR_SHAPE;
+  return launch_attn_prep_kv96_img(B16(k), k_stride, B16(v), v_stride, reinterpret_cast<const float*>(rope_cos_f32),
+                                   reinterpret_cast<const float*>(rope_sin_f32), B16(kp), B16(vt), (int)batch, (int)heads, (int)kv_len,
+                                   (int)kv_pad, (int)seg_len, slab_rows, S(stream));
+}
+
+int vsys_flash_attn_d96_img(const void* q, int64_t q_stride, const void* rope_cos_f32, const void* rope_sin_f32, const void* kp,
+                            const void* vt, const void* kv_lens_i32, void* out, int64_t out_stride, int64_t batch, int64_t heads,
+                            int64_t q_len, int64_t kv_len, int64_t kv_pad, int64_t seg_len, int64_t q_slab_rows, int64_t out_slab_rows,
+                            void* stream) {
+  if (!q || !kp || !vt || !out) return VSYS_ERR_ARG;
+  if (!fits_int(batch, heads, q_len, kv_len, kv_pad, seg_len)) return VSYS_ERR_SHAPE;
+  return launch_flash_attn_d96_img(B16(q), q_stride, reinterpret_cast<const float*>(rope_cos_f32),
+                                   reinterpret_cast<const float*>(rope_sin_f32), B16(kp), B16(vt),
+                                   reinterpret_cast<const int*>(kv_lens_i32), B16(out), out_stride, (int)batch, (int)heads, (int)q_len,
+                                   (int)kv_len, (int)kv_pad, (int)seg_len, q_slab_rows, out_slab_rows, S(stream));
+}
+
 int vsys_linear_small(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* out, int64_t ldo,
                       int64_t M, int64_t N, int64_t K, int act_in, int act_out, void* stream) {
   if (!x || !w || !out) return VSYS_ERR_ARG;

@@ -280,6 +280,12 @@ int launch_attn_prep_kv96(const bf16_t* k, int64_t k_stride, const bf16_t* v, in
 int launch_flash_attn_d96(const bf16_t* q, int64_t q_stride, const float* rope_cos, const float* rope_sin, const bf16_t* kp,
                           const bf16_t* vt, const int* kv_lens, bf16_t* out, int64_t out_stride, int batch, int heads, int q_len,
                           int kv_len, int kv_pad, hipStream_t stream);
+int launch_attn_prep_kv96_img(const bf16_t* k, int64_t k_stride, const bf16_t* v, int64_t v_stride, const float* rope_cos,
+                              const float* rope_sin, bf16_t* kp, bf16_t* vt, int batch, int heads, int kv_len, int kv_pad, int seg_len,
+                              int64_t slab_rows, hipStream_t stream);
+int launch_flash_attn_d96_img(const bf16_t* q, int64_t q_stride, const float* rope_cos, const float* rope_sin, const bf16_t* kp,
+                              const bf16_t* vt, const int* kv_lens, bf16_t* out, int64_t out_stride, int batch, int heads, int q_len,
+                              int kv_len, int kv_pad, int seg_len, int64_t q_slab_rows, int64_t out_slab_rows, hipStream_t stream);
 int launch_ln_modulate(const bf16_t* x, const bf16_t* ln_w, const bf16_t* ln_b, const bf16_t* shift, const bf16_t* scale,
                        bf16_t* y, int64_t rows, int C, int64_t rows_per_sample, int64_t mod_stride, int64_t seg_split,
                        int64_t mod_alt, float eps, hipStream_t stream);

@@ -798,7 +798,8 @@ def plan_heads_scatter(B, Lt, Lvl, Lv, C, P, rank):
     Ll, L = Lt + Lvl, Lt + Lv
     pack = [CopyOp(Lt * 3 * C + r * hw, r * B * Lvl * 3 * hw, B, Lvl, 3, hw, (Ll * 3 * C, 3 * C, C), (Lvl * 3 * hw, 3 * hw, hw), Lvl, 3)
             for r in range(P)]
-    unpack = [CopyOp(rank * hw, 0, B, Lt, 3, hw, (Ll * 3 * C, 3 * C, C), (L * 3 * hw, 3 * hw, hw), Lt, 3)]  # from the LOCAL qkv
+    # from the LOCAL qkv (no text rows, Lt = 0 — Open-Sora-Plan: no problem at all, never a zero-row one)
+    unpack = [CopyOp(rank * hw, 0, B, Lt, 3, hw, (Ll * 3 * C, 3 * C, C), (L * 3 * hw, 3 * hw, hw), Lt, 3)] if Lt > 0 else []
     unpack_recv = []
     for s in range(P):
         valid = max(0, min(Lvl, Lv - s * Lvl))
@@ -816,7 +817,8 @@ def plan_heads_gather(B, Lt, Lvl, Lv, C, P):
     pack = []
     for r in range(P):
         base = r * B * Ll * hw
-        pack.append(CopyOp(0, base, B, Lt, 1, hw, (L * hw, hw, hw), (Ll * hw, hw, hw), Lt, 1))
+        if Lt > 0:
+            pack.append(CopyOp(0, base, B, Lt, 1, hw, (L * hw, hw, hw), (Ll * hw, hw, hw), Lt, 1))
         valid = max(0, min(Lvl, Lv - r * Lvl))
         pack.append(CopyOp((Lt + r * Lvl) * hw if valid > 0 else 0, base + Lt * hw, B, Lvl, 1, hw, (L * hw, hw, hw), (Ll * hw, hw, hw), valid, 1))
     unpack = [CopyOp(s * B * Ll * hw, s * hw, B, Ll, 1, hw, (Ll * hw, hw, hw), (Ll * C, C, C), Ll, 1) for s in range(P)]
@@ -835,7 +837,7 @@ def plan_p2p_heads_scatter(B, Lt, Lvl, Lv, C, P, rank):
         if valid > 0:
             mine.append(CopyOp(Lt * 3 * C + r * hw, (Lt + rank * Lvl) * 3 * hw, B, valid, 3, hw, (Ll * 3 * C, 3 * C, C), (L * 3 * hw, 3 * hw, hw),
                                valid, 3))
-        if r == rank:
+        if r == rank and Lt > 0:
             mine.append(CopyOp(rank * hw, 0, B, Lt, 3, hw, (Ll * 3 * C, 3 * C, C), (L * 3 * hw, 3 * hw, hw), Lt, 3))
         ops.append(mine or None)
     return ops, (B, L, 3 * hw)
@@ -849,24 +851,28 @@ def plan_p2p_heads_gather(B, Lt, Lvl, Lv, C, P, rank):
     ops = []
     for r in range(P):
         valid = max(0, min(Lvl, Lv - r * Lvl))
-        ops.append([CopyOp(0, rank * hw, B, Lt, 1, hw, (L * hw, hw, hw), (Ll * C, C, C), Lt, 1),
-                    CopyOp((Lt + r * Lvl) * hw if valid > 0 else 0, Lt * C + rank * hw, B, Lvl, 1, hw, (L * hw, hw, hw), (Ll * C, C, C), valid, 1)])
+        text = [CopyOp(0, rank * hw, B, Lt, 1, hw, (L * hw, hw, hw), (Ll * C, C, C), Lt, 1)] if Lt > 0 else []
+        ops.append(text + [CopyOp((Lt + r * Lvl) * hw if valid > 0 else 0, Lt * C + rank * hw, B, Lvl, 1, hw, (L * hw, hw, hw),
+                                  (Ll * C, C, C), valid, 1)])
     return ops, (B, Ll, C)
 
 
 class UlyssesParallel:
     """Head <-> sequence exchange of one rank (packed buffers + all_to_all_single, like SequenceParallel)."""
 
-    def __init__(self, group, copy_executor: Callable = hip_copy_executor):
+    def __init__(self, group, copy_executor: Callable = hip_copy_executor, text_rows: bool = True):
+        """``text_rows=False``: the caller's sequences hold no replicated text rows (Lt = 0 in every call, Open-Sora-Plan): a gather is
+        then ONE problem per peer, and the one-kernel exchange carries up to 16 ranks instead of 8."""
         self.group = group
         self.P = group_size(group)
         self.rank = group_rank(group)
         self.exec = copy_executor
         self._bufs = {}
         self.exchange_info = {}
+        self.text_rows = text_rows
         self.p2p = _make_peer_exchange(group, self.P, self.rank, copy_executor, self.exchange_info)   # None: pack + all_to_all_single + unpack
-        if self.p2p is not None and 2 * self.P > 16:
-            self.p2p = None        # (the gather carries two problems per peer: at most 8 ranks in one launch)
+        if self.p2p is not None and (2 if text_rows else 1) * self.P > 16:
+            self.p2p = None        # (the gather carries two problems per peer with text rows, one without: 8 / 16 ranks in one launch)
             self.exchange_info["exchange_path"] = "rccl"
 
     _buf = SequenceParallel._buf
@@ -877,6 +883,7 @@ class UlyssesParallel:
     def scatter_heads(self, qkv, B, Lt, Lv, C, out=None):
         """qkv [B*(Lt+Lvl), 3C] (local rows) -> [B*(Lt+Lv), 3C/P] (this rank's heads, whole sequence)."""
         Lvl = self.shard_len(Lv)
+        assert self.text_rows or Lt == 0, "built with text_rows=False: the launch limit assumed Lt = 0"
         if self.p2p is not None and qkv.is_cuda and out is not None:
             ops_, oshape = plan_p2p_heads_scatter(B, Lt, Lvl, Lv, C, self.P, self.rank)
             assert tuple(out.shape) == oshape and out.is_contiguous() and qkv.is_contiguous()
@@ -896,6 +903,7 @@ class UlyssesParallel:
     def gather_heads(self, ao, B, Lt, Lv, C, out=None):
         """ao [B*(Lt+Lv), C/P] -> [B*(Lt+Lvl), C] (all heads, local rows)."""
         Lvl = self.shard_len(Lv)
+        assert self.text_rows or Lt == 0, "built with text_rows=False: the launch limit assumed Lt = 0"
         if self.p2p is not None and ao.is_cuda and out is not None:
             ops_, oshape = plan_p2p_heads_gather(B, Lt, Lvl, Lv, C, self.P, self.rank)
             assert tuple(out.shape) == oshape and out.is_contiguous() and ao.is_contiguous()
@@ -908,5 +916,40 @@ class UlyssesParallel:
         all_to_all_single(recv, send, self.group)
         if out is None:
             out = torch.empty(oshape, dtype=ao.dtype, device=ao.device)
+        self.exec(recv, out, unpack)
+        return out.view(oshape[0] * oshape[1], oshape[2])
+
+    # ---- the image route (Lt = 0, Lv % P == 0; over all_to_all_single only — the one-kernel exchange has no receive image).  The
+    # attention kernels of the caller read the receive image of the scatter as it lies and write the send image of the gather
+    # (vsys_attn_prep_kv96_img / vsys_flash_attn_d96_img): token s of sample b is row (s // Nl) * (B * Nl) + b * Nl + s % Nl of both.
+    def _image_len(self, Lv):
+        assert Lv % self.P == 0, "the image route has no padded shard: Lv must be a multiple of the group size"
+        return Lv // self.P
+
+    def scatter_heads_image(self, qkv, B, Lv, C):
+        """qkv [B*Nl, 3C] (local rows, no text) -> the receive image [P (source)][B][Nl][3][C/P] of the exchange, NOT unpacked: row
+        (src, b, sl) holds q | k | v of this rank's heads for token src * Nl + sl."""
+        Nl = self._image_len(Lv)
+        pack, _, _, sshape, _ = plan_heads_scatter(B, 0, Nl, Lv, C, self.P, self.rank)
+        send = self._buf("u_send", sshape, qkv)
+        recv = self._buf("u_recv", sshape, qkv)
+        self.exec(qkv, send, pack)
+        all_to_all_single(recv, send, self.group)
+        return recv
+
+    def heads_send_image(self, B, Lv, C, like):
+        """The resident send image [P (destination)][B][Nl][C/P] of gather_heads_image, for the caller to fill."""
+        return self._buf("g_send", (self.P, B, self._image_len(Lv), C // self.P), like)
+
+    def gather_heads_image(self, send, B, Lv, C, out=None, before=None):
+        """``send``: the caller-filled image of heads_send_image (nothing is packed) -> [B*Nl, C] (all heads, local rows).  ``before``: a
+        launch without an op code that fills ``send``, issued in the collective's host action (all_to_all_single)."""
+        Nl = self._image_len(Lv)
+        _, unpack, sshape, oshape = plan_heads_gather(B, 0, Nl, Lv, C, self.P)
+        assert tuple(send.shape) == sshape and send.is_contiguous()
+        recv = self._buf("g_recv", sshape, send)
+        all_to_all_single(recv, send, self.group, before=before)
+        if out is None:
+            out = torch.empty(oshape, dtype=send.dtype, device=send.device)
         self.exec(recv, out, unpack)
         return out.view(oshape[0] * oshape[1], oshape[2])

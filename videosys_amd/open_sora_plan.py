@@ -16,8 +16,18 @@ instead of 16 at the production geometry, about 0.1 ms of a 154 ms step, and was
 Built: norm_type="ada_norm_single", use_rope=True, downsampler=None, patch_size_t=1, activation_fn="gelu-approximate",
 attention_head_dim=96, biased projections, LayerNorms without affine, out_channels in {in_channels, 2 in_channels},
 use_image_num=0.  Anything else raises NotImplementedError at construction — nothing is approximated.  The CausalVAE decode, mT5, the
-sampler and the pipeline / config classes are vae_open_sora_plan.py and pipeline_open_sora_plan.py; not built (follow-ups): v1.1,
-sequence parallelism.
+sampler and the pipeline / config classes are vae_open_sora_plan.py and pipeline_open_sora_plan.py; not built (follow-ups): v1.1, the
+CFG split (enable_cp).
+
+Sequence parallelism (enable_parallel; :916-941,1716-1728,1896-1900,1975-1979).  The video tokens are split over
+the P ranks at rest (split_sequence, dim 1: rank r holds tokens [r Nl, (r + 1) Nl), Nl = N / P — N % P != 0 is a ValueError, as the
+reference's assert at comm.py:163, this family has no padding): the patch embedding, the modulation, cross-attention (the text K / V
+are replicated for all heads), both projections and the MLP run on the local rows [B * Nl, C]; self-attention swaps sequence for
+heads around the attention (all_to_all_comm: H / P heads, all N tokens, RoPE3D over the whole sequence) through dsp.UlyssesParallel
+with no text rows; the tail all-gathers the projected rows (192 columns, not the hidden states) and every rank returns the full
+prediction.  Three routes for the swap: "rows" over the one-kernel peer-to-peer exchange, "rows" over all_to_all_single (pack, unpack,
+pack, unpack around the plain kernels) and "image" over all_to_all_single (vsys_attn_prep_kv96_img / vsys_flash_attn_d96_img read the
+receive image as it lies and write the send image of the way back: pack and unpack only) — ``attn_route`` / DEFAULT_A2A_ROUTE.
 
 Differences that do not change results:
   * attn1's to_q / to_k / to_v are one [3C, C] GEMM; attn2's to_k / to_v run once per (prompt, mask) — the text is constant over the
@@ -37,6 +47,7 @@ from typing import Dict
 
 import torch
 
+from . import dsp
 from . import open_sora_plan_ops as oops
 from . import ops, pab
 from .pipeline import VideoSysPipelineOutput
@@ -75,6 +86,32 @@ def rope3d_tables(T: int, H: int, W: int, interpolation_scale_thw=(1.0, 1.0, 1.0
         cs.append(made[n][0][idx])
         sn.append(made[n][1][idx])
     return torch.cat(cs, dim=-1).float().contiguous(), torch.cat(sn, dim=-1).float().contiguous()
+
+
+class _NoGroupOfThatSize(NotImplementedError, AssertionError):
+    """enable_parallel without an injected manager asked for a dp x cp x sp mesh that is not the size of the process group initialised
+    in this process (none = 1).  A NotImplementedError for callers written when sequence parallelism was not built; also the
+    AssertionError dsp.ParallelManager raises for the same mismatch."""
+
+
+def _resolve_parallel(dp_size, sp_size, enable_cp, parallel_mgr):
+    """:1716-1728 (the reference halves an even sp_size under enable_cp and builds a dp x cp x sp mesh).  Returns the manager to use,
+    or None for a single rank.  The CFG split (cp > 1) is not built."""
+    import torch.distributed as dist
+
+    if enable_cp:
+        raise NotImplementedError("OpenSoraT2V on MI355X: the CFG split (enable_cp) is not built; shard with enable_cp=False")
+    if parallel_mgr is not None:
+        if getattr(parallel_mgr, "cp_size", 1) > 1:
+            raise NotImplementedError("OpenSoraT2V on MI355X: the CFG split (cp_size > 1) is not built")
+        return parallel_mgr if parallel_mgr.sp_size > 1 else None
+    dp, sp = dp_size or 1, sp_size or 1
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    if dp * sp != world:
+        raise _NoGroupOfThatSize(f"OpenSoraT2V sequence parallelism: there is no process group of {dp} x 1 x {sp} = {dp * sp} ranks in this "
+                                 f"process (the initialised world has {world}); initialise torch.distributed with that many ranks, or "
+                                 f"hand in a manager (parallel_mgr=)")
+    return dsp.ParallelManager(dp, 1, sp) if sp > 1 else None
 
 
 def _to_2tuple(x):
@@ -147,6 +184,8 @@ class OpenSoraT2V:
         self.device, self.dtype, self.rope_dtype = torch.device(device), dtype, rope_dtype
         self.w: Dict[str, torch.Tensor] = {}
         self.parallel_manager = SimpleNamespace(sp_size=1, cp_size=1, dp_size=1, dp_rank=0, sp_group=None, cp_group=None)
+        self._sp = None
+        self.attn_route = None      # None: DEFAULT_A2A_ROUTE; "rows" | "image" force one (_route)
         self.states = [pab.BlockState(i, False) for i in range(num_layers)]
         self.last_decisions = []     # per block of the last forward: (spatial broadcast?, cross broadcast?)
         self._ws = Workspace(self.device, dtype)
@@ -209,10 +248,58 @@ class OpenSoraT2V:
         self._text_cache = None
         return self
 
-    def enable_parallel(self, dp_size=1, sp_size=1, enable_cp=False):
-        """:1716-1728.  Only the single-rank mesh is built; sequence and CFG parallelism are follow-ups."""
-        if (dp_size or 1) != 1 or (sp_size or 1) != 1 or enable_cp:
-            raise NotImplementedError("OpenSoraT2V on MI355X: dp / sp / cp parallelism is not built")
+    # Which self-attention route runs over all_to_all_single when nothing is forced: the image kernels, whose per-rank step (wire
+    # stubbed, 29x480p, 32 layers) was 26.97 ms (26.88 .. 27.14) against 27.56 ms (27.47 .. 27.73) at 8 ranks and 48.65 against 49.52 ms
+    # at 4 — median below, ranges apart (profiles/osp_sp_timing.json).  "rows" stays reachable through ``attn_route``;
+    # the one-kernel peer-to-peer exchange has no receive image and always takes "rows".
+    DEFAULT_A2A_ROUTE = "image"
+
+    def enable_parallel(self, dp_size=1, sp_size=1, enable_cp=False, parallel_mgr=None, copy_executor=None):
+        """:1716-1728.  Ulysses sequence parallelism over ``sp_size`` ranks (module docstring); the CFG split (enable_cp, or an injected
+        manager with cp_size > 1) is not built.  Without a manager the mesh must be the size of the process group initialised in this
+        process.  ``copy_executor``: the pack / unpack executor of dsp.UlyssesParallel (default: the HIP copy kernel)."""
+        mgr = _resolve_parallel(dp_size, sp_size, enable_cp, parallel_mgr)
+        if mgr is None:
+            self.parallel_manager = SimpleNamespace(sp_size=1, cp_size=1, dp_size=1, dp_rank=0, sp_group=None, cp_group=None)
+            self._sp = None
+            return
+        if self.H % mgr.sp_size:
+            raise ValueError(f"Number of heads {self.H} must be divisible by sequence parallel size {mgr.sp_size}")
+        kw = {} if copy_executor is None else {"copy_executor": copy_executor}
+        self.parallel_manager = mgr
+        self._sp = dsp.UlyssesParallel(mgr.sp_group, text_rows=False, **kw)
+
+    def _route(self):
+        """"rows" or "image" for this call."""
+        if self._sp.p2p is not None:
+            return "rows"
+        r = self.attn_route or self.DEFAULT_A2A_ROUTE
+        if r not in ("rows", "image"):
+            raise ValueError(f"attn_route {r!r}: expected 'rows' or 'image'")
+        return r
+
+    def _self_attention(self, qkv, cos, sin, kp, vt, B, N):
+        """qkv [B * Nl, 3C] (local rows) -> the attention output [B * Nl, C] of the local rows, all heads."""
+        sp, C, H = self._sp, self.C, self.H
+        if sp is None:
+            oops.attn_prep_kv96(qkv[:, C:2 * C], qkv[:, 2 * C:], cos, sin, kp, vt, B, H, N)
+            return oops.flash_attn96(qkv[:, :C], cos, sin, kp, vt, None, self._buf("attn_out", (B * N, C)), B, H, N, N)
+        P = sp.P
+        Nl, Hl, hw = N // P, H // P, C // P
+        out = self._buf("attn_out", (B, Nl, C))
+        if self._route() == "rows":      # sequence -> heads, the plain kernels on [B, N, H/P heads], heads -> sequence
+            qh = sp.scatter_heads(qkv, B, 0, N, C, out=self._buf("qkv_h", (B, N, 3 * hw)))
+            oops.attn_prep_kv96(qh[:, hw:2 * hw], qh[:, 2 * hw:], cos, sin, kp, vt, B, Hl, N)
+            ao = oops.flash_attn96(qh[:, :hw], cos, sin, kp, vt, None, self._buf("attn_out_h", (B * N, hw)), B, Hl, N, N)
+            return sp.gather_heads(ao, B, 0, N, C, out=out)
+        # "image": the kernels read the receive image [P (source)][B][Nl][3][hw] as it lies and write the send image
+        # [P (destination)][B][Nl][hw] of the way back; the flash launch is issued by the host action of the collective it feeds
+        img = sp.scatter_heads_image(qkv, B, N, C).view(P * B * Nl, 3 * hw)
+        oops.attn_prep_kv96_img(img[:, hw:2 * hw], img[:, 2 * hw:], cos, sin, kp, vt, B, Hl, N, Nl, B * Nl)
+        send = sp.heads_send_image(B, N, C, qkv)
+        attend = oops.flash_attn96_img(img[:, :hw], cos, sin, kp, vt, None, send.view(P * B * Nl, hw), B, Hl, N, N, Nl, B * Nl, B * Nl,
+                                       defer=True)
+        return sp.gather_heads_image(send, B, N, C, out=out, before=attend)
 
     def reset_pab_state(self):
         pab.reset_states(self.states)
@@ -306,6 +393,12 @@ class OpenSoraT2V:
             raise ValueError("latent height and width must be multiples of the patch size")
         gh, gw = Hh // p, Ww // p
         N = T * gh * gw            # tokens of a sample, ordered (t, h, w)
+        sp = self._sp
+        P = 1 if sp is None else sp.P
+        if N % P:
+            raise ValueError(f"{N} video tokens cannot be split over {P} sequence-parallel ranks (comm.py:163; this family has no padding)")
+        Nl = N // P                # ... of which this rank holds [rank Nl, (rank + 1) Nl) at rest
+        Hl = H // P                # heads of this rank inside the self-attention
         C6 = 6 * C
         # ---- AdaLayerNormSingle: embedded_timestep and the 6C modulation row; per-block tables added in one kernel
         ts_host = torch.as_tensor(timestep).detach().to("cpu").float().reshape(-1)
@@ -325,13 +418,20 @@ class OpenSoraT2V:
         txt = self._encode_text(encoder_hidden_states, encoder_attention_mask)
         cos, sin = self._rope(T, gh, gw)
         # ---- PatchEmbed2D without position embedding (use_abs_pos = not use_rope): the patch-embed kernel with a zero table
-        zero_pos = self._ws.once(("zero_pos", gh * gw), lambda: torch.zeros(gh * gw, C, dtype=self.dtype, device=dev))
         xz = hidden_states.to(device=dev, dtype=torch.float32).contiguous()
-        x = ops.patch_embed(xz, w["pos_embed.proj.weight"], w["pos_embed.proj.bias"], zero_pos, B, (1, p, p), C).view(B * N, C)
+        if sp is None:
+            zero_pos = self._ws.once(("zero_pos", gh * gw), lambda: torch.zeros(gh * gw, C, dtype=self.dtype, device=dev))
+            x = ops.patch_embed(xz, w["pos_embed.proj.weight"], w["pos_embed.proj.bias"], zero_pos, B, (1, p, p), C).view(B * N, C)
+        else:
+            # the local tokens only.  A rank's range of the (t, h, w) order may straddle frames: the T frames are read as ONE frame of
+            # T * Hh rows (a patch never crosses a frame: Hh % p == 0), whose token s is token s of the sequence; same arithmetic per token
+            zero_pos = self._ws.once(("zero_pos", N), lambda: torch.zeros(N, C, dtype=self.dtype, device=dev))
+            x = ops.patch_embed_shard(xz.view(xz.shape[0], cin, 1, T * Hh, Ww), w["pos_embed.proj.weight"], w["pos_embed.proj.bias"],
+                                      zero_pos, B, (1, p, p), C, sp.rank * Nl, Nl).view(B * Nl, C)
 
         use_pab = pab.enable_pab()
         timestep_int = int(ts_host[0]) if use_pab else None
-        kp, vt = self._ws.once(("kv_self", B, N), lambda: oops.alloc_kv_buffers96(B, H, N, dev))
+        kp, vt = self._ws.once(("kv_self", B, N, Hl), lambda: oops.alloc_kv_buffers96(B, Hl, N, dev))
         self.last_decisions = []
         for i in range(self.L):
             pre = f"transformer_blocks.{i}"
@@ -344,29 +444,27 @@ class OpenSoraT2V:
             if use_pab:
                 bc_s, st.attn_count = pab.if_broadcast_spatial(timestep_int, st.attn_count)
             if not bc_s:
-                xm = ops.ln_modulate(x, None, None, shift_a, scale_a, N, mod_stride=C6, eps=cfg.norm_eps, out=self._buf("xm", (B * N, C)))
-                qkv = ops.gemm(xm, w[pre + ".attn1.qkv.weight"], w[pre + ".attn1.qkv.bias"], out=self._buf("qkv", (B * N, 3 * C)))
-                oops.attn_prep_kv96(qkv[:, C:2 * C], qkv[:, 2 * C:], cos, sin, kp, vt, B, H, N)
-                ao = self._buf("attn_out", (B * N, C))
-                oops.flash_attn96(qkv[:, :C], cos, sin, kp, vt, None, ao, B, H, N, N)
+                xm = ops.ln_modulate(x, None, None, shift_a, scale_a, Nl, mod_stride=C6, eps=cfg.norm_eps, out=self._buf("xm", (B * Nl, C)))
+                qkv = ops.gemm(xm, w[pre + ".attn1.qkv.weight"], w[pre + ".attn1.qkv.bias"], out=self._buf("qkv", (B * Nl, 3 * C)))
+                ao = self._self_attention(qkv, cos, sin, kp, vt, B, N)
             if use_pab:
                 # the cache holds the UN-gated attention output (:1372-1373); it is gated with this step's gate (:1378)
                 if not bc_s:
                     if st.last_attn is None or st.last_attn.shape != x.shape:
                         st.last_attn = torch.empty_like(x)
                     ops.gemm(ao, w[pre + ".attn1.to_out.0.weight"], w[pre + ".attn1.to_out.0.bias"], out=st.last_attn)
-                ops.gate_add_rows(x, st.last_attn, gate_a, N, C6)
+                ops.gate_add_rows(x, st.last_attn, gate_a, Nl, C6)
             else:
                 ops.gemm(ao, w[pre + ".attn1.to_out.0.weight"], w[pre + ".attn1.to_out.0.bias"], epilogue=ops.EPI_GATE_RES, gate=gate_a,
-                         gate_stride=C6, rows_per_sample=N, res=x, out=x)
-            # -- cross-attention on the un-normed x (the PixArt rule, :1399-1402), no gate (:1420)
+                         gate_stride=C6, rows_per_sample=Nl, res=x, out=x)
+            # -- cross-attention on the un-normed x (the PixArt rule, :1399-1402), no gate (:1420); local rows, all heads: no exchange
             bc_c = False
             if use_pab:
                 bc_c, st.cross_count = pab.if_broadcast_cross(timestep_int, st.cross_count)
             if not bc_c:
-                q = ops.gemm(x, w[pre + ".attn2.to_q.weight"], w[pre + ".attn2.to_q.bias"], out=self._buf("xm", (B * N, C)))
-                ao = self._buf("attn_out", (B * N, C))
-                oops.flash_attn96(q, None, None, txt["kp"][i], txt["vt"][i], txt["kv_lens"], ao, B, H, N, txt["Lk"])
+                q = ops.gemm(x, w[pre + ".attn2.to_q.weight"], w[pre + ".attn2.to_q.bias"], out=self._buf("xm", (B * Nl, C)))
+                ao = self._buf("attn_out", (B * Nl, C))
+                oops.flash_attn96(q, None, None, txt["kp"][i], txt["vt"][i], txt["kv_lens"], ao, B, H, Nl, txt["Lk"])
             if use_pab:
                 if not bc_c:
                     if st.last_cross is None or st.last_cross.shape != x.shape:
@@ -377,15 +475,21 @@ class OpenSoraT2V:
                 ops.gemm(ao, w[pre + ".attn2.to_out.0.weight"], w[pre + ".attn2.to_out.0.bias"], epilogue=ops.EPI_GATE_RES, res=x, out=x)
             self.last_decisions.append((bc_s, bc_c))
             # -- feed-forward (:1432-1451)
-            xm = ops.ln_modulate(x, None, None, shift_m, scale_m, N, mod_stride=C6, eps=cfg.norm_eps, out=self._buf("xm", (B * N, C)))
+            xm = ops.ln_modulate(x, None, None, shift_m, scale_m, Nl, mod_stride=C6, eps=cfg.norm_eps, out=self._buf("xm", (B * Nl, C)))
             hb = ops.gemm(xm, w[pre + ".ff.net.0.proj.weight"], w[pre + ".ff.net.0.proj.bias"], epilogue=ops.EPI_BIAS_GELU,
-                          out=self._buf("mlp_h", (B * N, 4 * C)))
+                          out=self._buf("mlp_h", (B * Nl, 4 * C)))
             ops.gemm(hb, w[pre + ".ff.net.2.weight"], w[pre + ".ff.net.2.bias"], epilogue=ops.EPI_GATE_RES, gate=gate_m, gate_stride=C6,
-                     rows_per_sample=N, res=x, out=x)
+                     rows_per_sample=Nl, res=x, out=x)
         # ---- norm_out, (shift, scale) = scale_shift_table + embedded_timestep, proj_out, unpatchify (:2077-2108)
         fin = ops.mod_table(w["scale_shift_table"], emb, out=self._buf("mod_out", (2, B, C)))     # [shift | scale] x B x C
-        xo = ops.ln_modulate(x, None, None, fin[0, 0], fin[1, 0], N, mod_stride=C, eps=1e-6, out=self._buf("xm", (B * N, C)))
-        po = ops.gemm(xo, w["_proj_out.weight"], w["_proj_out.bias"], out=self._buf("proj", (B * N, 192)))
+        xo = ops.ln_modulate(x, None, None, fin[0, 0], fin[1, 0], Nl, mod_stride=C, eps=1e-6, out=self._buf("xm", (B * Nl, C)))
+        po = ops.gemm(xo, w["_proj_out.weight"], w["_proj_out.bias"], out=self._buf("proj", (B * Nl, 192)))
+        if sp is not None:     # gather_sequence (:1975-1979) on the projected rows: 192 columns travel instead of C
+            parts = self._buf("proj_parts", (P, B, Nl, 192))
+            dsp.all_gather_into_tensor(parts.view(P * B, Nl, 192), po.view(B, Nl, 192), sp.group)
+            gather, _ = dsp.plan_gather(B, 1, Nl, N, 192, P)
+            po = self._buf("proj_all", (B * N, 192))
+            sp.exec(parts, po, gather)
         co = cfg.out_channels
         out = torch.empty(B, co, T, Hh, Ww, dtype=torch.float32, device=dev)
         for b in range(B):       # rows (t, h, w) x columns (c, dy, dx) -> out[b, c, t, y, x]: one [T, 1, H, W] problem per (b, c)

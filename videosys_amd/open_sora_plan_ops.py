@@ -1,12 +1,14 @@
 """Tensor-level wrappers of the entry points that exist for Open-Sora-Plan v1.2 (include/videosys_amd.h): the head-dim-96 attention
-(vsys_attn_prep_kv96, vsys_flash_attn_d96) and, at the end of the file, the CausalVAE decode and sampler kernels
+(vsys_attn_prep_kv96, vsys_flash_attn_d96 and their forms on a sequence-parallel exchange image, vsys_attn_prep_kv96_img,
+vsys_flash_attn_d96_img) and, at the end of the file, the CausalVAE decode and sampler kernels
 (vsys_upsample_trilinear2x, vsys_cfg_ancestral_step, vsys_pixels_to_u8_trunc).  HIP device tensors only, no eager fallback.
 
-Neither attention entry point has an op code (the op table is pinned, csrc/gen/program_gen.py NO_OP), so the launch goes through ctypes on
+No attention entry point has an op code (the op table is pinned, csrc/gen/program_gen.py NO_OP), so the launch goes through ctypes on
 torch's current stream, and under a launch-program recorder it is a ``program.host_call`` closure: the program keeps the tensors
 alive and re-issues the same call, with the same addresses, at the same position of every replay.  The per-sample key counts of the
 cross-attention are read by the kernel from device memory, so a replay carries no count.
-Element-wise tests: tests/test_gpu_osp_attention.py; guard bands: tests/test_gpu_isolation_osp.py."""
+Element-wise tests: tests/test_gpu_osp_attention.py, tests/test_gpu_osp_attention_img.py; guard bands: tests/test_gpu_isolation_osp.py,
+tests/test_gpu_isolation_osp_img.py."""
 from __future__ import annotations
 
 import torch
@@ -25,14 +27,18 @@ def alloc_kv_buffers96(batch, heads, kv_len, device):
     return kp, vt
 
 
-def _issue(name, tensors, args):
-    """Launch ``name`` now and, under a recorder, at this position of every replay."""
+def _issue(name, tensors, args, defer=False):
+    """Launch ``name`` now and, under a recorder, at this position of every replay.  ``defer=True``: launch nothing, return the closure
+    (the caller issues it from the host action of the collective it feeds or follows, dsp.all_to_all_single(before=): a replayed step
+    then gets no segment of its own for it)."""
     fn = getattr(_lib.load(), name)
     program.keep(tensors)
 
     def issue():
         _lib.check(fn(*args, torch.cuda.current_stream().cuda_stream), name)
 
+    if defer:
+        return issue
     program.host_call(issue)
 
 
@@ -78,6 +84,56 @@ def flash_attn96(q, rope_cos, rope_sin, kp, vt, kv_lens, out, batch, heads, q_le
            (dp(q), q.stride(0), dp(rope_cos), dp(rope_sin), dp(kp), dp(vt), dp(kv_lens), dp(out), out.stride(0), batch, heads, q_len,
             kv_len, kv_pad))
     return out
+
+
+def _image(t, batch, heads, length, seg_len, slab_rows):
+    """The slab checks of the image entry points: ``t`` is a 2-D row-strided view that holds every slab of ``length`` tokens."""
+    assert t.dim() == 2 and t.stride(1) == 1 and t.shape[1] >= heads * HEAD_DIM
+    assert seg_len >= 1
+    if seg_len >= length:        # one slab: samples seg_len rows apart, the slab stride is unused
+        assert t.shape[0] >= (batch - 1) * seg_len + length
+        return
+    assert slab_rows >= batch * seg_len, "a slab holds at least batch * seg_len rows"
+    nslab = -(-length // seg_len)
+    last = length - (nslab - 1) * seg_len
+    assert t.shape[0] >= (nslab - 1) * slab_rows + (batch - 1) * seg_len + last
+
+
+def attn_prep_kv96_img(k, v, rope_cos, rope_sin, kp, vt, batch, heads, kv_len, seg_len, slab_rows, defer=False):
+    """attn_prep_kv96 on an exchange image (vsys_attn_prep_kv96_img): token s of sample b is row (s // seg_len) * slab_rows + b * seg_len
+    + s % seg_len of k and of v (the receive image [P (source)][B][Nl][...] of the Ulysses all-to-all: seg_len = Nl, slab_rows = B * Nl).
+    Same bits as attn_prep_kv96 on the gathered rows; rows that belong to no token are neither read nor written."""
+    _chk(k, v, rope_cos, rope_sin, kp, vt)
+    _bf16(k, v, kp, vt)
+    assert kp.is_contiguous() and vt.is_contiguous()
+    _image(k, batch, heads, kv_len, seg_len, slab_rows), _image(v, batch, heads, kv_len, seg_len, slab_rows)
+    kv_pad = kp.shape[-2]
+    assert tuple(kp.shape[-3:]) == (heads, kv_pad, HEAD_DIM) and tuple(vt.shape[-3:]) == (heads, HEAD_DIM, kv_pad)
+    assert kp.numel() == vt.numel() == batch * heads * kv_pad * HEAD_DIM
+    _tables(rope_cos, rope_sin, kv_len)
+    dp = lambda t: None if t is None else t.data_ptr()
+    return _issue("vsys_attn_prep_kv96_img", (k, v, rope_cos, rope_sin, kp, vt),
+                  (dp(k), k.stride(0), dp(v), v.stride(0), dp(rope_cos), dp(rope_sin), dp(kp), dp(vt), batch, heads, kv_len, kv_pad,
+                   seg_len, slab_rows), defer)
+
+
+def flash_attn96_img(q, rope_cos, rope_sin, kp, vt, kv_lens, out, batch, heads, q_len, kv_len, seg_len, q_slab_rows, out_slab_rows,
+                     defer=False):
+    """flash_attn96 with q and out as exchange images (vsys_flash_attn_d96_img): query token s of sample b is row (s // seg_len) *
+    slab_rows + b * seg_len + s % seg_len, q and out each with its own slab stride and row stride — q the receive image of the way
+    there, out the send image of the way back.  Same bits as flash_attn96 on the gathered rows."""
+    _chk(q, rope_cos, rope_sin, kp, vt, kv_lens, out)
+    _bf16(q, kp, vt, out)
+    _image(q, batch, heads, q_len, seg_len, q_slab_rows), _image(out, batch, heads, q_len, seg_len, out_slab_rows)
+    kv_pad = kp.shape[-2]
+    assert kp.numel() == vt.numel() == batch * heads * kv_pad * HEAD_DIM and kv_len <= kv_pad
+    _tables(rope_cos, rope_sin, q_len)
+    if kv_lens is not None:
+        assert kv_lens.dtype == torch.int32 and kv_lens.is_contiguous() and kv_lens.numel() == batch
+    dp = lambda t: None if t is None else t.data_ptr()
+    return _issue("vsys_flash_attn_d96_img", (q, rope_cos, rope_sin, kp, vt, kv_lens, out),
+                  (dp(q), q.stride(0), dp(rope_cos), dp(rope_sin), dp(kp), dp(vt), dp(kv_lens), dp(out), out.stride(0), batch, heads,
+                   q_len, kv_len, kv_pad, seg_len, q_slab_rows, out_slab_rows), defer)
 
 
 # ------------------------------------------------------------------------------------------------ CausalVAE decode and sampler

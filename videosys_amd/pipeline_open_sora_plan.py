@@ -20,7 +20,9 @@ in one launch.  The per-step noise is ``torch.randn`` from the caller's ``genera
 generator draws on the host and the draw moves, as diffusers' randn_tensor does); the last step has sigma_up = 0 and draws none.
 Without guidance (``guidance_scale <= 1``) the model runs on [prompt | prompt] at guidance 1: u + 1 (c - u) with u = c is c exactly.
 
-``num_gpus > 1`` raises: sequence parallelism of this family is a follow-up."""
+``num_gpus`` = the size of the process group this process belongs to (one process per GPU; anything else raises): the transformer
+runs Ulysses sequence parallelism over it (open_sora_plan.py), every rank replays its own recorded step and runs the sampler step on
+the full gathered prediction; the text encoder and the VAE decode are replicated."""
 from __future__ import annotations
 
 import inspect
@@ -32,8 +34,8 @@ import numpy as np
 import torch
 
 from . import open_sora_plan_ops as oops
-from . import pab, program
-from .open_sora_plan import OpenSoraT2V, synth_state_dict
+from . import dsp, pab, program
+from .open_sora_plan import OpenSoraT2V, _NoGroupOfThatSize, synth_state_dict
 from .pab import PABConfig
 from .pipeline import VideoSysPipeline, VideoSysPipelineOutput, build_text_encoder, is_foreign_module, module_state
 from .pipeline_vchitect import retrieve_timesteps  # noqa: F401  (the same diffusers helper, pipeline_open_sora_plan.py:1197-1252)
@@ -165,8 +167,13 @@ class OpenSoraPlanPipeline(VideoSysPipeline):
                  device: torch.device = torch.device("cuda"), dtype: torch.dtype = torch.bfloat16):
         """pipeline_open_sora_plan.py:257-341, same parameter order.  Components left at None are read from ``config.transformer`` when
         that is a LOCAL checkpoint directory (``<transformer_type>/``, ``vae/``); ``"synthetic:<seed>"`` builds seeded weights."""
-        if config.num_gpus != 1:
-            raise NotImplementedError("OpenSoraPlanPipeline: sequence parallelism of this family is not built (num_gpus must be 1)")
+        import torch.distributed as dist
+
+        world = dist.get_world_size() if dist.is_initialized() else 1
+        if config.num_gpus != world:      # before any component is read
+            raise _NoGroupOfThatSize(f"OpenSoraPlanPipeline: num_gpus={config.num_gpus}, but the process group initialised in this process "
+                                     f"has {world} rank(s): a pipeline is one rank of a group of num_gpus processes (VideoSysEngine "
+                                     f"starts them; or dsp.initialize in every process)")
         self._config = config
         self._dtype = self._check_dtype(dtype)
         self._device = self._resolve_device(device, "OpenSoraPlanPipeline")
@@ -259,10 +266,17 @@ class OpenSoraPlanPipeline(VideoSysPipeline):
         sd = read_component(name, "vae")[1]
         return self._vae_from_state(sd) if sd is not None else None
 
-    def _set_parallel(self, dp_size: Optional[int] = None, sp_size: Optional[int] = None, enable_cp: Optional[bool] = False):
-        """pipeline_open_sora_plan.py:349-363; only the single-rank mesh is built."""
+    def _set_parallel(self, dp_size: Optional[int] = None, sp_size: Optional[int] = None, enable_cp: Optional[bool] = False,
+                      parallel_mgr=None):
+        """pipeline_open_sora_plan.py:349-363: sp = world size unless given.  The transformer shards the video tokens (open_sora_plan.py:
+        every rank calls generate() with the same seed, draws the same latents and per-step noise, and gets the full prediction, the
+        model gathering it inside); the text encoder and the CausalVAE decode stay replicated.  ``parallel_mgr`` (an extension): an
+        injected manager instead of the process group, as the transformer takes it."""
         import torch.distributed as dist
 
+        self._programs = {}                # a recorded step belongs to the sharding it was recorded under
+        if parallel_mgr is not None:
+            return self.transformer.enable_parallel(parallel_mgr=parallel_mgr)
         world = dist.get_world_size() if dist.is_initialized() else 1
         if sp_size is None:
             sp_size, dp_size = world, 1
@@ -521,6 +535,7 @@ class OpenSoraPlanPipeline(VideoSysPipeline):
             oops.cfg_ancestral_step(z, pred, noise, model_in, g, dt, sigma_up, sch.in_scale(i + 1))
             if callback is not None and i % callback_steps == 0:                                       # (:1164-1167)
                 callback(i, t, z)
+        dsp.check_exchange(self.transformer)     # a timed-out peer-to-peer exchange raises here, before anything is decoded
         if self.vae is None or output_type in ("latent", "latents"):
             self._enter_stage(None)
             out = z.clone()
