@@ -13,7 +13,15 @@
     python tools/osp_pipeline_bench.py [--reps 7] [--out profiles/osp_pipeline_timing.json] [--skip-step] [--skip-decode]
 
 Prints one JSON line.  Every figure is the median of ``reps`` repetitions, each timed on the host between two stream
-synchronisations, after one warm-up of the same shape."""
+synchronisations, after one warm-up of the same shape.
+
+    python tools/osp_pipeline_bench.py --shard 2 4 8 [--reps 5] [--out profiles/osp_decode_shard_timing.json]
+
+times, at 29x480p and 93x480p, OpenSoraPlanPipeline.decode_latents (tiled decode + the uint8 pass + the copy to the host) as rank 0 of
+a P-way group for every P — its units of the deal, the zeroed gather buffer, the all-gather stubbed by tools/local_group.StubGroup (one
+device copy of the buffer per rank), crop, stitch, uint8 — against the unsharded decode_latents and against rank 0's units decoded
+alone (what is left of rank 0's time is the replicated tail), in turn in one process.  No multi-GPU run: the wire is not in these
+numbers."""
 import argparse
 import json
 import os
@@ -75,9 +83,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-step", action="store_true")
     ap.add_argument("--skip-decode", action="store_true")
+    ap.add_argument("--shard", type=int, nargs="+", default=None, metavar="P",
+                    help="time rank 0's share of the tiled decode sharded over P ranks (gather stubbed) against the unsharded decode")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this benchmark needs a HIP device"
     dev = torch.device("cuda:0")
+    if args.shard:
+        return shard_main(args, dev)
     T, h, w = 8, 60, 80
     res = {"device": torch.cuda.get_device_name(0), "geometry": "29x480p", "latent": [T, h, w], "reps": args.reps,
            "what": "random weights; median (min, max) of the repetitions in ms, host clock between stream synchronisations"}
@@ -126,6 +138,78 @@ def main():
 
         res["step_ms_29x480p_512_text_tokens"] = median_ms(step, args.reps)
         res["step_stats"] = dict(pipe.step_stats)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+def shard_main(args, dev):
+    from types import SimpleNamespace
+
+    from tools.local_group import StubGroup
+    from videosys_amd.pipeline_open_sora_plan import _V120_GEOMETRY, OpenSoraPlanPipeline
+    from videosys_amd.vae_blocks import deal_units
+    from videosys_amd.vae_open_sora_plan import SCALE, CausalVAEModelWrapper
+
+    vae = CausalVAEModelWrapper("synthetic:0", device=dev, hidden_size=128)
+    v = vae.vae                                          # the pipeline's setting (OpenSoraPlanPipeline.__init__)
+    v.enable_tiling()
+    v.tile_overlap_factor, v.tile_sample_min_size, v.tile_latent_min_size = 0.25, 512, 64
+    v.tile_sample_min_size_t, v.tile_latent_min_size_t = 29, 8
+    lat_t = v.tile_latent_min_size
+
+    def pipeline(group):
+        """decode_latents as a rank of ``group`` runs it: the method of the pipeline class on the parts it reads."""
+        p = OpenSoraPlanPipeline.__new__(OpenSoraPlanPipeline)
+        p.vae, p._config = vae, SimpleNamespace(shard_vae_decode=True)
+        p.transformer = SimpleNamespace(_sp=None if group is None else SimpleNamespace(P=group.size, group=group))
+        return p
+
+    res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "geometries": {},
+           "what": "OpenSoraPlanPipeline.decode_latents (tiled CausalVAE decode at hidden_size 128 + uint8 pass + copy to the host), random "
+                   "weights; rank 0 of P with the all-gather STUBBED (tools/local_group.StubGroup: a device copy of the rank's own buffer "
+                   "per rank; no multi-GPU run exists, the wire is not in these numbers); ms, median (min, max) of the repetitions, host "
+                   "clock between stream synchronisations, the cases in turn in one process"}
+    for name in ("29x480p", "93x480p"):
+        geo = _V120_GEOMETRY[name]
+        T, (h, w) = geo["sample_size_t"], geo["sample_size"]
+        lat = (torch.randn(1, 4, T, h, w, generator=torch.Generator().manual_seed(0)) * SCALE).to(dev)
+        zb = lat[0].to(torch.bfloat16)
+        units, costs = v.tile_units(1, T, h, w)
+        cases = {"unsharded": lambda p=pipeline(None): p.decode_latents(lat)}
+        balance = {}
+        for P in args.shard:
+            owner, _, _ = deal_units(costs, P)
+            mine = [units[u] for u in range(len(units)) if owner[u] == 0]
+            balance[P] = sum(costs) / max(sum(c for c, o in zip(costs, owner) if o == r) for r in range(P))
+            cases[f"rank0_of_{P}"] = lambda p=pipeline(StubGroup(P, 0)): p.decode_latents(lat)
+            cases[f"units_of_rank0_of_{P}"] = lambda mine=mine: [
+                v._decode_tile(zb[:, t0:t1, i:i + lat_t, j:j + lat_t].contiguous(), 1.0 / SCALE) for _, (t0, t1), i, j in mine]
+        times = {k: [] for k in cases}
+        for fn in cases.values():
+            fn()
+        for _ in range(args.reps):                       # in turn, so that drift hits them alike
+            for k, fn in cases.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                times[k].append((time.perf_counter() - t0) * 1e3)
+        med = {k: statistics.median(ts) for k, ts in times.items()}
+        tri = lambda k: [round(med[k], 3), round(min(times[k]), 3), round(max(times[k]), 3)]
+        out = {"latent": [T, h, w], "units": len(units), "unsharded_ms": tri("unsharded"), "ranks": {}}
+        for P in args.shard:
+            r0, own = med[f"rank0_of_{P}"], med[f"units_of_rank0_of_{P}"]
+            out["ranks"][str(P)] = {"rank0_ms": tri(f"rank0_of_{P}"), "its_units_alone_ms": round(own, 3),
+                                    "balance_of_the_deal": round(balance[P], 2), "expected_ms_unsharded_over_balance": round(med["unsharded"] / balance[P], 3),
+                                    "unsharded_over_rank0": round(med["unsharded"] / r0, 3), "tail_ms": round(r0 - own, 3),
+                                    "tail_share_of_rank0": round((r0 - own) / r0, 4)}
+        res["geometries"][name] = out
+        v.clear_cache()
+        torch.cuda.empty_cache()
     line = json.dumps(res)
     print(line)
     if args.out:

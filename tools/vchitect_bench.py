@@ -15,7 +15,14 @@ times the same step as ONE rank (rank 0) of an N-way sequence-parallel group wit
 collective is a device copy of the rank's own send buffer, so the results are meaningless and the time is the rank's own work):
 the recorded step of every route — "rows" (unpack, old kernel, pack) and "image" (vsys_attn_temporal_d64_img on the exchange image)
 over all_to_all_single, "p2p_rows" over the one-kernel exchange — and of the single-rank model in the same run, replayed in turn;
-per route the median of ``reps`` replays, each timed on the host between two stream synchronisations, and the launch count."""
+per route the median of ``reps`` replays, each timed on the host between two stream synchronisations, and the launch count.
+
+    python tools/vchitect_bench.py --shard-decode 2 4 8 [--reps 7] [--out profiles/vchitect_decode_shard_timing.json]
+
+times rank 0's share of ``decode_u8(latents, group=)`` for every P (its ceil(F / P) frames + the zeroed piece, the all-gather stubbed
+by StubGroup — one device copy of the piece per rank — and the trim), the same frames decoded WITHOUT a group (what is left is the
+replicated tail) and the unsharded decode, in turn in one process; medians of ``reps`` repetitions on the host clock between stream
+synchronisations.  No multi-GPU run: the wire is not in these numbers."""
 import argparse
 import json
 import os
@@ -45,9 +52,13 @@ def main():
     ap.add_argument("--skip-step", action="store_true")
     ap.add_argument("--skip-decode", action="store_true")
     ap.add_argument("--ranks", type=int, default=0, help="time one rank of an N-way sequence-parallel group, wire stubbed")
+    ap.add_argument("--shard-decode", type=int, nargs="+", default=None, metavar="P",
+                    help="time rank 0's share of the VAE decode sharded over P ranks (gather stubbed) against the unsharded decode")
     args = ap.parse_args()
     if args.ranks:
         return ranks_main(args)
+    if args.shard_decode:
+        return shard_decode_main(args)
     dev = torch.device("cuda:0")
     F, h, w = 40, 36, 60
     res = {"device": torch.cuda.get_device_name(0), "frames": F, "latent": [h, w], "reps": args.reps}
@@ -154,6 +165,57 @@ def ranks_main(args):
     for name, ts in times.items():
         info[name].update(step_ms_median=round(statistics.median(ts), 3), step_ms_min=round(min(ts), 3), step_ms_max=round(max(ts), 3))
     res["routes"] = info
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+def shard_decode_main(args):
+    import statistics
+    import time
+
+    from tools.local_group import StubGroup
+    from videosys_amd import vae_sd3
+    from videosys_amd.vae_blocks import frame_shards
+
+    dev = torch.device("cuda:0")
+    F, h, w = 40, 36, 60
+    reps = max(args.reps, 5)
+    lat = torch.randn(1, F, 16, h, w, generator=torch.Generator().manual_seed(0)).to(dev)
+    dec = vae_sd3.AutoencoderKLSD3Decoder(vae_sd3.synth_state_dict(0), device=dev)
+    cases = {"unsharded": lambda: dec.decode_u8(lat)}
+    for P in args.shard_decode:
+        f0, f1 = frame_shards(F, P)[0]
+        grp, mine = StubGroup(P, 0), lat[:, f0:f1].contiguous()
+        cases[f"rank0_of_{P}"] = lambda grp=grp: dec.decode_u8(lat, group=grp)
+        cases[f"frames_of_rank0_of_{P}"] = lambda mine=mine: dec.decode_u8(mine)
+    times = {k: [] for k in cases}
+    for fn in cases.values():
+        fn()
+    for _ in range(reps):                       # in turn, so that drift hits them alike
+        for k, fn in cases.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[k].append((time.perf_counter() - t0) * 1e3)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    res = {"device": torch.cuda.get_device_name(0), "frames": F, "latent": [h, w], "frames_per_launch": dec.frames_per_launch, "reps": reps,
+           "what": "AutoencoderKLSD3Decoder.decode_u8, random weights; rank 0 of P with the all-gather STUBBED (tools/local_group.StubGroup: "
+                   "a device copy of the rank's own piece per rank; no multi-GPU run exists, the wire is not in these numbers); ms, median "
+                   "(min, max) of the repetitions, host clock between stream synchronisations, the cases in turn in one process",
+           "unsharded_ms": [round(med["unsharded"], 3), round(min(times["unsharded"]), 3), round(max(times["unsharded"]), 3)], "ranks": {}}
+    for P in args.shard_decode:
+        t, own = times[f"rank0_of_{P}"], med[f"frames_of_rank0_of_{P}"]
+        per = -(-F // P)
+        res["ranks"][str(P)] = {"frames_of_rank0": per, "rank0_ms": [round(med[f"rank0_of_{P}"], 3), round(min(t), 3), round(max(t), 3)],
+                                "its_frames_alone_ms": round(own, 3), "expected_ms_unsharded_x_share": round(med["unsharded"] * per / F, 3),
+                                "unsharded_over_rank0": round(med["unsharded"] / med[f"rank0_of_{P}"], 3), "ideal_ratio": round(F / per, 3),
+                                "tail_ms": round(med[f"rank0_of_{P}"] - own, 3),
+                                "tail_share_of_rank0": round((med[f"rank0_of_{P}"] - own) / med[f"rank0_of_{P}"], 4)}
     line = json.dumps(res)
     print(line)
     if args.out:

@@ -22,7 +22,10 @@ Without guidance (``guidance_scale <= 1``) the model runs on [prompt | prompt] a
 
 ``num_gpus`` = the size of the process group this process belongs to (one process per GPU; anything else raises): the transformer
 runs Ulysses sequence parallelism over it (open_sora_plan.py), every rank replays its own recorded step and runs the sampler step on
-the full gathered prediction; the text encoder and the VAE decode are replicated."""
+the full gathered prediction; the text encoder is replicated.  The tiled CausalVAE decode is shared: its (sample, temporal chunk,
+spatial tile) units are dealt over the ranks of the transformer's group and gathered once, then every rank stitches and converts to
+uint8 (``_decode_group``; ``OpenSoraPlanConfig(shard_vae_decode=False)`` or ``VSYS_VAE_SHARD=0``: every rank decodes every tile, as
+the reference does); a decode that does not tile stays replicated."""
 from __future__ import annotations
 
 import inspect
@@ -58,7 +61,8 @@ class OpenSoraPlanConfig:
     """pipeline_open_sora_plan.py:123-225 — identical kwargs / defaults.  ``transformer``: a LOCAL checkpoint directory in the
     published layout (``<transformer_type>/``, ``vae/``), ``"synthetic:<seed>"`` (seeded transformer and CausalVAE weights), or a hub
     id (cannot be fetched here: the published geometry with seeded transformer weights, no VAE).  Extensions, for tests:
-    ``transformer_config`` / ``vae_config`` (geometry overrides) and ``num_frames`` (instead of the one ``transformer_type`` names)."""
+    ``transformer_config`` / ``vae_config`` (geometry overrides) and ``num_frames`` (instead of the one ``transformer_type`` names);
+    ``shard_vae_decode`` (default True): see below."""
 
     def __init__(self, version: str = "v120", transformer_type: str = "29x480p", transformer: str = None, text_encoder: str = None,
                  num_gpus: int = 1, cpu_offload: bool = False, enable_tiling: bool = True, tile_overlap_factor: float = 0.25,
@@ -81,6 +85,9 @@ class OpenSoraPlanConfig:
         self.pab_config = OpenSoraPlanV120PABConfig() if (enable_pab and pab_config is None) else pab_config
         self.transformer_config = extra.pop("transformer_config", None)
         self.vae_config = extra.pop("vae_config", None)
+        # with num_gpus > 1 the units of the tiled CausalVAE decode are dealt over the ranks and gathered once (the reference decodes
+        # every tile on every rank: pipeline_open_sora_plan.py:1184-1190 under engine.py:85-95); False = the reference's behaviour
+        self.shard_vae_decode = bool(extra.pop("shard_vae_decode", True))
         if extra:
             raise TypeError(f"unexpected OpenSoraPlanConfig kwargs: {sorted(extra)}")
 
@@ -270,8 +277,9 @@ class OpenSoraPlanPipeline(VideoSysPipeline):
                       parallel_mgr=None):
         """pipeline_open_sora_plan.py:349-363: sp = world size unless given.  The transformer shards the video tokens (open_sora_plan.py:
         every rank calls generate() with the same seed, draws the same latents and per-step noise, and gets the full prediction, the
-        model gathering it inside); the text encoder and the CausalVAE decode stay replicated.  ``parallel_mgr`` (an extension): an
-        injected manager instead of the process group, as the transformer takes it."""
+        model gathering it inside); the text encoder stays replicated, the tiled CausalVAE decode is shared over the same group
+        (``_decode_group``).  ``parallel_mgr`` (an extension): an injected manager instead of the process group, as the transformer
+        takes it."""
         import torch.distributed as dist
 
         self._programs = {}                # a recorded step belongs to the sharding it was recorded under
@@ -545,12 +553,25 @@ class OpenSoraPlanPipeline(VideoSysPipeline):
         self._enter_stage(None)
         return VideoSysPipelineOutput(video=video) if return_dict else (video,)
 
+    def _decode_group(self):
+        """The ranks that share one video's VAE decode: the sequence-parallel group of the transformer (every one of its ranks holds
+        the same final latents), None on one GPU, with ``shard_vae_decode=False`` or with ``VSYS_VAE_SHARD=0``."""
+        if not getattr(self._config, "shard_vae_decode", True) or os.environ.get("VSYS_VAE_SHARD") == "0":
+            return None
+        sp = getattr(self.transformer, "_sp", None)
+        if sp is not None and sp.P > 1:
+            return sp.group
+        return None
+
     def decode_latents(self, latents):
         """:1184-1190: the VAE on the bf16 latents, then ``((video / 2 + 0.5).clamp(0, 1) * 255).to(uint8)`` on the bf16 tensor
-        (vsys_pixels_to_u8_trunc) -> uint8 [B, T, H, W, 3] on the CPU."""
+        (vsys_pixels_to_u8_trunc) -> uint8 [B, T, H, W, 3] on the CPU.  Under sequence parallelism the tiles of the decode are shared
+        by the ranks (``_decode_group``); the uint8 pass runs after the blend, on every rank."""
         from .ops import VaeGrid
 
-        video = self.vae.decode(latents.to(torch.bfloat16))                  # [B, T, 3, H, W] bf16
+        grp = self._decode_group()
+        kw = {} if grp is None else {"group": grp}                           # (an injected VAE is called as the reference calls it)
+        video = self.vae.decode(latents.to(torch.bfloat16), **kw)            # [B, T, 3, H, W] bf16
         B, T, _, H, W = video.shape
         out = torch.empty(B * T, H, W, 3, dtype=torch.uint8, device=video.device)
         rows = torch.zeros(T * H * W, 4, dtype=torch.bfloat16, device=video.device)

@@ -31,7 +31,9 @@ With PAB off the pair of model calls of a step is recorded once (program.Recorde
 More than one rank (:266-280).  ``_set_parallel`` shards the transformer by frames (vchitect.py).  Every rank runs generate() with
 the same seed, holds the whole latent and gets the whole prediction back (the model all-gathers it), so the sampler, the recorded
 step (collectives are re-issued from the program's host actions) and the returned frames are the same on every rank; the text encoders
-and the VAE decode stay replicated."""
+stay replicated.  The VAE decode is shared: rank r decodes a contiguous block of ceil(F / P) frames and one all-gather hands every rank
+every frame (``_decode_group``; ``VchitectConfig(shard_vae_decode=False)`` or ``VSYS_VAE_SHARD=0``: every rank decodes every frame, as
+the reference does)."""
 from __future__ import annotations
 
 import inspect
@@ -81,6 +83,9 @@ class VchitectConfig:
         self.transformer_config = extra.pop("transformer_config", None)  # extension: geometry override for tests
         # extension: geometry overrides of the two "synthetic:<seed>" CLIP encoders, {"text_encoder": {...}, "text_encoder_2": {...}}
         self.clip_config = extra.pop("clip_config", None)
+        # extension: with num_gpus > 1 the frames of the VAE decode are sharded over the ranks and gathered once (the reference decodes
+        # every frame on every rank: pipeline_vchitect.py:980-985 under engine.py:85-95); False = the reference's behaviour
+        self.shard_vae_decode = bool(extra.pop("shard_vae_decode", True))
         if extra:
             raise TypeError(f"unexpected VchitectConfig kwargs: {sorted(extra)}")
 
@@ -277,8 +282,8 @@ class VchitectXLPipeline(VideoSysPipeline):
                       parallel_mgr=None):
         """pipeline_vchitect.py:266-280: sp = world size unless given.  The transformer is sharded by frames (vchitect.py: every rank
         calls generate() with the same seed and gets the same frames, the model gathering its prediction inside); the text encoders
-        and the VAE decode stay replicated.  ``parallel_mgr`` (an extension): an injected manager instead of the process group, as
-        the transformers take it."""
+        stay replicated, the VAE decode is shared over the same group by frames (``_decode_group``).  ``parallel_mgr`` (an
+        extension): an injected manager instead of the process group, as the transformers take it."""
         import torch.distributed as dist
 
         self._step_program = None          # a recorded step belongs to the sharding it was recorded under
@@ -590,13 +595,26 @@ class VchitectXLPipeline(VideoSysPipeline):
         self._enter_stage(None)
         return VideoSysPipelineOutput(video=videos) if return_dict else (videos,)
 
+    def _decode_group(self):
+        """The ranks that share one video's VAE decode: the sequence-parallel group of the transformer (every one of its ranks holds
+        the same final latents), None on one GPU, with ``shard_vae_decode=False`` or with ``VSYS_VAE_SHARD=0``."""
+        if not getattr(self._config, "shard_vae_decode", True) or os.environ.get("VSYS_VAE_SHARD") == "0":
+            return None
+        sp = getattr(self.transformer, "_sp", None)
+        if sp is not None and sp.P > 1:
+            return sp.group
+        return None
+
     def decode_frames(self, latents, output_type: str = "pil"):
         """pipeline_vchitect.py:980-985: `latents / scaling_factor + shift_factor`, every frame through the VAE, then
-        VaeImageProcessor.postprocess — the first and the last of these inside the decoder's two own kernels for "pil"."""
+        VaeImageProcessor.postprocess — the first and the last of these inside the decoder's two own kernels for "pil".  Under
+        sequence parallelism the frames are shared by the ranks (``_decode_group``) and every rank gets all of them."""
+        grp = self._decode_group()
+        kw = {} if grp is None else {"group": grp}               # (an injected VAE is called as the reference calls it)
         if output_type == "pil":
             from PIL import Image
 
-            u8 = self.vae.decode_u8(latents.to(torch.float32)).cpu().numpy()
+            u8 = self.vae.decode_u8(latents.to(torch.float32), **kw).cpu().numpy()
             return [Image.fromarray(f) for f in u8]
         if output_type not in ("np", "pt"):
             raise ValueError(f"output_type {output_type!r}: expected 'pil', 'np', 'pt' or 'latent'")
@@ -604,7 +622,7 @@ class VchitectXLPipeline(VideoSysPipeline):
         # (:980) on the bf16 latents; on the host, where a tensor / scalar is a true division as in the decoder's first kernel
         bf = lambda t: t.to(torch.bfloat16).float()
         zin = bf(bf(bf(latents[0].cpu()) / c.scaling_factor) + c.shift_factor).to(self._device)     # one rounding per step, fp32 between
-        img = (self.vae.decode(zin, return_dict=False)[0] / 2 + 0.5).clamp(0, 1)                  # denormalize, on the bf16 tensor
+        img = (self.vae.decode(zin, return_dict=False, **kw)[0] / 2 + 0.5).clamp(0, 1)                # denormalize, on the bf16 tensor
         if output_type == "pt":
             return img
         return list(img.cpu().permute(0, 2, 3, 1).float().numpy())

@@ -7,6 +7,8 @@ vae_open_sora_plan.py): the model modules describe their networks on top of thes
     buffer, the residual block, the per-frame attention and the body of the diffusers 2-D decoder;
   * ``attention_core``: q / k GEMMs, batched V^T, chunked fp32 scores, row softmax, P V^T and the out-projection with the residual;
   * ``stitch_tiles``: the in-place cross-fade and crop of a grid of decoded tiles;
+  * ``deal_units`` / ``gather_units`` / ``frame_shards``: who decodes what when the ranks of a group share one decode, and the one
+    all-gather that hands every rank every unit;
   * ``synth_weights`` and the parameter-inventory helpers behind every module's ``synth_state_dict`` / ``*_param_shapes``.
 
 Kernels are the ones of csrc/conv_bf16.hip and csrc/vae_ops.hip through ops.py; there is no CPU path."""
@@ -170,6 +172,45 @@ def stitch_tiles(rows, ext_h: int, ext_w: int, lim_h: int, lim_w: int) -> torch.
             res.append(tile[:, :, :lim_h, :lim_w])
         out_rows.append(torch.cat(res, dim=3))
     return torch.cat(out_rows, dim=2)
+
+
+# ---------------------------------------------------------------------------------------------------- decode shared by a group
+def deal_units(costs, P):
+    """Which rank decodes which unit (a tile, a chunk of a tile): largest cost first, each to the rank with the least cost so far, ties
+    to the lower index (the ragged last row and column of tiles are a fraction of a full tile: dealt r, r + P, ... the 3 x 3 tiles of
+    CogVideoX config 5 give one of four ranks 2 880 of 7 560 latent pixels; this way the busiest has 1 980).  Deterministic: every
+    rank computes the same table.  Returns (owner[u], slot[u], units per rank)."""
+    load, count = [0] * P, [0] * P
+    owner, slot = [0] * len(costs), [0] * len(costs)
+    for u in sorted(range(len(costs)), key=lambda k: (-costs[k], k)):
+        r = min(range(P), key=lambda q: (load[q], q))
+        owner[u], slot[u] = r, count[r]
+        load[r] += costs[u]
+        count[r] += 1
+    return owner, slot, max(count) if count else 0
+
+
+def gather_units(mine, owner, slot, per, pad_shape, group, device, shapes):
+    """``mine[u]``: the decoded tensor of every unit this rank owns (``deal_units``) -> the list of ALL units on every rank, after ONE
+    all-gather of a zeroed bf16 [per, *pad_shape] buffer per rank that holds unit u in the leading corner of slot ``slot[u]``.
+    ``shapes[u]``: unit u's own shape (every rank derives it from the geometry without decoding; no header gather), to which it is
+    cropped back; the returned tensors are contiguous copies, so they can be blended in place."""
+    from . import dsp
+
+    P = dsp.group_size(group)
+    buf = torch.zeros((per,) + tuple(pad_shape), dtype=torch.bfloat16, device=device)
+    for u, t in mine.items():
+        assert tuple(t.shape) == tuple(shapes[u]) and all(a <= b for a, b in zip(t.shape, pad_shape)), (u, tuple(t.shape), pad_shape)
+        buf[slot[u]][tuple(slice(0, s) for s in t.shape)] = t
+    allb = torch.empty((P * per,) + tuple(pad_shape), dtype=torch.bfloat16, device=device)
+    dsp.all_gather_into_tensor(allb, buf, group)
+    return [allb[owner[u] * per + slot[u]][tuple(slice(0, s) for s in shp)].contiguous() for u, shp in enumerate(shapes)]
+
+
+def frame_shards(F: int, P: int):
+    """Contiguous frame ranges [(f0, f1)] of ceil(F / P) frames, one per rank; empty (F, F) for the ranks past the end."""
+    per = -(-F // P)
+    return [(min(r * per, F), min((r + 1) * per, F)) for r in range(P)]
 
 
 class StagingCache:

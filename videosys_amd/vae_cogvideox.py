@@ -22,7 +22,7 @@ import torch
 
 from . import ops
 from .ops import VaeGrid
-from .vae_blocks import StagingCache, _Conv, conv3, stitch_tiles, synth_weights
+from .vae_blocks import StagingCache, _Conv, conv3, deal_units, stitch_tiles, synth_weights
 
 
 class _SNorm:
@@ -196,18 +196,9 @@ class CogVideoXVAE(StagingCache):
 
     @staticmethod
     def _deal_tiles(areas, P):
-        """Which rank decodes which tile: largest tile first, each to the rank with the least latent area so far (the ragged last row
-        and column of tiles are a fraction of a full tile: dealt r, r + P, ... the 3 x 3 tiles of config 5 give one of four ranks 2 880
-        of 7 560 latent pixels; this way the busiest has 1 980).  Deterministic: every rank computes the same table.
-        Returns (owner[t], slot[t], tiles per rank)."""
-        load, count = [0] * P, [0] * P
-        owner, slot = [0] * len(areas), [0] * len(areas)
-        for t in sorted(range(len(areas)), key=lambda k: (-areas[k], k)):
-            r = min(range(P), key=lambda q: (load[q], q))
-            owner[t], slot[t] = r, count[r]
-            load[r] += areas[t]
-            count[r] += 1
-        return owner, slot, max(count) if count else 0
+        """Which rank decodes which tile: vae_blocks.deal_units over the tiles' latent areas.  Returns (owner[t], slot[t], tiles per
+        rank)."""
+        return deal_units(areas, P)
 
     def _tiles_over_ranks(self, zb, coords, tl_h, tl_w, group):
         """The decoded tiles of ``coords`` dealt over the ranks of the group (_deal_tiles): one all-gather of the ranks' tiles (padded

@@ -27,7 +27,8 @@ No kernel changes, no extra launches; at ``hidden_size`` 128 the map is the iden
 
 The residual block, the staging cache, the attention core (with the mask for key counts that are no multiple of four) and the tile
 stitching are the shared ones of vae_blocks.py; this module adds the channel map, the causal front frames (``_norm_act``), the
-whole-sample GroupNorm around the attention core and the tiling geometry.  There is no CPU path."""
+whole-sample GroupNorm around the attention core and the tiling geometry.  Under a group of ranks (``decode(z, group=)``) the
+(sample, temporal chunk, spatial tile) units of a tiled decode are dealt over the ranks and gathered once.  There is no CPU path."""
 from __future__ import annotations
 
 from types import SimpleNamespace
@@ -38,7 +39,8 @@ import torch
 from . import ops
 from . import open_sora_plan_ops as oops
 from .ops import VaeGrid
-from .vae_blocks import AttnWeights, VaeBlocks, _vec, attention_core, conv3, norm, stitch_tiles, synth_weights
+from .vae_blocks import (AttnWeights, VaeBlocks, _vec, attention_core, conv3, deal_units, gather_units, norm, stitch_tiles,
+                         synth_weights)
 
 SCALE = 0.18215                      # CausalVAEModelWrapper.decode :1131
 Z_CHANNELS = 4
@@ -273,26 +275,80 @@ class CausalVAEDecoder(VaeBlocks):
             se.append([idx[-1], t])
         return se
 
-    def _tiled2d(self, zb: torch.Tensor, in_scale: float) -> torch.Tensor:
-        """tiled_decode2d :1006-1043 on planar [4, T, H, W]."""
+    def _tile_geometry(self):
+        """(latent tile, latent step, blend extent in pixels, row / column limit in pixels) of tiled_decode2d :1006-1012."""
         lat, smp = self.tile_latent_min_size, self.tile_sample_min_size
         step, ext = int(lat * (1 - self.tile_overlap_factor)), int(smp * self.tile_overlap_factor)
-        lim = smp - ext
+        return lat, step, ext, smp - ext
+
+    def _tiled2d(self, zb: torch.Tensor, in_scale: float) -> torch.Tensor:
+        """tiled_decode2d :1006-1043 on planar [4, T, H, W]."""
+        lat, step, ext, lim = self._tile_geometry()
         H, W = zb.shape[-2:]
         rows = [[self._decode_tile(zb[:, :, i:i + lat, j:j + lat].contiguous(), in_scale) for j in range(0, W, step)]
                 for i in range(0, H, step)]
         return stitch_tiles(rows, ext, ext, lim, lim)
 
+    def tile_units(self, B: int, T: int, H: int, W: int):
+        """The independent pieces of a tiled decode of latents [B, 4, T, H, W], in decode order: [(sample, (t0, t1), i, j)], one per
+        temporal chunk and spatial tile, and their costs (chunk latent frames x tile latent rows x tile latent columns)."""
+        lat, step, _, _ = self._tile_geometry()
+        units = [(b, (t0, t1), i, j) for b in range(B) for t0, t1 in self._t_chunks(T) for i in range(0, H, step)
+                 for j in range(0, W, step)]
+        costs = [(t1 - t0) * min(lat, H - i) * min(lat, W - j) for _, (t0, t1), i, j in units]
+        return units, costs
+
+    def _decode_over_ranks(self, z: torch.Tensor, in_scale: float, group) -> torch.Tensor:
+        """The tiled decode with its (sample, chunk, tile) units dealt over the ranks of ``group`` (vae_blocks.deal_units) and ONE
+        all-gather of the decoded units, each padded to a full chunk of a full tile; then the tail of the unsharded decode on every
+        rank: stitch per chunk, drop the first frame of the later chunks, concatenate.  A unit is decoded by ``_decode_tile`` exactly
+        as the unsharded decode does it (its GroupNorm runs over the unit alone), so the bits are the unsharded decode's."""
+        from . import dsp
+
+        B, _, T, H, W = z.shape
+        lat, step, ext, lim = self._tile_geometry()
+        smp, ft = self.tile_sample_min_size, 4 * (self.tile_latent_min_size_t - 1) + 1
+        if 8 * lat > smp:
+            raise ValueError(f"tile_latent_min_size {lat} decodes to {8 * lat} pixels, more than tile_sample_min_size {smp}")
+        units, costs = self.tile_units(B, T, H, W)
+        owner, slot, per = deal_units(costs, dsp.group_size(group))
+        r = dsp.group_rank(group)
+        shapes = [(3, 4 * (t1 - t0 - 1) + 1, 8 * min(lat, H - i), 8 * min(lat, W - j)) for _, (t0, t1), i, j in units]
+        zs = [z[b].to(torch.bfloat16) for b in range(B)]
+        mine = {}
+        for u in sorted((u for u in range(len(units)) if owner[u] == r), key=lambda u: slot[u]):
+            b, (t0, t1), i, j = units[u]
+            mine[u] = self._decode_tile(zs[b][:, t0:t1, i:i + lat, j:j + lat].contiguous(), in_scale)
+        tiles = gather_units(mine, owner, slot, per, (3, ft, smp, smp), group, self.device, shapes)
+        nrow, ncol, nchunk = len(range(0, H, step)), len(range(0, W, step)), len(self._t_chunks(T))
+        outs, u = [], 0
+        for b in range(B):
+            parts = []
+            for c in range(nchunk):
+                rows = [tiles[u + k * ncol:u + (k + 1) * ncol] for k in range(nrow)]
+                u += nrow * ncol
+                dec = stitch_tiles(rows, ext, ext, lim, lim)
+                parts.append(dec if c == 0 else dec[:, 1:])
+            outs.append(torch.cat(parts, dim=1))
+        return torch.stack(outs, 0)
+
     @torch.no_grad()
-    def decode(self, z: torch.Tensor, in_scale: float = 1.0) -> torch.Tensor:
+    def decode(self, z: torch.Tensor, in_scale: float = 1.0, group=None) -> torch.Tensor:
         """CausalVAEModel.decode :872-882: z [B, 4, T, H, W] -> [B, 3, 4(T-1)+1, 8H, 8W] bf16.  ``in_scale`` multiplies z inside the
-        first-layer kernel (the wrapper's 1 / 0.18215)."""
+        first-layer kernel (the wrapper's 1 / 0.18215).  ``group`` (dsp.py group protocol; every rank holds the same latents): the
+        units of a TILED decode are decoded by the ranks in turn and gathered once (``_decode_over_ranks``) — the reference decodes
+        all of them on every rank; every rank returns the whole video.  An untiled decode is not sharded and issues no collective."""
         if not z.is_cuda:
             raise RuntimeError("CausalVAEDecoder.decode needs a HIP device tensor (no CPU path)")
         if z.dim() != 5 or z.shape[1] != Z_CHANNELS:
             raise ValueError(f"expected latents [B, {Z_CHANNELS}, T, H, W], got {tuple(z.shape)}")
         tiled = self.use_tiling and (z.shape[-1] > self.tile_latent_min_size or z.shape[-2] > self.tile_latent_min_size
                                      or z.shape[-3] > self.tile_latent_min_size_t)
+        if tiled and group is not None:
+            from . import dsp
+
+            if dsp.group_size(group) > 1:
+                return self._decode_over_ranks(z, in_scale, group)
         outs = []
         for b in range(z.shape[0]):
             zb = z[b].to(torch.bfloat16).contiguous()
@@ -336,8 +392,9 @@ class CausalVAEModelWrapper:
         raise NotImplementedError("the CausalVAE encoder is not part of this build (decode only)")
 
     @torch.no_grad()
-    def decode(self, x: torch.Tensor) -> torch.Tensor:
-        return self.vae.decode(x, in_scale=1.0 / SCALE).permute(0, 2, 1, 3, 4).contiguous()
+    def decode(self, x: torch.Tensor, group=None) -> torch.Tensor:
+        """``group``: the ranks that share this decode (CausalVAEDecoder.decode)."""
+        return self.vae.decode(x, in_scale=1.0 / SCALE, group=group).permute(0, 2, 1, 3, 4).contiguous()
 
     forward = __call__ = decode
 

@@ -12,7 +12,8 @@ and SVD decoders run as well.  The two ends are their own kernels (csrc/vae_sd3.
     ``(x / 2 + 0.5).clamp(0, 1)`` on the bf16 tensor, then ``(float32 * 255).round()`` as uint8.
 
 The reference decodes one frame per ``vae.decode`` call (:982-985); GroupNorm and the attention are per frame, so ``frames_per_launch``
-frames in one pass give the same values.  There is no CPU path."""
+frames in one pass give the same values — and, under a group of ranks (``decode_u8(latents, group=)`` / ``decode(z, group=)``), a
+contiguous block of frames per rank and one all-gather do.  There is no CPU path."""
 from __future__ import annotations
 
 from types import SimpleNamespace
@@ -22,7 +23,7 @@ import torch
 
 from . import ops, vchitect_ops as vops
 from .ops import VaeGrid
-from .vae_blocks import Decoder2DWeights, VaeBlocks, _conv_w, _vec, diffusers_decoder_shapes, synth_weights
+from .vae_blocks import Decoder2DWeights, VaeBlocks, _conv_w, _vec, diffusers_decoder_shapes, frame_shards, synth_weights
 
 LATENT_CHANNELS = 16
 BLOCK_OUT_CHANNELS = (128, 256, 512, 512)
@@ -65,35 +66,69 @@ class AutoencoderKLSD3Decoder(VaeBlocks):
         if z.dim() != 4 or z.shape[1] != LATENT_CHANNELS:
             raise ValueError(f"expected latents [F, {LATENT_CHANNELS}, h, w], got {tuple(z.shape)}")
 
+    def _my_frames(self, Fr: int, group):
+        """(f0, f1, frames per rank, ranks): this rank's contiguous frame range of ``frame_shards`` and the size of every rank's
+        piece of the gather; the whole range, alone, without a group (or in a group of one)."""
+        if group is None:
+            return 0, Fr, Fr, 1
+        from . import dsp
+
+        P = dsp.group_size(group)
+        if P == 1:
+            return 0, Fr, Fr, 1
+        f0, f1 = frame_shards(Fr, P)[dsp.group_rank(group)]
+        return f0, f1, -(-Fr // P), P
+
+    def _gather_frames(self, mine: torch.Tensor, P: int, group) -> torch.Tensor:
+        """mine [per, ...] (this rank's piece, zero behind its frames) -> [P, per, ...] after ONE all-gather: the ranks' pieces
+        in rank order, which is frame order."""
+        from . import dsp
+
+        flat = torch.empty((P * mine.shape[0],) + tuple(mine.shape[1:]), dtype=mine.dtype, device=self.device)
+        dsp.all_gather_into_tensor(flat, mine, group)
+        return flat.view((P,) + tuple(mine.shape))
+
     @torch.no_grad()
-    def decode(self, z: torch.Tensor, return_dict: bool = False):
+    def decode(self, z: torch.Tensor, return_dict: bool = False, group=None):
         """AutoencoderKL.decode: z [F, 16, h, w] (what the pipeline hands over at :983: already `/ scaling_factor + shift_factor`) ->
-        (sample [F, 3, 8h, 8w] bf16,); the input is rounded to bf16 as the reference's bf16 VAE sees it."""
+        (sample [F, 3, 8h, 8w] bf16,); the input is rounded to bf16 as the reference's bf16 VAE sees it.  ``group``: see decode_u8
+        (the gathered pieces are planar bf16)."""
         self._check(z)
         Fr, _, H, W = z.shape
         zf = z.to(torch.float32).contiguous()
-        vid = torch.empty(3, Fr, 8 * H, 8 * W, dtype=torch.bfloat16, device=self.device)
-        for f in range(0, Fr, self.frames_per_launch):
-            y, g = self._decode_rows(zf[f:f + self.frames_per_launch], 1.0, 0.0)
-            ops.extract_planar(y, g, 3, 0, vid, f)
+        f0, f1, per, P = self._my_frames(Fr, group)
+        alloc = torch.zeros if P > 1 else torch.empty
+        vid = alloc(3, per, 8 * H, 8 * W, dtype=torch.bfloat16, device=self.device)
+        for f in range(f0, f1, self.frames_per_launch):
+            y, g = self._decode_rows(zf[f:min(f + self.frames_per_launch, f1)], 1.0, 0.0)
+            ops.extract_planar(y, g, 3, 0, vid, f - f0)
+        if P > 1:                                    # [P, 3, per, 8h, 8w] -> [3, F, 8h, 8w]
+            vid = self._gather_frames(vid, P, group).permute(1, 0, 2, 3, 4).reshape(3, P * per, 8 * H, 8 * W)[:, :Fr]
         sample = vid.permute(1, 0, 2, 3)
         return SimpleNamespace(sample=sample) if return_dict else (sample,)
 
     @torch.no_grad()
-    def decode_u8(self, latents: torch.Tensor) -> torch.Tensor:
+    def decode_u8(self, latents: torch.Tensor, group=None) -> torch.Tensor:
         """pipeline_vchitect.py:980-985 for output_type "pil": the sampler's latents [1, F, 16, h, w] -> uint8 frames [F, 8h, 8w, 3] on
-        the device (one PIL image per frame is ``Image.fromarray`` of a row of it)."""
+        the device (one PIL image per frame is ``Image.fromarray`` of a row of it).  ``group`` (dsp.py group protocol; every rank
+        holds the same latents): rank r decodes the frames of ``frame_shards(F, P)[r]`` into its ceil(F / P)-frame piece and ONE
+        all-gather of the uint8 pieces gives every rank every frame — the reference decodes all of them on every rank; the 2-D decoder
+        is per frame, so the bits are the ungrouped call's.  A rank without frames launches nothing and still takes part."""
         if latents.dim() != 5 or latents.shape[0] != 1:
             raise ValueError(f"expected latents [1, F, {LATENT_CHANNELS}, h, w], got {tuple(latents.shape)}")
         z = latents[0]
         self._check(z)
         Fr, _, H, W = z.shape
         zf = z.to(torch.float32).contiguous()
-        out = torch.empty(Fr, 8 * H, 8 * W, 3, dtype=torch.uint8, device=self.device)
+        f0, f1, per, P = self._my_frames(Fr, group)
+        alloc = torch.zeros if P > 1 else torch.empty
+        out = alloc(per, 8 * H, 8 * W, 3, dtype=torch.uint8, device=self.device)
         c = self.config
-        for f in range(0, Fr, self.frames_per_launch):
-            y, g = self._decode_rows(zf[f:f + self.frames_per_launch], c.scaling_factor, c.shift_factor)
-            vops.pixels_to_u8(y, g, out, f)
+        for f in range(f0, f1, self.frames_per_launch):
+            y, g = self._decode_rows(zf[f:min(f + self.frames_per_launch, f1)], c.scaling_factor, c.shift_factor)
+            vops.pixels_to_u8(y, g, out, f - f0)
+        if P > 1:
+            out = self._gather_frames(out, P, group).view(P * per, 8 * H, 8 * W, 3)[:Fr]
         return out
 
     __call__ = decode_u8
