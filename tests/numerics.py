@@ -377,3 +377,216 @@ def first_im2col_ref(z, kt, kcols, params):
         return torch.cat([m, torch.zeros(Fr * H * W, kcols - kt * 36, dtype=m.dtype)], dim=1)
 
     return cols(u), cols(bound), cols(inside) > 0
+
+
+# ------------------------------------------------------------------------------------------------ row-wise family
+# The kernels of csrc/rowwise.hip and csrc/t5_ops.hip that surround every GEMM: LayerNorm / RMS norm + modulate, patch embed, final layer,
+# timestep embedding, the scheduler steps, the split-K finish.  Every reference is float64 from the bf16-exact (fp32-exact) operands,
+# written from the definition on tensor axes; the gathers of per-sample vectors are the CALLER's (tests/rowwise_numerics_cases.py).
+U_LIBM = 2.0**-21   # accuracy assumed for rsqrtf, expf, sinf, cosf (relative; absolute for sin / cos, whose values are <= 1): an assumption
+                    # like U_EXP and U_RCP above — the device library documents a few ulp of fp32; it vanishes next to 2^-8
+
+
+class RowStats:
+    """mean / rstd of rows in float64 with the error of an fp32 kernel that holds the row in registers and takes TWO passes:
+      e_mu   = acc(C, E|x|) + 2^-24 |mu|                       any order of an fp32 sum of C terms; the division by C
+      d_var  = acc(C + 4, var) + e_mu^2                        sum (x - mu~)^2: the error c of the mean enters as c^2 ONLY (sum (x - mu) = 0),
+                                                               each term carries the subtract's and the square's rounding, all terms >= 0
+      r_rstd = d / (2 (1 - d)) + 2 2^-24 + U_LIBM, d = d_var / (var + eps)       the division by C, the + eps, rsqrtf
+    There is no E[x^2] / (var + eps) factor anywhere: a one-pass E[x^2] - mu^2 does not fit.  ``rms``: no mean (T5LayerNorm), the same
+    with mu = e_mu = 0 and var = E[x^2].  ``exact_mean`` [rows] bool: rows whose every partial sum is exact in fp32 in ANY order (the case
+    says which: a constant 1.5, alternating +-2^-10), e_mu = 0 there."""
+
+    def __init__(self, x, eps, rms=False, exact_mean=None):
+        C = x.shape[-1]
+        self.C = C
+        self.mu = torch.zeros_like(x[..., :1]) if rms else x.mean(dim=-1, keepdim=True)
+        d = x - self.mu
+        self.var = (d * d).mean(dim=-1, keepdim=True)
+        self.rstd = torch.rsqrt(self.var + eps)
+        self.e_mu = torch.zeros_like(self.mu) if rms else acc(C, x.abs().mean(dim=-1, keepdim=True)) + U_F32 * self.mu.abs()
+        if exact_mean is not None:
+            self.e_mu = torch.where(exact_mean.reshape(self.mu.shape), torch.zeros_like(self.e_mu), self.e_mu)
+        dd = (acc(C + 4, self.var) + self.e_mu**2) / (self.var + eps)
+        assert float(dd.max()) < 0.5, "the statistics bound has broken down"
+        self.r_rstd = dd / (2 * (1 - dd)) + 2 * U_F32 + U_LIBM
+        self.n = d * self.rstd                       # the normalised row
+        self.e_n = self.rstd * self.e_mu + self.n.abs() * (self.r_rstd + 2 * U_F32)     # + the subtract and the multiply
+
+
+def ln_modulate_ref(x, eps, w=None, b=None, shift=None, scale=None, exact_mean=None):
+    """LayerNorm + modulate, the contract of adaln_modulate / ln_modulate (rowwise.hip): fp32 up to ONE bf16 store,
+    pre = ((x - mu) rstd w + b) (1 + scale) + shift  with w, b [C] and shift, scale [rows, C] ALREADY gathered per row (None = absent).
+    With g = w (1 + scale) (the factors present), n = (x - mu) rstd:
+      e_pre = |g| e_n + 8 2^-24 (|n g| + |b (1 + scale)| + |shift|)     e_n of RowStats carried through |g|; the <= 6 fp32 operations behind it
+      bound = e_pre + rnd(pre).
+    Returns (ref, bound, e_pre) [rows, C] float64."""
+    st = RowStats(x, eps, exact_mean=exact_mean)
+    one = torch.ones_like(x)
+    g = one if w is None else one * w.double()
+    off = torch.zeros_like(x) if b is None else one * b.double()
+    if scale is not None:
+        g, off = g * (1 + scale.double()), off * (1 + scale.double())
+    sh = torch.zeros_like(x) if shift is None else shift.double()
+    pre = st.n * g + off + sh
+    e_pre = g.abs() * st.e_n + 8 * U_F32 * ((st.n * g).abs() + off.abs() + sh.abs())
+    return pre, e_pre + rnd(pre), e_pre
+
+
+def bf16_neighbours(v):
+    """(vb, ulp, gap): ``v`` float64 rounded to bf16 (as float64), the distance from |vb| to the next bf16 value above it, and the distance
+    from v to the nearer of the two rounding boundaries of vb's cell (the midpoints to its neighbours; the cell below a power of two is
+    half as wide, which the neighbour below accounts for)."""
+    vb16 = v.to(torch.bfloat16).abs()
+    big, zero = torch.full_like(vb16, float("inf")), torch.zeros_like(vb16)
+    up = torch.nextafter(vb16, big).double()
+    dn = torch.where(vb16 > 0, torch.nextafter(vb16, zero), -torch.nextafter(vb16, big)).double()
+    m = vb16.double()
+    gap = torch.minimum((m + up) / 2 - v.abs(), v.abs() - (m + dn) / 2)
+    return v.to(torch.bfloat16).double(), up - m, gap
+
+
+class Tie:
+    """An intermediate that the contract rounds to bf16, held by the NEAR-TIE rule instead of a worst-case rnd(): ``vb`` = bf16 of the
+    float64 value, ``flag`` = the elements whose float64 value lies within the fp32 error ``e`` of a bf16 rounding boundary, ``err`` = one
+    bf16 ulp of a flagged element and ZERO of an unflagged one (a kernel that follows the contract produces exactly ``vb`` there)."""
+
+    def __init__(self, v, e):
+        self.v, self.e = v, e
+        self.vb, self.ulp, gap = bf16_neighbours(v)
+        self.flag = gap <= e
+        self.err = torch.where(self.flag, self.ulp, torch.zeros_like(self.ulp))
+
+    def share(self) -> float:
+        return float(self.flag.double().mean())
+
+
+def final_layer_ref(x, table, tvec, w, bias, eps, exact_mean=None):
+    """T2IFinalLayer on token rows x [B, R, C] (R = the rows of a sample), table [2, C], tvec [B, C], w [NOUT, C], bias [NOUT]:
+      shift, scale = bf16(table[0] + t_b), bf16(table[1] + t_b)        one fp32 addition of two bf16 values (IEEE), rounded: determined
+      a   = bf16(LN(x) (1 + scale) + shift)                            near-tie (Tie) with e_pre of ln_modulate_ref
+      out = bf16(sum_c a_c w_nc + bias_n), widened to fp32             bound = sum_c tie_c |w_nc| + acc(C + 1, sum |a w| + |bias|) + rnd(out)
+    Returns (ref, bound [B, R, NOUT], the Tie of a)."""
+    B, R, C = x.shape
+    tb = bf16_exact(table.float()[None] + tvec.float()[:, None])       # [B, 2, C]: ONE fp32 addition (IEEE: determined), then the rounding
+    shift, scale = tb[:, 0:1].expand(B, R, C), tb[:, 1:2].expand(B, R, C)
+    pre, _, e_pre = ln_modulate_ref(x.double().reshape(B * R, C), eps, shift=shift.reshape(B * R, C), scale=scale.reshape(B * R, C),
+                                    exact_mean=exact_mean)
+    tie = Tie(pre, e_pre)
+    w64 = w.double()
+    p = tie.vb @ w64.t() + bias.double()
+    s = tie.vb.abs() @ w64.abs().t() + bias.double().abs()
+    bound = tie.err @ w64.abs().t() + acc(C + 1, s) + rnd(p)
+    return p.reshape(B, R, -1), bound.reshape(B, R, -1), tie
+
+
+def unpatchify_ref(tok, T, Hp, Wp, patch, Cout, H, W):
+    """tok [B, T Hp Wp, ph pw Cout] (channel order (dy, dx, co)) -> [B, Cout, T, H, W], cropped: STDiT3.unpatchify on tensor axes."""
+    B = tok.shape[0]
+    ph, pw = patch
+    v = tok.reshape(B, T, Hp, Wp, ph, pw, Cout).permute(0, 6, 1, 2, 4, 3, 5).reshape(B, Cout, T, Hp * ph, Wp * pw)
+    return v[:, :, :, :H, :W]
+
+
+def patch_embed_ref(z, Bz_to_B, w, bias, pos, patch, C):
+    """OpenSoraPatchEmbed3D + pos: z fp32 [Bz, Cin, T, H, W], sample b reads z[b % Bz] (``Bz_to_B`` = B), w [C, Cin, 1, ph, pw], bias [C],
+    pos [S, C] -> [B, T, S, C].  x = bf16(z) at the load (one rounding of an fp32 value: determined); F.pad with zeros to whole patches;
+      v   = bias + sum_k x_k w_k in fp32, then bf16          near-tie (Tie), e = acc(K + 1, sum |x w| + |bias|)
+      out = bf16(bf16(v) + pos)                              bound = tie + 2^-24 |v + pos| + rnd(out)
+    Returns (ref, bound [B, T, S, C], the Tie of v)."""
+    import torch.nn.functional as F
+
+    Bz, Cin, T, H, W = z.shape
+    ph, pw = patch
+    x = bf16_exact(z)
+    x = F.pad(x, (0, (-W) % pw, 0, (-H) % ph))
+    Hp, Wp = x.shape[3] // ph, x.shape[4] // pw
+    x = x.repeat(Bz_to_B // Bz, 1, 1, 1, 1)                                         # torch.cat([z, z]): sample b = z[b % Bz]
+    cols = x.reshape(Bz_to_B, Cin, T, Hp, ph, Wp, pw).permute(0, 2, 3, 5, 1, 4, 6).reshape(Bz_to_B, T, Hp * Wp, Cin * ph * pw)
+    wk = w.double().reshape(C, -1)
+    K = wk.shape[1]
+    v = cols @ wk.t() + bias.double()
+    s = cols.abs() @ wk.abs().t() + bias.double().abs()
+    tie = Tie(v, acc(K + 1, s))
+    tie.abs_sum = s                                                                 # sum_k |x_k w_k| + |bias|
+    out = tie.vb + pos.double()
+    return out, tie.err + U_F32 * out.abs() + rnd(out), tie
+
+
+def rms_norm_ref(x, w, eps):
+    """T5LayerNorm: out = bf16(w bf16(x rstd)), rstd = rsqrt(mean(x^2) + eps) in fp32.  n = x rstd is held by the near-tie rule with e_n of
+    RowStats(rms); the product of two bf16 values is exact in fp32: bound = tie |w| + rnd(out).  Returns (ref, bound, Tie)."""
+    st = RowStats(x.double(), eps, rms=True)
+    tie = Tie(st.n, st.e_n)
+    out = tie.vb * w.double()
+    return out, tie.err * w.double().abs() + rnd(out), tie
+
+
+def gelu_new64(a):
+    import math
+
+    return 0.5 * a * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (a + 0.044715 * a**3)))
+
+
+def geglu_ref(h):
+    """T5DenseGatedActDense middle on h = [a | b] [rows, 2F]: out = bf16(bf16(gelu_new(a)) b).  The kernel forms gelu_new(a) = a / (1 + E),
+    E = exp(-2 u), u = k0 a (1 + k1 a^2), with a fast exp2 and a fast reciprocal:
+      e_g = |g| (U_RCP + 2 2^-24 + min(1, E) (U_EXP + 8 2^-24 (1 + |2 u|)))        the quotient, the sum; E's own error weighs E / (1 + E) <= min(1, E)
+    (6 fp32 operations form the argument of the exp2, whose error |2 u| multiplies).  g is held by the near-tie rule; bound = tie |b| + rnd(out)."""
+    import math
+
+    F_ = h.shape[1] // 2
+    a, b = h.double()[:, :F_], h.double()[:, F_:]
+    g = gelu_new64(a)
+    u2 = (2 * math.sqrt(2.0 / math.pi) * a * (1 + 0.044715 * a * a)).abs()
+    E = torch.exp(-2 * math.sqrt(2.0 / math.pi) * a * (1 + 0.044715 * a * a))
+    e_g = g.abs() * (U_RCP + 2 * U_F32 + E.clamp_max(1.0) * (U_EXP + 8 * U_F32 * (1 + u2)))
+    tie = Tie(g, e_g)
+    out = tie.vb * b
+    return out, tie.err * b.abs() + rnd(out), tie
+
+
+def timestep_embedding_ref(t, dim):
+    """out[b] = [cos(a_k) | sin(a_k)], a_k = t_b exp(-ln(1e4) k / half), t fp32 [B].  The kernel's angle: the argument of expf is a product
+    and a quotient of fp32 values (3 roundings with the constant's), expf, one product:
+      e_a = |a| (3 2^-24 ln(1e4) k / half + U_LIBM + 2^-24);   bound = e_a + U_LIBM + rnd(out)       (|d cos| , |d sin| <= e_a)."""
+    import math
+
+    half = dim // 2
+    k = torch.arange(half, dtype=torch.float64)
+    arg = math.log(10000.0) * k / half
+    a = t.double()[:, None] * torch.exp(-arg)[None]
+    e_a = a.abs() * (3 * U_F32 * arg[None] + U_LIBM + U_F32)
+    ref = torch.cat([torch.cos(a), torch.sin(a)], dim=1)
+    return ref, torch.cat([e_a, e_a], dim=1) + U_LIBM + rnd(ref)
+
+
+def f32(v: float) -> float:
+    """A Python float as the kernel receives it (an fp32 argument)."""
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+def cfg_step_ref(z, model_out, guidance, c_z, c_eps, cond_first=True):
+    """z' = c_z z + c_eps (u + g (c - u)) on the first Cin of model_out's Cout channels; model_out [2 Bz, Cout, ...], the conditional half
+    first when ``cond_first``.  cfg_euler_step is c_z = 1, c_eps = dt.  fp32 in, fp32 out: three to four fp32 operations on the terms,
+    bound = acc(4, |c_z z| + |c_eps| (|u| + |g| (|c| + |u|))) — an FMA contraction passes, there is no bf16 term."""
+    Bz, Cin = z.shape[:2]
+    g, c_z, c_eps = f32(guidance), f32(c_z), f32(c_eps)
+    halves = model_out.double().reshape(2, Bz, *model_out.shape[1:])[:, :, :Cin]
+    c, u = (halves[0], halves[1]) if cond_first else (halves[1], halves[0])
+    ref = c_z * z.double() + c_eps * (u + g * (c - u))
+    return ref, acc(4, abs(c_z) * z.double().abs() + abs(c_eps) * (u.abs() + abs(g) * (c.abs() + u.abs())))
+
+
+def splitk_linear_ref(x, w, nsplit, res=None):
+    """ops.linear_skinny: S = nsplit fp32 partials over slices of K (linear_ref's fp32 form: acc(Ks + 2, .) each, Ks = the longest slice),
+    summed in fp32 by splitk_reduce[_t] (acc(S + 1, .)), one bf16 rounding; with a residual bf16(bf16(p) + res): one more rnd.
+    Returns (ref, bound) [M, N]."""
+    K = x.shape[1]
+    Ks = -(-(K // 32) // nsplit) * 32
+    p, s = matmul_ref(x, w)
+    bound = acc(Ks + 2, s) + acc(nsplit + 1, s) + rnd(p)
+    if res is not None:
+        p = p + res.double()
+        bound = bound + rnd(p)
+    return p, bound
