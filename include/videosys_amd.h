@@ -405,6 +405,42 @@ int vsys_flash_attn_d96_img(const void* q, int64_t q_stride, const void* rope_co
                             int64_t q_len, int64_t kv_len, int64_t kv_pad, int64_t seg_len, int64_t q_slab_rows, int64_t out_slab_rows,
                             void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Open-Sora-Plan v1.1 (LatteT2V with use_rope): spatial self-attention at head_dim 72 with RoPE2D.
+ * The reference rotates rotate-half inside the row half and the column half of a head (RoPE2D,
+ * open_sora_plan_v110_transformer_3d.py:136-196, called from AttnProcessor2_0 :1142-1154, :1228-1238).  Attention logits do not change
+ * when the same column permutation is applied inside every head to q and to k, so the caller permutes the to_q / to_k output rows
+ * once at load time such that every rotate-half pair (j, j + 18) of a half becomes the neighbours (2p, 2p + 1), and these two entry
+ * points rotate INTERLEAVED pairs.  Neither has a VSYS_OP code (the op table keeps its size): a launch program replays them from a
+ * host closure.
+ * ------------------------------------------------------------------------------------------------------------------ */
+
+/* K side of AttnProcessor2_0 with use_rope (open_sora_plan_v110_transformer_3d.py:1220-1244, RoPE2D.forward :167-184): vsys_attn_prep_kv
+ * without the K norm, with a per-key rotation before the scale.  rope_cos_f32 / rope_sin_f32: fp32 [kv_len, 36],
+ * entry p of row s belongs to the column pair (2p, 2p + 1) of every head of key s; ONE table serves every batch item (the batch is
+ * the (sample, frame) pairs, every frame has the same token grid) and every head.  NULL tables are VSYS_ERR_SHAPE: that case is
+ * vsys_attn_prep_kv.  Rounding: k^[2p] = bf16((fp32(k[2p] c) - fp32(k[2p+1] s)) * KSCALE), k^[2p+1] = bf16((fp32(k[2p+1] c) +
+ * fp32(k[2p] s)) * KSCALE): two fp32 products and one fp32 sum (no fused multiply-add), KSCALE = 72^-1/2 * log2(e) the fp32 constant
+ * vsys_attn_prep_kv folds in, ONE rounding.  Writes exactly the opaque (kp, vt) pair of vsys_attn_prep_kv — same layouts, the ones
+ * rows 72 and 76 of vt over the valid keys, zeros behind kv_len up to kv_pad — so every vsys_flash_attn_d72* entry point consumes
+ * it.  Strides % 8 == 0, kv_pad % 64 == 0; k, v, kp, vt and the tables 16-byte aligned, else VSYS_ERR_ALIGN. */
+int vsys_attn_prep_kv_rope(const void* k, int64_t k_stride, const void* v, int64_t v_stride, const void* rope_cos_f32,
+                           const void* rope_sin_f32, void* kp, void* vt, int64_t batch, int64_t heads, int64_t kv_len, int64_t kv_pad,
+                           void* stream);
+
+/* Q side and the attention of AttnProcessor2_0 with use_rope (open_sora_plan_v110_transformer_3d.py:1213-1252): vsys_flash_attn_d72
+ * without the q norm, with Q rotated in the prologue: q^[2p] = bf16(fp32(q[2p] c) - fp32(q[2p+1] s)),
+ * q^[2p+1] = bf16(fp32(q[2p+1] c) + fp32(q[2p] s)) with rope_cos_f32 / rope_sin_f32 fp32 [q_len, 36] (one table for every batch
+ * item and head; NULL is VSYS_ERR_SHAPE); two fp32 products, one fp32 sum, no fused multiply-add, ONE rounding.  Everything after the
+ * prologue is the 32-rows-per-wave streaming kernel of vsys_flash_attn_d72: same tile walk, same masking of keys >= kv_len, same
+ * padding rules for Kp / Vt.  It ALWAYS runs that kernel: it never dispatches to the generated 64-row instruction streams or to the
+ * resident-K/V kernel (neither carries a rotation).  v1.1's spatial attention is 1 024 keys per frame at 512 x 512, where the 32-row
+ * kernel is vsys_flash_attn_d72's default as well.  q_stride % 8 == 0, out_stride % 4 == 0; q, kp, vt and the tables 16-byte
+ * aligned, out 8-byte, else VSYS_ERR_ALIGN. */
+int vsys_flash_attn_d72_rope(const void* q, int64_t q_stride, const void* rope_cos_f32, const void* rope_sin_f32, const void* kp,
+                             const void* vt, void* out, int64_t out_stride, int64_t batch, int64_t heads, int64_t q_len,
+                             int64_t kv_len, int64_t kv_pad, void* stream);
+
 /* Temporal self-attention over the T frames of every (b, s) token: RMS qk-norm, RoPE (cos/sin fp32 [T, 72], NULL =
  * none), fp32 softmax (attentions.py:75-78,95-97,111-120; open_sora_transformer_3d.py:203-206).
  * q_norm_w == k_norm_w == NULL: no qk-norm (Latte temporal blocks, latte_transformer_3d.py:680-760).

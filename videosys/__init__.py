@@ -38,6 +38,7 @@ _MODULES = {
     "models.transformers.cogvideox_transformer_3d": "cogvideox",    # CogVideoXTransformer3DModel
     "models.transformers.vchitect_transformer_3d": "vchitect",      # VchitectXLTransformerModel, JointTransformerBlock
     "models.transformers.open_sora_plan_v120_transformer_3d": "open_sora_plan",   # OpenSoraT2V, OpenSoraT2V_ROPE_L_122
+    "models.transformers.open_sora_plan_v110_transformer_3d": "open_sora_plan_v110",   # LatteT2V (v1.1: use_rope)
     "models.autoencoders.autoencoder_kl_open_sora": "vae_open_sora",    # OpenSoraVAE_V1_2
     "models.autoencoders.autoencoder_kl_cogvideox": "vae_cogvideox",    # AutoencoderKLCogVideoX
     "models.autoencoders.autoencoder_kl_open_sora_plan_v120": "vae_open_sora_plan",   # CausalVAEModelWrapper, CausalVAEModel (decode side)

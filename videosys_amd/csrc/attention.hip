@@ -45,6 +45,21 @@ constexpr float NEG_BIG = -1.0e30f;
 // VARLEN (vsys_attn_prep_kv_varlen): k / v are the rows of the PACKED text; sample b owns rows cu_seqlens[b] .. cu_seqlens[b + 1]
 // (device int32[batch + 1]) and its own key count takes the place of kv_len — same tiles, same arithmetic, same bits per sample.
 // ---------------------------------------------------------------------------------------------------------
+// Interleaved-pair rotation of N pairs (the RoPE of vsys_attn_prep_kv_rope / vsys_flash_attn_d72_rope): x[2e] <- x[2e] c - x[2e+1] s,
+// x[2e+1] <- x[2e+1] c + x[2e] s, each of the two products rounded to fp32 before the sum (no fused multiply-add): a host restatement
+// with separate mul / add gives the same bits.
+template <int N>
+__device__ __forceinline__ void rope_pairs(float* x, const float* c, const float* s) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+    const float a = x[2 * e], bb = x[2 * e + 1];
+    const float ac = a * c[e], bs = bb * s[e], bc = bb * c[e], as = a * s[e];
+    x[2 * e] = ac - bs;
+    x[2 * e + 1] = bc + as;
+  }
+}
+
 template <bool VARLEN>
 __global__ __launch_bounds__(256) void attn_prep_kv_kernel(const bf16_t* __restrict__ k, int64_t k_stride,
                                                            const bf16_t* __restrict__ v, int64_t v_stride,
@@ -138,7 +153,10 @@ __global__ __launch_bounds__(256) void attn_prep_kv_kernel(const bf16_t* __restr
 // ---------------------------------------------------------------------------------------------------------
 struct FlashParams {
   const bf16_t* q; int64_t q_stride;      // q(b, s, h) at q + (b*q_len + s)*q_stride + h*72
-  const bf16_t* q_norm_w;                  // [72] or null
+  union {
+    const bf16_t* q_norm_w;                // [72] or null
+    const float* rope_cos;                 // ABL_ROPE instantiation only: fp32 [q_len][36] (it has no q norm)
+  };
   const bf16_t* kp;                        // [batch][H][kv_pad][72]
   const bf16_t* vt;                        // [batch][H][96][kv_pad]
   bf16_t* out; int64_t out_stride;         // out(b, s, h) at out + (b*q_len + s)*out_stride + h*72
@@ -146,8 +164,13 @@ struct FlashParams {
   int chunks;                              // RES kernel: workgroups per (batch, head), each walks nqb / chunks query blocks
   float eps;
   unsigned long long* dbg;                 // lab variant 2 only: 5 phase-cycle accumulators
-  const int* kv_lens;                      // VARLEN instantiation only: [batch] key counts in device memory (kv_len is then unused)
+  union {
+    const int* kv_lens;                    // VARLEN instantiation only: [batch] key counts in device memory (kv_len is then unused)
+    const float* rope_sin;                 // ABL_ROPE instantiation only: fp32 [q_len][36]
+  };
 };
+// (the two unions keep the parameter block, and with it the offsets of the hidden arguments behind it, what every other instantiation
+//  was compiled with: tools/isa_same.py, profiles/osp_v110_isa_same.json)
 
 // WPS = waves per SIMD the register allocation targets: 2 (two workgroups per CU, no spills) or 3 (168 registers: the peeled
 // MASKED last tile spills — cross shape 0.156 vs 0.099 ms — but unmasked long key sequences gain: spatial 0.241 vs 0.251 ms;
@@ -160,6 +183,12 @@ struct FlashParams {
 // step stages ALL KV tiles of its (batch, head) into LDS once (<= 5 stages = 112.5 KiB) and then walks nqb / chunks query blocks
 // with no LDS-DMA, no vmcnt wait and no barrier in the loop: a wave's 5 pieces per tile cost it ~180 cycles each at issue
 // (DESIGN.md §3.2), which for 5-tile problems is most of the per-tile overhead.  Same tile() code, same arithmetic, same bits.
+// ABL_ROPE (vsys_flash_attn_d72_rope; a value of ABL so that no other instantiation changes its name): the streaming kernel with no
+// q norm and query row s rotated in the prologue as interleaved pairs (2p, 2p + 1) by the fp32 tables p.rope_cos / p.rope_sin
+// [q_len][36]: q^[2p] = bf16(fp32(q[2p] c) - fp32(q[2p+1] s)), the odd column with +, nothing contracted, one rounding.  A lane's
+// 8-column pieces hold their four pairs whole (one float4 of each table per piece): the rotation is lane-local, and everything behind
+// the prologue is the code of ABL 0.  (Open-Sora-Plan v1.1 RoPE2D on head-permuted to_q rows)
+constexpr int ABL_ROPE = 7;
 constexpr int RES_MAX_TILES = 5;
 constexpr int RES_Q_BYTES = 5 * 1024;   // per-wave Q image (32 rows x 144 B = 4.5 KiB, staged in 5 LDS-DMA pieces)
 // EXACT (RES only; vsys_flash_attn_d72_exact): the caller promises that the Kp rows and Vt columns behind kv_len are the zeros
@@ -264,6 +293,7 @@ __global__ __launch_bounds__(RES ? 512 : 256, RES ? 2 : WPS) void flash_attn_d72
   bf16x8 qf[5];
   // split in two so that the resident-K/V loop can request the rows of query block i + 1 before the tiles of block i
   uint4 qraw[5];
+  float4 qcs[5], qsn[5];   // ABL_ROPE: the four (cos, sin) pairs of each piece
   auto fetch_q = [&](int q0_) {
     int qs = q0_ + l31;
     qs = qs < p.q_len ? qs : p.q_len - 1;
@@ -273,8 +303,34 @@ __global__ __launch_bounds__(RES ? 512 : 256, RES ? 2 : WPS) void flash_attn_d72
       const int d0 = 16 * c + 8 * hi;
       qraw[c] = d0 < HD ? *reinterpret_cast<const uint4*>(qrow + d0) : make_uint4(0, 0, 0, 0);
     }
+    if constexpr (ABL == ABL_ROPE) {   // (qs is clamped to the last row above: the tables have q_len rows)
+      static_assert(ABL != ABL_ROPE || !RES, "the rotation lives in the streaming kernel's prologue only");
+#pragma unroll
+      for (int c = 0; c < 5; ++c) {
+        const int d0 = 16 * c + 8 * hi;
+        qcs[c] = qsn[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (d0 < HD) {
+          qcs[c] = *reinterpret_cast<const float4*>(p.rope_cos + (int64_t)qs * (HD / 2) + (d0 >> 1));
+          qsn[c] = *reinterpret_cast<const float4*>(p.rope_sin + (int64_t)qs * (HD / 2) + (d0 >> 1));
+        }
+      }
+    }
   };
   auto finish_q = [&]() {
+    if constexpr (ABL == ABL_ROPE) {
+#pragma unroll
+      for (int c = 0; c < 5; ++c) {
+        float x[8];
+        unpack8(qraw[c], x);
+        rope_pairs<1>(x + 0, &qcs[c].x, &qsn[c].x);
+        rope_pairs<1>(x + 2, &qcs[c].y, &qsn[c].y);
+        rope_pairs<1>(x + 4, &qcs[c].z, &qsn[c].z);
+        rope_pairs<1>(x + 6, &qcs[c].w, &qsn[c].w);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) qf[c][e] = (__bf16)x[e];
+      }
+      return;
+    }
     if (p.q_norm_w == nullptr) {   // (cross attention, Latte: no q norm) the raw bf16 pieces ARE the fragment: no unpack / repack pass
 #pragma unroll
       for (int c = 0; c < 5; ++c) qf[c] = __builtin_bit_cast(bf16x8, qraw[c]);
@@ -684,7 +740,9 @@ __global__ __launch_bounds__(RES ? 512 : 256, RES ? 2 : WPS) void flash_attn_d72
       __syncthreads();                                   // ... and so have everybody else's
       FLASH_STAMP(4);
     }
-    if (kv_len & 63) tile(ntiles - 1, (ntiles - 1) & 1, true);
+    // (ABL_ROPE at three workgroups per CU is launched for whole tiles only and is compiled without the masked tile: no spill code)
+    constexpr bool WHOLE_TILES_ONLY = ABL == ABL_ROPE && WPS == 3;
+    if (!WHOLE_TILES_ONLY && (kv_len & 63)) tile(ntiles - 1, (ntiles - 1) & 1, true);
     else tile(ntiles - 1, (ntiles - 1) & 1, false);
 
     if (ABL == 2 && lane == 0 && p.dbg != nullptr) {
@@ -984,6 +1042,94 @@ __global__ __launch_bounds__(256) void attn_temporal_d72_v2_kernel(const bf16_t*
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// attn_prep_kv_rope (vsys_attn_prep_kv_rope): attn_prep_kv_kernel without the K norm, key s rotated as interleaved pairs by the fp32
+// tables rope_cos / rope_sin [kv_len][36] before the scale: k^[2p] = bf16((fp32(k[2p] c) - fp32(k[2p+1] s)) kscale), ONE rounding.  A
+// lane's third of 24 columns holds its 12 pairs whole.  Same grid, same tiles, same (kp, vt) layouts, the same ones rows and zeros
+// behind kv_len.  The V tile / Vt rows / ones rows below REPEAT attn_prep_kv_kernel's and must be kept in step with them by hand:
+// moving them into __device__ helpers shared by both kernels was tried and changes the instruction sequence of the two plain
+// instantiations (same count, other order), which this file's other kernels must not do (tools/isa_same.py against the parent).  A
+// template for the same reason: a template's instantiations are emitted behind the file's plain kernels, so no parent kernel's labels
+// move; only the fixed-count form exists.
+// ---------------------------------------------------------------------------------------------------------
+template <bool VARLEN>
+__global__ __launch_bounds__(256) void attn_prep_kv_rope_kernel(const bf16_t* __restrict__ k, int64_t k_stride,
+                                                                const bf16_t* __restrict__ v, int64_t v_stride,
+                                                                const float* __restrict__ rope_cos, const float* __restrict__ rope_sin,
+                                                                bf16_t* __restrict__ kp, bf16_t* __restrict__ vt, int heads, int kv_len,
+                                                                int kv_pad, float kscale) {
+  static_assert(!VARLEN, "one table serves every batch item: fixed key count only");
+  __shared__ __attribute__((aligned(16))) bf16_t vs[64][HD + 8];  // [token][d], 160-byte rows
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int s0 = blockIdx.x * 64;
+  const int bh = blockIdx.y;
+  const int b = bh / heads, h = bh - b * heads;
+  const int64_t row0 = (int64_t)b * kv_len;
+
+  // ---- V tile -> LDS (64 tokens x 9 chunks)
+  for (int q = tid; q < 64 * 9; q += 256) {
+    const int r = q / 9, c = q - r * 9;
+    const int s = s0 + r;
+    uint4 val = make_uint4(0, 0, 0, 0);
+    if (s < kv_len) val = *reinterpret_cast<const uint4*>(v + (row0 + s) * v_stride + h * HD + c * 8);
+    *reinterpret_cast<uint4*>(&vs[r][c * 8]) = val;
+  }
+
+  // ---- K: 3 lanes per token row (24 dims = 12 pairs each), 21 rows per wave
+  {
+    const int g = lane / 3, part = lane - g * 3;
+    const int r = wave * 21 + g;
+    const bool active = (lane < 63) && (r < 64);
+    const int s = s0 + r;
+    float x[24];
+#pragma unroll
+    for (int e = 0; e < 24; ++e) x[e] = 0.f;
+    if (active && s < kv_len) {   // (rows behind kv_len stay zero: no table row exists for them)
+      const bf16_t* src = k + (row0 + s) * k_stride + h * HD + part * 24;
+      const float* tc = rope_cos + (int64_t)s * (HD / 2) + part * 12;
+      const float* ts = rope_sin + (int64_t)s * (HD / 2) + part * 12;
+      float cs[12], sn[12];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        unpack8(*reinterpret_cast<const uint4*>(src + c * 8), x + c * 8);
+        *reinterpret_cast<float4*>(cs + c * 4) = *reinterpret_cast<const float4*>(tc + c * 4);
+        *reinterpret_cast<float4*>(sn + c * 4) = *reinterpret_cast<const float4*>(ts + c * 4);
+      }
+      rope_pairs<12>(x, cs, sn);
+    }
+    KNorm72::apply(x, 0.f, nullptr, kscale);
+    if (active) {
+      bf16_t* dst = kp + (((int64_t)bh * kv_pad) + s) * HD + part * 24;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) *reinterpret_cast<uint4*>(dst + c * 8) = pack8(x + c * 8);
+    }
+  }
+  __syncthreads();
+
+  // ---- Vt rows: thread -> (d, 8-token chunk); then the ones rows 72 and 76 over the valid keys (as attn_prep_kv_kernel)
+  for (int q = tid; q < HD * 8; q += 256) {
+    const int d = q >> 3, c = q & 7;
+    uint4 o;
+    uint32_t w[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) w[e] = (uint32_t)vs[c * 8 + 2 * e][d] | ((uint32_t)vs[c * 8 + 2 * e + 1][d] << 16);
+    o.x = w[0]; o.y = w[1]; o.z = w[2]; o.w = w[3];
+    *reinterpret_cast<uint4*>(vt + ((int64_t)bh * HD_ROWS + d) * kv_pad + s0 + c * 8) = o;
+  }
+  if (tid < 16) {
+    const int d = HD + 4 * (tid >> 3), c = tid & 7;
+    uint32_t w[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int k0 = s0 + c * 8 + 2 * e;
+      w[e] = (k0 < kv_len ? 0x3f80u : 0u) | (k0 + 1 < kv_len ? 0x3f800000u : 0u);
+    }
+    uint4 o;
+    o.x = w[0]; o.y = w[1]; o.z = w[2]; o.w = w[3];
+    *reinterpret_cast<uint4*>(vt + ((int64_t)bh * HD_ROWS + d) * kv_pad + s0 + c * 8) = o;
+  }
+}
+
 }  // namespace
 
 // A/B selector of the measurement tools and the kernel-equivalence tests (vsys_tune_flash_variant): process-wide, read once per
@@ -1214,6 +1360,44 @@ int launch_attn_temporal_d72(const bf16_t* qkv, int64_t row_stride, int C, const
     hipLaunchKernelGGL(attn_temporal_d72_kernel, dim3((unsigned)grid), dim3(64 * wpb), lds, stream, qkv, row_stride, C, q_norm_w,
                        k_norm_w, rope_cos, rope_sin, out, out_stride, B, T, S, heads, wpb, eps, scale);
   }
+  return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
+}
+
+// ---- Open-Sora-Plan v1.1 spatial attention (vsys_attn_prep_kv_rope, vsys_flash_attn_d72_rope).  Kept at the end of the file: the
+// kernels they instantiate are then emitted behind every other kernel of this file.
+int launch_attn_prep_kv_rope(const bf16_t* k, int64_t k_stride, const bf16_t* v, int64_t v_stride, const float* rope_cos,
+                             const float* rope_sin, bf16_t* kp, bf16_t* vt, int batch, int heads, int kv_len, int kv_pad,
+                             hipStream_t stream) {
+  if (batch <= 0 || heads <= 0 || kv_len <= 0) return 0;
+  if (kv_pad % 64 != 0 || kv_pad < kv_len || (k_stride % 8) || (v_stride % 8)) return VSYS_ERR_SHAPE;
+  dim3 grid(kv_pad / 64, batch * heads);
+  hipLaunchKernelGGL(attn_prep_kv_rope_kernel<false>, grid, dim3(256), 0, stream, k, k_stride, v, v_stride, rope_cos, rope_sin, kp, vt,
+                     heads, kv_len, kv_pad, 0.11785113019775793f * 1.4426950408889634f /* 72^-0.5 * log2(e), as launch_attn_prep_kv */);
+  return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
+}
+
+// ALWAYS the streaming 32-rows-per-wave kernel (the resident-K/V kernel and the 64-row instruction streams carry no rotation), so the
+// flash variant selector (vsys_tune_flash_variant) has nothing to select here and is not read.  Two or three workgroups per CU by the
+// last step of launch_flash_attn_d72's rule: three for kv_len >= 512 that is a multiple of 64 (the three-workgroup instantiation has
+// no masked tile), VSYS_FLASH_WPS3=0 keeps two — the A/B switch of the plain launch, honoured here as well.
+int launch_flash_attn_d72_rope(const bf16_t* q, int64_t q_stride, const float* rope_cos, const float* rope_sin, const bf16_t* kp,
+                               const bf16_t* vt, bf16_t* out, int64_t out_stride, int batch, int heads, int q_len, int kv_len,
+                               int kv_pad, hipStream_t stream) {
+  if (batch <= 0 || heads <= 0 || q_len <= 0) return 0;
+  if (kv_len <= 0 || kv_pad % 64 != 0 || kv_pad < kv_len || (q_stride % 8) || (out_stride % 4)) return VSYS_ERR_SHAPE;
+  FlashParams p;
+  p.q = q; p.q_stride = q_stride; p.rope_cos = rope_cos; p.kp = kp; p.vt = vt; p.out = out; p.out_stride = out_stride;
+  p.heads = heads; p.q_len = q_len; p.kv_len = kv_len; p.kv_pad = kv_pad; p.eps = 0.f;
+  p.rope_sin = rope_sin;
+  p.dbg = nullptr;
+  p.nqb = (q_len + 127) / 128;
+  p.chunks = 1;
+  const int64_t nblk = (int64_t)p.nqb * batch * heads;
+  if (nblk > 0x7fffffff) return VSYS_ERR_SHAPE;
+  const size_t lds = 2 * KV_STAGE;
+  static const bool wps3_ok = [] { const char* e = getenv("VSYS_FLASH_WPS3"); return !(e && e[0] == '0'); }();
+  if (wps3_ok && kv_len >= 512 && (kv_len & 63) == 0) hipLaunchKernelGGL((flash_attn_d72_kernel<ABL_ROPE, 3>), dim3((unsigned)nblk), dim3(256), lds, stream, p);
+  else hipLaunchKernelGGL((flash_attn_d72_kernel<ABL_ROPE, 2>), dim3((unsigned)nblk), dim3(256), lds, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
 }
 

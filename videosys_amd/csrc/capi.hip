@@ -465,6 +465,33 @@ int vsys_flash_attn_d72_varlen(const void* q, int64_t q_stride, const void* q_no
                                       (int)batch, (int)heads, (int)q_len, (int)kv_pad, eps, S(stream));
 }
 
+int vsys_attn_prep_kv_rope(const void* k, int64_t k_stride, const void* v, int64_t v_stride, const void* rope_cos_f32,
+                           const void* rope_sin_f32, void* kp, void* vt, int64_t batch, int64_t heads, int64_t kv_len, int64_t kv_pad,
+                           void* stream) {
+  if (!k || !v || !kp || !vt) return VSYS_ERR_ARG;
+  if (!rope_cos_f32 || !rope_sin_f32) return VSYS_ERR_SHAPE;   // no rotation: vsys_attn_prep_kv
+  if (!fits_int(batch, heads, kv_len, kv_pad) || batch * heads > 65535) return VSYS_ERR_SHAPE;
+  for (const void* ptr : {k, v, rope_cos_f32, rope_sin_f32, (const void*)kp, (const void*)vt})
+    if (reinterpret_cast<uintptr_t>(ptr) & 15) return VSYS_ERR_ALIGN;
+  return launch_attn_prep_kv_rope(B16(k), k_stride, B16(v), v_stride, reinterpret_cast<const float*>(rope_cos_f32),
+                                  reinterpret_cast<const float*>(rope_sin_f32), B16(kp), B16(vt), (int)batch, (int)heads, (int)kv_len,
+                                  (int)kv_pad, S(stream));
+}
+
+int vsys_flash_attn_d72_rope(const void* q, int64_t q_stride, const void* rope_cos_f32, const void* rope_sin_f32, const void* kp,
+                             const void* vt, void* out, int64_t out_stride, int64_t batch, int64_t heads, int64_t q_len,
+                             int64_t kv_len, int64_t kv_pad, void* stream) {
+  if (!q || !kp || !vt || !out) return VSYS_ERR_ARG;
+  if (!rope_cos_f32 || !rope_sin_f32) return VSYS_ERR_SHAPE;   // no rotation: vsys_flash_attn_d72
+  if (!fits_int(batch, heads, q_len, kv_len, kv_pad) || batch * heads > 65535) return VSYS_ERR_SHAPE;
+  for (const void* ptr : {q, rope_cos_f32, rope_sin_f32, kp, vt})
+    if (reinterpret_cast<uintptr_t>(ptr) & 15) return VSYS_ERR_ALIGN;
+  if (reinterpret_cast<uintptr_t>(out) & 7) return VSYS_ERR_ALIGN;
+  return launch_flash_attn_d72_rope(B16(q), q_stride, reinterpret_cast<const float*>(rope_cos_f32),
+                                    reinterpret_cast<const float*>(rope_sin_f32), B16(kp), B16(vt), B16(out), out_stride, (int)batch,
+                                    (int)heads, (int)q_len, (int)kv_len, (int)kv_pad, S(stream));
+}
+
 int vsys_flash_attn_d72_kb(const void* q, int64_t q_stride, const void* q_norm_w, const void* kp, const void* vt, void* out,
                            int64_t out_stride, int64_t batch, int64_t heads, int64_t q_len, int64_t kv_len, int64_t kv_pad, float eps,
                            float k_norm_bound, void* stream) {

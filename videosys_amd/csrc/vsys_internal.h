@@ -273,6 +273,13 @@ int launch_flash_attn_d64(const bf16_t* q, int64_t q_stride, const bf16_t* ln_w,
                           const float* rope_sin, int rope_start, int rope_len, const bf16_t* kp, const bf16_t* vt, bf16_t* out,
                           int64_t out_stride, int batch, int heads, int q_len, int kv_len, int kv_pad, float eps, float k_bound,
                           hipStream_t stream);
+// Open-Sora-Plan v1.1: head dim 72 with interleaved-pair RoPE tables [len][36] per token (attention.hip)
+int launch_attn_prep_kv_rope(const bf16_t* k, int64_t k_stride, const bf16_t* v, int64_t v_stride, const float* rope_cos,
+                             const float* rope_sin, bf16_t* kp, bf16_t* vt, int batch, int heads, int kv_len, int kv_pad,
+                             hipStream_t stream);
+int launch_flash_attn_d72_rope(const bf16_t* q, int64_t q_stride, const float* rope_cos, const float* rope_sin, const bf16_t* kp,
+                               const bf16_t* vt, bf16_t* out, int64_t out_stride, int batch, int heads, int q_len, int kv_len,
+                               int kv_pad, hipStream_t stream);
 // Open-Sora-Plan v1.2: head dim 96 with RoPE3D tables per token (attention96.hip)
 int launch_attn_prep_kv96(const bf16_t* k, int64_t k_stride, const bf16_t* v, int64_t v_stride, const float* rope_cos,
                           const float* rope_sin, bf16_t* kp, bf16_t* vt, int batch, int heads, int kv_len, int kv_pad,

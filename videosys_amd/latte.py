@@ -269,14 +269,8 @@ class LatteT2V:
         else:
             qkv = self._gemm(xm, p + ".attn1.qkv", out=self._buf("qkv", (N, 3 * C)))
             ao = self._buf("attn_out", (N, C))
-        if temporal and qkv is None:
-            pass
-        elif temporal:
-            ops.attn_temporal(qkv, C, None, None, None, None, ao, B, Fr, S, H)
-        else:
-            kp, vt = self._ws.once(("kv_spatial", B * Fr, S), lambda: ops.alloc_kv_buffers(B * Fr, H, S, self.device))
-            ops.attn_prep_kv(qkv[:, C:2 * C], qkv[:, 2 * C:], None, kp, vt, B * Fr, H, S)
-            ops.flash_attn(qkv[:, :C], None, kp, vt, ao, B * Fr, H, S, S)
+        if qkv is not None:
+            self._attention(qkv, ao, B, Fr, S, temporal)
         aux = None
         if use_pab:
             if st.last_attn is None or st.last_attn.shape != x.shape:
@@ -284,6 +278,16 @@ class LatteT2V:
             aux = st.last_attn
         ops.gemm(ao, w[p + ".attn1.to_out.0.weight"], w[p + ".attn1.to_out.0.bias"], epilogue=ops.EPI_GATE_RES, gate=gate,
                  gate_stride=C6, rows_per_sample=Fr * S, res=x, aux=aux, out=x)
+
+    def _attention(self, qkv, ao, B, Fr, S, temporal):
+        """attn1 on the qkv rows of one block -> ao (no qk-norm, no rotation; open_sora_plan_v110.LatteT2V overrides it)."""
+        C, H = self.C, self.H
+        if temporal:
+            ops.attn_temporal(qkv, C, None, None, None, None, ao, B, Fr, S, H)
+        else:
+            kp, vt = self._ws.once(("kv_spatial", B * Fr, S), lambda: ops.alloc_kv_buffers(B * Fr, H, S, self.device))
+            ops.attn_prep_kv(qkv[:, C:2 * C], qkv[:, 2 * C:], None, kp, vt, B * Fr, H, S)
+            ops.flash_attn(qkv[:, :C], None, kp, vt, ao, B * Fr, H, S, S)
 
     def _ff(self, i, x, mod_i, B, Fr, S, st, timestep_int, ats, temporal):
         w, C = self.w, self.C

@@ -16,8 +16,8 @@ instead of 16 at the production geometry, about 0.1 ms of a 154 ms step, and was
 Built: norm_type="ada_norm_single", use_rope=True, downsampler=None, patch_size_t=1, activation_fn="gelu-approximate",
 attention_head_dim=96, biased projections, LayerNorms without affine, out_channels in {in_channels, 2 in_channels},
 use_image_num=0.  Anything else raises NotImplementedError at construction — nothing is approximated.  The CausalVAE decode, mT5, the
-sampler and the pipeline / config classes are vae_open_sora_plan.py and pipeline_open_sora_plan.py; not built (follow-ups): v1.1, the
-CFG split (enable_cp).
+sampler and the pipeline / config classes are vae_open_sora_plan.py and pipeline_open_sora_plan.py; not built (follow-ups): the v1.1 pipeline
+(its transformer is open_sora_plan_v110.py), the CFG split (enable_cp).
 
 Sequence parallelism (enable_parallel; :916-941,1716-1728,1896-1900,1975-1979).  The video tokens are split over
 the P ranks at rest (split_sequence, dim 1: rank r holds tokens [r Nl, (r + 1) Nl), Nl = N / P — N % P != 0 is a ValueError, as the

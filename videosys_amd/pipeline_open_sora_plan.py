@@ -1,7 +1,8 @@
 """Open-Sora-Plan v1.2 pipeline plug-in — host mirror of videosys/pipelines/open_sora_plan/pipeline_open_sora_plan.py
 (OpenSoraPlanV120PABConfig :103-120, OpenSoraPlanConfig :123-225, OpenSoraPlanPipeline :228-1193, retrieve_timesteps :1197-1252):
 prompt -> mT5 embeddings with their masks -> Euler-ancestral sampling with OpenSoraT2V (open_sora_plan.py) -> CausalVAE decode
-(vae_open_sora_plan.py) -> uint8 video [B, T, H, W, 3].  v1.1 (LatteT2V, PNDM, its VAE) is not built: ``version="v110"`` raises.
+(vae_open_sora_plan.py) -> uint8 video [B, T, H, W, 3].  The v1.1 PIPELINE (PNDM, its CausalVAE, T5 at 120 tokens) is not built: ``version="v110"`` raises
+(the v1.1 transformer is open_sora_plan_v110.py).
 
 ``OpenSoraPlanConfig`` / ``OpenSoraPlanV120PABConfig`` take the reference's keywords with its defaults and drop into ``VideoSysEngine``.
 
@@ -70,7 +71,8 @@ class OpenSoraPlanConfig:
         self.pipeline_cls = OpenSoraPlanPipeline
         assert version in ["v110", "v120"], f"Unknown Open-Sora-Plan version: {version}"
         if version == "v110":
-            raise NotImplementedError("Open-Sora-Plan v1.1 (LatteT2V, PNDM, its CausalVAE) is not built: version='v120' is")
+            raise NotImplementedError("the Open-Sora-Plan v1.1 pipeline (PNDM, its CausalVAE, T5 at 120 tokens) is not built (its transformer is "
+                                      "open_sora_plan_v110.LatteT2V): version='v120' is")
         self.version = version
         assert transformer_type in V120_TYPES, f"transformer_type must be one of {V120_TYPES}"
         self.transformer_type = transformer_type
