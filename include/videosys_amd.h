@@ -681,6 +681,37 @@ int vsys_cfg_ancestral_step(void* z_f32, const void* model_out_f32, const void* 
 int vsys_pixels_to_u8_trunc(const void* x, const int64_t* grid, int64_t N, int64_t ldx, void* out_u8, int64_t Ftot, int64_t f0,
                             void* stream);
 
+/* Open-Sora-Plan v1.1 CausalVAE decode and sampler (csrc/vae_osp.hip).  Neither has a VSYS_OP code, for the reasons above. */
+/* TimeUpsample2x.forward (autoencoder_kl_open_sora_plan_v110.py:1549-1554) and TimeUpsampleRes2x.forward up to its conv (:1590-1596):
+ * frame 0 is copied; frames 1..T-1 are F.interpolate(scale_factor=(2, 1, 1), mode="trilinear", align_corners=False) of source frames
+ * 1..T-1 taken as a range of their own (weights 1/4 and 3/4, source indices clamped at both ends of THAT range), concatenated:
+ * grid_dst has T == 1 ? 1 : 2T - 1 frames of the same (H, W).  x: bf16 channels-last rows over grid_src; y: rows over grid_dst,
+ * interior rows written only (the destination is the padded input grid of the causal conv that follows).  v = w0 a + w1 b in fp32,
+ * y = bf16(v): one rounding (a frame whose two taps coincide is a copy).  y_res (may be NULL, then grid_res and alpha are unused):
+ * a second destination over its own descriptor grid_res with the frame count, H and W of grid_dst, interior rows only, receives
+ * bf16(alpha * v) from the same fp32 v — the `alpha * x` term of TimeUpsampleRes2x, to be handed to vsys_conv_bf16 as `res` with the
+ * conv's weights and bias scaled by (1 - alpha); alpha = sigmoid(mix_factor) is the host's.  C % 8 == 0, C <= 2048; x, y and y_res
+ * 16-byte aligned and distinct buffers. */
+int vsys_upsample_time2x(const void* x, const int64_t* grid_src, void* y, const int64_t* grid_dst, void* y_res, const int64_t* grid_res,
+                         float alpha, int64_t N, int64_t C, void* stream);
+/* One PNDMScheduler.step of the Open-Sora-Plan v1.1 pipeline (pipeline_open_sora_plan.py with `PNDMScheduler()`, :302-304; diffusers,
+ * third-party) in ONE launch: the CFG combine and the drop of the learned-sigma half, the scheduler update as a linear form, and the
+ * next call's model input.  e = u + guidance (c - u) on the first Cin of the Cout == 2 Cin channels of model_out fp32 [2 Bz, Cout, thw],
+ * negative prompt first (u = model_out[b], c = model_out[b + Bz]).  With S = {e, src0, src1, src2, src3} (src: fp32 [Bz, Cin, thw]):
+ *   e_out   (fp32 [Bz, Cin, thw], may be NULL) = e                                    the history slot
+ *   z_out   (fp32 [Bz, Cin, thw])              = c_base base + sum_i cz[i] S[i]        the previous sample
+ *   aux_out (fp32 [Bz, Cin, thw], may be NULL) = sum_i ca[i] S[i]                      the Runge-Kutta accumulator
+ *   model_in[b] = model_in[b + Bz] (bf16 [2 Bz, Cin, thw]) = the same form in bf16      scale_model_input is the identity
+ * coef: 12 doubles ON THE HOST, read during the call: {guidance, c_base, cz[0..4], ca[0..4]}.  Every form is evaluated in fp64 on the
+ * fp32 operands and each stored value is rounded once from the fp64 value (e enters the sums unrounded; model_in is the fp64 value
+ * rounded to bf16, not the fp32 z_out rounded again — the two differ in about one element in 2^16). A source or base whose weights are all zero is
+ * never read and may be NULL (NaN there is harmless); a non-zero weight on a NULL operand is VSYS_ERR_ARG; ca is ignored when aux_out
+ * is NULL.  Element i of an output depends on element i of the inputs only, so an output may be an input's buffer (base == z_out,
+ * aux_out == a source); the outputs are distinct from each other and from model_out. */
+int vsys_cfg_pndm_step(const void* model_out_f32, void* e_out_f32, const void* src0_f32, const void* src1_f32, const void* src2_f32,
+                       const void* src3_f32, const void* base_f32, void* z_out_f32, void* aux_out_f32, void* model_in, int64_t Bz,
+                       int64_t Cin, int64_t Cout, int64_t thw, const double* coef, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------------------
  * Launch programs.  A denoise step is ~450 launches of the entry points above with arguments that do not change from step to
  * step (workspaces, weights and PAB slabs are resident; per-step values live in device buffers).  The host mirror records the

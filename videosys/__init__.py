@@ -42,6 +42,7 @@ _MODULES = {
     "models.autoencoders.autoencoder_kl_open_sora": "vae_open_sora",    # OpenSoraVAE_V1_2
     "models.autoencoders.autoencoder_kl_cogvideox": "vae_cogvideox",    # AutoencoderKLCogVideoX
     "models.autoencoders.autoencoder_kl_open_sora_plan_v120": "vae_open_sora_plan",   # CausalVAEModelWrapper, CausalVAEModel (decode side)
+    "models.autoencoders.autoencoder_kl_open_sora_plan_v110": "vae_open_sora_plan_v110",   # the v1.1 CausalVAEModelWrapper, CausalVAEModel
     "pipelines.open_sora": "pipeline_open_sora",              # OpenSoraConfig, OpenSoraPABConfig, OpenSoraPipeline
     "pipelines.open_sora.pipeline_open_sora": "pipeline_open_sora",
     "pipelines.latte": "pipeline_latte",
@@ -95,6 +96,12 @@ def _install_aliases():
                 setattr(dp, k, v)
     sys.modules[dp.__name__] = dp
     package(f"{__name__}.pipelines.open_sora").data_process = dp
+    # the v1.1 route of pipelines/open_sora_plan/pipeline_open_sora_plan.py has classes of its own in a module of its own (the module
+    # it belongs to in the reference resolves them lazily, videosys_amd/pipeline_open_sora_plan.py __getattr__): name them here too
+    from videosys_amd import pipeline_open_sora_plan, pipeline_open_sora_plan_v110
+
+    for n in pipeline_open_sora_plan._V110_NAMES:
+        setattr(package(f"{__name__}.pipelines.open_sora_plan"), n, getattr(pipeline_open_sora_plan_v110, n))
 
 
 _install_aliases()

@@ -834,4 +834,24 @@ int vsys_pixels_to_u8_trunc(const void* x, const int64_t* grid, int64_t N, int64
   return launch_pixels_to_u8_trunc(B16(x), g, (int)N, ldx, reinterpret_cast<uint8_t*>(out_u8), Ftot, f0, S(stream));
 }
 
+int vsys_upsample_time2x(const void* x, const int64_t* grid_src, void* y, const int64_t* grid_dst, void* y_res, const int64_t* grid_res,
+                         float alpha, int64_t N, int64_t C, void* stream) {
+  VaeGrid gs, gd, gr;
+  if (!x || !y || !to_grid(grid_src, gs) || !to_grid(grid_dst, gd) || (y_res && !to_grid(grid_res, gr))) return VSYS_ERR_ARG;
+  if (!fits_int(N, C)) return VSYS_ERR_SHAPE;
+  return launch_upsample_time2x(B16(x), gs, B16(y), gd, B16(y_res), y_res ? &gr : nullptr, alpha, (int)N, (int)C, S(stream));
+}
+
+int vsys_cfg_pndm_step(const void* model_out_f32, void* e_out_f32, const void* src0_f32, const void* src1_f32, const void* src2_f32,
+                       const void* src3_f32, const void* base_f32, void* z_out_f32, void* aux_out_f32, void* model_in, int64_t Bz,
+                       int64_t Cin, int64_t Cout, int64_t thw, const double* coef, void* stream) {
+  if (!model_out_f32 || !z_out_f32 || !model_in || !coef) return VSYS_ERR_ARG;
+  if (!fits_int(Bz, Cin, Cout) || thw < 0) return VSYS_ERR_SHAPE;
+  const float* src[4] = {reinterpret_cast<const float*>(src0_f32), reinterpret_cast<const float*>(src1_f32),
+                         reinterpret_cast<const float*>(src2_f32), reinterpret_cast<const float*>(src3_f32)};
+  return launch_cfg_pndm_step(reinterpret_cast<const float*>(model_out_f32), reinterpret_cast<float*>(e_out_f32), src,
+                              reinterpret_cast<const float*>(base_f32), reinterpret_cast<float*>(z_out_f32),
+                              reinterpret_cast<float*>(aux_out_f32), B16(model_in), (int)Bz, (int)Cin, (int)Cout, thw, coef, S(stream));
+}
+
 }  // extern "C"

@@ -27,11 +27,12 @@ PYM = os.path.join(ROOT, "videosys_amd", "_opcodes.py")
 #  vsys_attn_prep_kv96 / vsys_flash_attn_d96: a recorded Open-Sora-Plan step replays them from host closures, open_sora_plan_ops.py;
 #  vsys_attn_prep_kv96_img / vsys_flash_attn_d96_img: the same, on the exchange image of a sequence-parallel step;
 #  vsys_attn_prep_kv_rope / vsys_flash_attn_d72_rope: the same for Open-Sora-Plan v1.1, open_sora_plan_v110_ops.py;
-#  vsys_cfg_ancestral_step: the Open-Sora-Plan sampler launches it from the host after each replay, its scalars change every step)
+#  vsys_cfg_ancestral_step: the Open-Sora-Plan sampler launches it from the host after each replay, its scalars change every step;
+#  vsys_cfg_pndm_step: the same for the v1.1 sampler, whose pointers rotate as well; vsys_upsample_time2x: the v1.1 VAE decode)
 NO_OP = {"vsys_vae_first_im2col_nc", "vsys_pixels_to_u8", "vsys_clip_attention_d64", "vsys_splitk_reduce_bias_act",
          "vsys_attn_temporal_d64_img", "vsys_attn_prep_kv96", "vsys_flash_attn_d96", "vsys_upsample_trilinear2x",
          "vsys_cfg_ancestral_step", "vsys_pixels_to_u8_trunc", "vsys_attn_prep_kv96_img", "vsys_flash_attn_d96_img",
-         "vsys_attn_prep_kv_rope", "vsys_flash_attn_d72_rope"}
+         "vsys_attn_prep_kv_rope", "vsys_flash_attn_d72_rope", "vsys_upsample_time2x", "vsys_cfg_pndm_step"}
 BEGIN, END = "/* >>> VSYS_OP codes (generated: csrc/gen/program_gen.py) */", "/* <<< VSYS_OP codes */"
 
 

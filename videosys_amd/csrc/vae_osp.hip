@@ -1,4 +1,4 @@
-// The three kernels the Open-Sora-Plan v1.2 pipeline needs beside the ones it shares with the other families
+// The kernels the Open-Sora-Plan pipelines need beside the ones they share with the other families.  v1.2
 // (autoencoder_kl_open_sora_plan_v120.py, pipeline_open_sora_plan.py):
 //
 //   vsys_upsample_trilinear2x   Spatial2xTime2x3DUpsample.forward (:349-357) up to its conv: F.interpolate(mode="trilinear") of frame 0
@@ -6,6 +6,14 @@
 //   vsys_cfg_ancestral_step     CFG combine + EulerAncestralDiscreteScheduler.step + the next step's scale_model_input, one launch
 //   vsys_pixels_to_u8_trunc     conv_out rows -> uint8 [F][H][W][3] with the reference's own post-process (:1186-1188: bf16 tensor
 //                               arithmetic, then a truncating cast)
+//
+// v1.1 (autoencoder_kl_open_sora_plan_v110.py, pipeline_open_sora_plan.py with PNDMScheduler):
+//
+//   vsys_upsample_time2x        TimeUpsample2x.forward (:1545-1554) / TimeUpsampleRes2x.forward (:1590-1596) up to its conv: frame 0 copied,
+//                               frames 1.. interpolated by (2, 1, 1) among themselves, written into the interior of the conv's padded
+//                               input grid; optionally alpha * the same value into a second grid (the conv's residual operand)
+//   vsys_cfg_pndm_step          CFG combine + one PNDMScheduler.step (a Runge-Kutta warm-up call or the linear multistep) + the next
+//                               call's model input, one launch
 //
 // Grid convention (VaeGrid, grid_row) as in vae_ops.hip: kernels read and write INTERIOR rows only.
 #include "common.h"
@@ -109,6 +117,101 @@ __global__ __launch_bounds__(256) void cfg_ancestral_kernel(float* __restrict__ 
   }
 }
 
+// Block = one destination image row (n, t, h), thread = (pixel lane, 8-channel chunk) as upsample_trilinear2x_kernel; the frame taps
+// are block-uniform.  A destination frame whose two taps are the same source frame (frame 0; both frames of a one-frame range) is that
+// frame's bits.  Otherwise v = w0 a + w1 b in fp32 (exact: a bf16 value times k / 4 has ten significant bits, the sum one rounding)
+// and y = bf16(v).  RES: y2 = bf16(alpha * v) from the same fp32 v, over its own grid.
+template <bool RES>
+__global__ __launch_bounds__(256) void upsample_time2x_kernel(const bf16_t* __restrict__ x, VaeGrid gs, bf16_t* __restrict__ y, VaeGrid gd,
+                                                              bf16_t* __restrict__ y2, VaeGrid g2, float alpha, int C, int N) {
+  const int nch = C >> 3;
+  const int lanes = 256 / nch;
+  const int ch = threadIdx.x % nch, pl = threadIdx.x / nch;
+  if (pl >= lanes) return;
+  const int64_t nrows = (int64_t)N * gd.T * gd.H;
+  for (int64_t br = blockIdx.x; br < nrows; br += gridDim.x) {
+    const int h = (int)(br % gd.H);
+    const int64_t r1 = br / gd.H;
+    const int t = (int)(r1 % gd.T), n = (int)(r1 / gd.T);
+    Taps tt;
+    if (t == 0) { tt.i0 = tt.i1 = 0; tt.w0 = 1.f; tt.w1 = 0.f; }   // frame 0 is copied
+    else tt = taps2x(t - 1, 1, gs.T - 1);                          // frames 1.. among themselves
+    const bool same = tt.i0 == tt.i1;
+    const bf16_t* s0 = x + grid_row(gs, n, tt.i0, h, 0) * C + ch * 8;
+    const bf16_t* s1 = x + grid_row(gs, n, tt.i1, h, 0) * C + ch * 8;
+    bf16_t* yr = y + grid_row(gd, n, t, h, 0) * C + ch * 8;
+    bf16_t* y2r = RES ? y2 + grid_row(g2, n, t, h, 0) * C + ch * 8 : nullptr;
+    for (int w = pl; w < gd.W; w += lanes) {
+      const int64_t o = (int64_t)w * C;
+      const uint4 va = *reinterpret_cast<const uint4*>(s0 + o);
+      float a[8], b[8], acc[8];
+      unpack8(va, a);
+      if (same) {
+        *reinterpret_cast<uint4*>(yr + o) = va;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] = a[e];
+      } else {
+        unpack8(*reinterpret_cast<const uint4*>(s1 + o), b);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] = tt.w0 * a[e] + tt.w1 * b[e];
+        *reinterpret_cast<uint4*>(yr + o) = pack8(acc);
+      }
+      if (RES) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] *= alpha;
+        *reinterpret_cast<uint4*>(y2r + o) = pack8(acc);
+      }
+    }
+  }
+}
+
+// e = uncond + g (cond - uncond) on the first Cin of Cout channels (negative prompt first), then two linear forms over S = {e, src[0..3]}:
+// z_out = c_base base + sum cz[i] S[i] and aux_out = sum ca[i] S[i].  Everything is evaluated in fp64 on the fp32 operands and every
+// stored value is rounded once, as cfg_ancestral_kernel does.  A source is read only where one of its weights is non-zero, and enters
+// only the sums whose weight is non-zero.  Element i of every output depends on element i of the inputs alone and a thread reads all
+// of them before it writes, so an output may share its buffer with an input (base == z_out: the multistep runs in place; aux_out ==
+// src[k]: the Runge-Kutta accumulator) — hence no __restrict__ on them.
+struct PndmArgs {
+  const float* src[4];
+  double g, cb, cz[5], ca[5];
+};
+__global__ __launch_bounds__(256) void cfg_pndm_kernel(const float* model_out, float* e_out, PndmArgs a, const float* base, float* z_out,
+                                                       float* aux_out, bf16_t* __restrict__ model_in, int Bz, int Cin, int Cout,
+                                                       int64_t thw) {
+  const int64_t per = (int64_t)Cin * thw;
+  const int64_t total = (int64_t)Bz * per;
+  const int64_t b = blockIdx.y;                   // one sample per grid row: no division in the loop
+  const float* mu = model_out + b * Cout * thw;
+  const float* mc = model_out + (b + Bz) * Cout * thw;
+  for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < per; r += (int64_t)gridDim.x * 256) {
+    const int64_t i = b * per + r;                // r = c * thw + position, c < Cin: the same offset inside a model_out sample
+    const double unc = mu[r];
+    const double cond = mc[r];
+    const double e = unc + a.g * (cond - unc);
+    double z = a.cb != 0.0 ? a.cb * (double)base[i] : 0.0;
+    double aux = 0.0;
+    if (a.cz[0] != 0.0) z += a.cz[0] * e;
+    if (a.ca[0] != 0.0) aux += a.ca[0] * e;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (a.cz[k + 1] != 0.0 || a.ca[k + 1] != 0.0) {
+        const double s = a.src[k][i];
+        if (a.cz[k + 1] != 0.0) z += a.cz[k + 1] * s;
+        if (a.ca[k + 1] != 0.0) aux += a.ca[k + 1] * s;
+      }
+    }
+    const float zn = (float)z;
+    if (e_out) e_out[i] = (float)e;
+    if (aux_out) aux_out[i] = (float)aux;
+    z_out[i] = zn;
+    // one rounding of the fp64 value, like every other store — NOT bf16(zn): the compiler folds (bf16)(float)z into this conversion
+    // anyway (round-to-odd to fp32, then to bf16), so it is spelled out; the two differ in about one element in 2^16
+    const bf16_t m = __builtin_bit_cast(bf16_t, (__bf16)z);
+    model_in[i] = m;
+    model_in[total + i] = m;
+  }
+}
+
 // bf16 pixel value -> the byte of OpenSoraPlanPipeline.decode_latents (:1186-1188), every tensor op of the reference rounding to bf16:
 // d = clamp(bf16(bf16(x / 2) + 0.5), 0, 1), m = bf16(d * 255), byte = trunc(m) (m is a non-negative integer-or-fraction <= 255).
 __device__ __forceinline__ uint32_t pixel_byte_trunc(uint32_t bits16) {
@@ -192,6 +295,45 @@ int launch_cfg_ancestral_step(float* z, const float* model_out, const float* noi
   if (total == 0) return 0;
   hipLaunchKernelGGL(cfg_ancestral_kernel, dim3(grid_for(total)), dim3(256), 0, stream, z, model_out, noise, model_in, Bz, Cin, Cout,
                      thw, guidance, dt, sigma_up, in_scale);
+  return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
+}
+
+int launch_upsample_time2x(const bf16_t* x, const VaeGrid& gs, bf16_t* y, const VaeGrid& gd, bf16_t* y_res, const VaeGrid* g_res,
+                           float alpha, int N, int C, hipStream_t stream) {
+  if (!x || !y || (y_res && !g_res)) return VSYS_ERR_ARG;
+  if (N < 0 || N > 65535 || !grid_ok(gs) || !grid_ok(gd) || gd.T != (gs.T == 1 ? 1 : 2 * gs.T - 1) || gd.H != gs.H || gd.W != gs.W ||
+      C <= 0 || C % 8 != 0 || C > 2048)
+    return VSYS_ERR_SHAPE;
+  if (y_res && (!grid_ok(*g_res) || g_res->T != gd.T || g_res->H != gd.H || g_res->W != gd.W)) return VSYS_ERR_SHAPE;
+  if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(y) % 16 || reinterpret_cast<uintptr_t>(y_res) % 16)
+    return VSYS_ERR_ALIGN;
+  if (N == 0) return 0;
+  const int64_t nrows = (int64_t)N * gd.T * gd.H;
+  const dim3 grid((unsigned)(nrows < 65536 ? nrows : 65536));
+  if (y_res)
+    hipLaunchKernelGGL(upsample_time2x_kernel<true>, grid, dim3(256), 0, stream, x, gs, y, gd, y_res, *g_res, alpha, C, N);
+  else
+    hipLaunchKernelGGL(upsample_time2x_kernel<false>, grid, dim3(256), 0, stream, x, gs, y, gd, (bf16_t*)nullptr, gd, 0.f, C, N);
+  return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
+}
+
+int launch_cfg_pndm_step(const float* model_out, float* e_out, const float* const* src, const float* base, float* z_out, float* aux_out,
+                         bf16_t* model_in, int Bz, int Cin, int Cout, int64_t thw, const double* coef, hipStream_t stream) {
+  if (!model_out || !z_out || !model_in || !coef) return VSYS_ERR_ARG;
+  PndmArgs a;
+  a.g = coef[0];
+  a.cb = coef[1];
+  for (int k = 0; k < 5; ++k) { a.cz[k] = coef[2 + k]; a.ca[k] = aux_out ? coef[7 + k] : 0.0; }   // no aux_out: nothing to store
+  for (int k = 0; k < 4; ++k) {
+    a.src[k] = src[k];
+    if (!src[k] && (a.cz[k + 1] != 0.0 || a.ca[k + 1] != 0.0)) return VSYS_ERR_ARG;   // a weight on a source that is not there
+  }
+  if (!base && a.cb != 0.0) return VSYS_ERR_ARG;
+  if (Bz < 0 || Bz > 65535 || Cin <= 0 || Cout != 2 * Cin || thw < 0) return VSYS_ERR_SHAPE;
+  const int64_t total = (int64_t)Bz * Cin * thw;
+  if (total == 0) return 0;
+  hipLaunchKernelGGL(cfg_pndm_kernel, dim3(grid_for((int64_t)Cin * thw), (unsigned)Bz), dim3(256), 0, stream, model_out, e_out, a, base, z_out, aux_out, model_in, Bz,
+                     Cin, Cout, thw);
   return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
 }
 

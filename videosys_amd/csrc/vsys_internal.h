@@ -162,6 +162,12 @@ int launch_cfg_ancestral_step(float* z, const float* model_out, const float* noi
                               int64_t thw, float guidance, float dt, float sigma_up, float in_scale, hipStream_t stream);
 int launch_pixels_to_u8_trunc(const bf16_t* x, const VaeGrid& g, int N, int64_t ldx, uint8_t* out, int64_t Ftot, int64_t f0,
                               hipStream_t stream);
+// Open-Sora-Plan v1.1 CausalVAE decode and sampler (vae_osp.hip); g_res belongs to y_res (both null: no second destination),
+// src: four pointers, coef: {guidance, c_base, cz[5], ca[5]} on the host
+int launch_upsample_time2x(const bf16_t* x, const VaeGrid& gs, bf16_t* y, const VaeGrid& gd, bf16_t* y_res, const VaeGrid* g_res,
+                           float alpha, int N, int C, hipStream_t stream);
+int launch_cfg_pndm_step(const float* model_out, float* e_out, const float* const* src, const float* base, float* z_out, float* aux_out,
+                         bf16_t* model_in, int Bz, int Cin, int Cout, int64_t thw, const double* coef, hipStream_t stream);
 
 // T5 encoder pieces (t5_ops.hip)
 int launch_gather_rows(const bf16_t* table, const int64_t* ids, bf16_t* out, int64_t n, int C, int64_t vocab, hipStream_t stream);

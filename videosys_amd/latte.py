@@ -164,6 +164,14 @@ class LatteT2V:
                                 lens=lens, kp=kps, vt=vts, Lk=Lk)
         return self._text_cache
 
+    def step_timesteps(self, B: int) -> torch.Tensor:
+        """The resident fp32 [B] buffer the timestep embedding reads.  forward() fills it from ``timestep``; a sampler that replays a
+        recorded step writes the step's timestep here instead (as open_sora_plan.OpenSoraT2V.step_timesteps)."""
+        bufs = self.__dict__.setdefault("_ts_bufs", {})
+        if B not in bufs:
+            bufs[B] = torch.empty(B, dtype=torch.float32, device=self.device)
+        return bufs[B]
+
     def reset_text_cache(self):
         self._text_cache = None
 
@@ -187,7 +195,9 @@ class LatteT2V:
         ts_host = timestep.detach().to("cpu").float().reshape(-1)
         if ts_host.numel() != B:
             ts_host = ts_host.repeat(B // ts_host.numel())
-        f = ops.timestep_embedding(ts_host.to(dev).contiguous(), 256)
+        tsb = self.step_timesteps(B)
+        tsb.copy_(ts_host)
+        f = ops.timestep_embedding(tsb, 256)
         e1 = ops.linear_small(f, w["adaln_single.emb.timestep_embedder.linear_1.weight"],
                               w["adaln_single.emb.timestep_embedder.linear_1.bias"], act_out=ops.ACT_SILU)
         emb = ops.linear_small(e1, w["adaln_single.emb.timestep_embedder.linear_2.weight"],

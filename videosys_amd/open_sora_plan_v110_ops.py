@@ -1,17 +1,22 @@
-"""Tensor-level wrappers of the two entry points that exist for Open-Sora-Plan v1.1 (include/videosys_amd.h): the head-dim-72 spatial
+"""Tensor-level wrappers of the entry points that exist for Open-Sora-Plan v1.1 (include/videosys_amd.h): the head-dim-72 spatial
 attention with a per-token rotation of interleaved column pairs, vsys_attn_prep_kv_rope (K side, writes the (kp, vt) pair of
-ops.attn_prep_kv) and vsys_flash_attn_d72_rope (Q side, the streaming 32-rows-per-wave flash kernel).  HIP device tensors only, no eager
+ops.attn_prep_kv) and vsys_flash_attn_d72_rope (Q side, the streaming 32-rows-per-wave flash kernel), and, at the end of the file, the
+temporal upsampler of its CausalVAE and its sampler step (vsys_upsample_time2x, vsys_cfg_pndm_step).  HIP device tensors only, no eager
 fallback.
 
 Neither has an op code (the op table is pinned, csrc/gen/program_gen.py NO_OP): the launch goes through ctypes on torch's current stream
 and, under a launch-program recorder, is a ``program.host_call`` closure, as in open_sora_plan_ops.py.
-Element-wise tests: tests/test_gpu_osp_v110_attention.py; guard bands: tests/test_gpu_isolation_osp_v110.py."""
+Element-wise tests: tests/test_gpu_osp_v110_attention.py, tests/test_gpu_osp_v110_kernels.py; guard bands:
+tests/test_gpu_isolation_osp_v110.py, tests/test_gpu_isolation_osp_v110_pipeline.py."""
 from __future__ import annotations
+
+import ctypes
 
 import torch
 
+from . import program
 from .open_sora_plan_ops import _issue
-from .ops import HEAD_DIM, VT_ROWS, _bf16, _chk, alloc_kv_buffers, kv_pad_len  # noqa: F401  (alloc_kv_buffers, kv_pad_len: re-exported)
+from .ops import HEAD_DIM, VT_ROWS, VaeGrid, _bf16, _call, _chk, _p, alloc_kv_buffers, kv_pad_len  # noqa: F401  (alloc_kv_buffers, kv_pad_len: re-exported)
 
 PAIRS = HEAD_DIM // 2    # 36 (cos, sin) entries per token: entry p rotates the columns (2p, 2p + 1) of every head
 
@@ -54,3 +59,57 @@ def flash_attn_rope(q, rope_cos, rope_sin, kp, vt, out, batch, heads, q_len, kv_
            (q.data_ptr(), q.stride(0), rope_cos.data_ptr(), rope_sin.data_ptr(), kp.data_ptr(), vt.data_ptr(), out.data_ptr(), out.stride(0),
             batch, heads, q_len, kv_len, kv_pad))
     return out
+
+
+# ------------------------------------------------------------------------------------------------ CausalVAE decode and sampler
+# (csrc/vae_osp.hip; no op codes, as their v1.2 siblings of open_sora_plan_ops.py: ctypes on torch's current stream, refused under a
+#  recorder — the decode is not part of a recorded step and the sampler step is launched by the host after each replay)
+def upsample_time2x(x, gs: VaeGrid, y, gd: VaeGrid, C, y_res=None, g_res: VaeGrid = None, alpha: float = 0.0):
+    """TimeUpsample2x / TimeUpsampleRes2x up to its conv: x rows over gs -> the interior rows of gd ((1 if T == 1 else 2T - 1) frames of
+    the same (H, W)); frame 0 copied, the later frames interpolated by (2, 1, 1) among themselves in fp32, one rounding.  ``y_res`` rows
+    over ``g_res`` (same frames, H and W): bf16(alpha * v) from the same fp32 value (include/videosys_amd.h)."""
+    assert program.active() is None, "vsys_upsample_time2x has no op code"
+    assert C % 8 == 0 and 0 < C <= 2048, f"C = {C}: a multiple of 8, at most 2048"
+    assert (gd.n, gd.T, gd.H, gd.W) == (gs.n, 1 if gs.T == 1 else 2 * gs.T - 1, gs.H, gs.W), "grid_dst does not match grid_src"
+    assert x.shape == (gs.rows, C) and y.shape == (gd.rows, C) and x.is_contiguous() and y.is_contiguous()
+    if y_res is not None:
+        assert g_res is not None and (g_res.n, g_res.T, g_res.H, g_res.W) == (gd.n, gd.T, gd.H, gd.W), "grid_res does not match grid_dst"
+        assert y_res.shape == (g_res.rows, C) and y_res.is_contiguous()
+    _chk(x, y, y_res)          # (after the argument checks: a wrong call is refused as such on any device, before any launch)
+    _bf16(x, y, y_res)
+    _call("vsys_upsample_time2x", _p(x), gs._c, _p(y), gd._c, _p(y_res), None if y_res is None else g_res._c, float(alpha), gs.n, C)
+    return y
+
+
+def cfg_pndm_step(model_out, model_in, z_out, guidance, c_base, cz, ca=None, base=None, srcs=(), e_out=None, aux_out=None):
+    """One launch per sampler call (vsys_cfg_pndm_step): e = u + guidance (c - u) with u = model_out[b], c = model_out[b + Bz] on the first
+    Cin of the 2 Cin channels of model_out fp32 [2 Bz, 2 Cin, ...]; over S = (e, *srcs) (up to four fp32 tensors like z_out, None = absent)
+    z_out = c_base base + sum cz[i] S[i], aux_out = sum ca[i] S[i], e_out = e, both halves of model_in bf16 [2 Bz, Cin, ...] = the same
+    form as z_out rounded to bf16.  fp64 arithmetic on the fp32 operands, one rounding per stored value FROM THE fp64 VALUE (model_in
+    is not the fp32 z_out rounded again).  ``base`` may be ``z_out``, ``aux_out`` may be one of ``srcs``.
+    ``cz`` / ``ca``: up to five host floats each (missing ones are 0)."""
+    srcs = tuple(srcs) + (None,) * (4 - len(srcs))
+    assert len(srcs) == 4, "at most four sources"
+    assert program.active() is None, "vsys_cfg_pndm_step has no op code: launch it after the replay"
+    Bz, Cin = z_out.shape[:2]
+    thw = z_out[0, 0].numel()
+    assert model_out.dtype == torch.float32 and model_out.is_contiguous()
+    assert model_out.shape[1] == 2 * Cin, f"model_out has {model_out.shape[1]} channels, not 2 x {Cin} (learned sigma)"
+    assert tuple(model_out.shape) == (2 * Bz, 2 * Cin) + tuple(z_out.shape[2:]), (tuple(model_out.shape), tuple(z_out.shape))
+    assert model_in.is_contiguous() and tuple(model_in.shape) == (2 * Bz,) + tuple(z_out.shape[1:])
+    for t in (z_out, base, e_out, aux_out) + srcs:
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.shape == z_out.shape)
+    outs = [t for t in (z_out, e_out, aux_out) if t is not None]
+    assert len({t.data_ptr() for t in outs}) == len(outs), "the outputs must be distinct buffers"
+    cz = [float(v) for v in cz] + [0.0] * (5 - len(cz))
+    ca = [float(v) for v in (ca or ())] + [0.0] * (5 - len(ca or ()))
+    assert len(cz) == 5 and len(ca) == 5
+    for k, t in enumerate(srcs):
+        assert t is not None or (cz[k + 1] == 0.0 and (ca[k + 1] == 0.0 or aux_out is None)), f"a non-zero weight on source {k}, which is None"
+    assert base is not None or float(c_base) == 0.0, "a non-zero c_base, but no base"
+    _chk(model_out, model_in, z_out, base, e_out, aux_out, *srcs)       # (after the argument checks, as above)
+    _bf16(model_in)
+    coef = (ctypes.c_double * 12)(float(guidance), float(c_base), *cz, *ca)
+    _call("vsys_cfg_pndm_step", _p(model_out), _p(e_out), *[_p(t) for t in srcs], _p(base), _p(z_out), _p(aux_out), _p(model_in), Bz, Cin,
+          2 * Cin, thw, coef)
+    return z_out, model_in

@@ -1,8 +1,9 @@
 """Open-Sora-Plan v1.2 pipeline plug-in — host mirror of videosys/pipelines/open_sora_plan/pipeline_open_sora_plan.py
 (OpenSoraPlanV120PABConfig :103-120, OpenSoraPlanConfig :123-225, OpenSoraPlanPipeline :228-1193, retrieve_timesteps :1197-1252):
 prompt -> mT5 embeddings with their masks -> Euler-ancestral sampling with OpenSoraT2V (open_sora_plan.py) -> CausalVAE decode
-(vae_open_sora_plan.py) -> uint8 video [B, T, H, W, 3].  The v1.1 PIPELINE (PNDM, its CausalVAE, T5 at 120 tokens) is not built: ``version="v110"`` raises
-(the v1.1 transformer is open_sora_plan_v110.py).
+(vae_open_sora_plan.py) -> uint8 video [B, T, H, W, 3].  The v1.1 pipeline (PNDM, its CausalVAE, T5 at 300 tokens) has classes of its own in
+pipeline_open_sora_plan_v110.py (``OpenSoraPlanV110Config`` / ``OpenSoraPlanV110Pipeline``; ``OpenSoraPlanV110PABConfig`` is also
+reachable from here, as in the reference's module); ``version="v110"`` on the classes below still raises.
 
 ``OpenSoraPlanConfig`` / ``OpenSoraPlanV120PABConfig`` take the reference's keywords with its defaults and drop into ``VideoSysEngine``.
 
@@ -71,8 +72,8 @@ class OpenSoraPlanConfig:
         self.pipeline_cls = OpenSoraPlanPipeline
         assert version in ["v110", "v120"], f"Unknown Open-Sora-Plan version: {version}"
         if version == "v110":
-            raise NotImplementedError("the Open-Sora-Plan v1.1 pipeline (PNDM, its CausalVAE, T5 at 120 tokens) is not built (its transformer is "
-                                      "open_sora_plan_v110.LatteT2V): version='v120' is")
+            raise NotImplementedError("the Open-Sora-Plan v1.1 pipeline has classes of its own: OpenSoraPlanV110Config / "
+                                      "OpenSoraPlanV110Pipeline (pipeline_open_sora_plan_v110.py); this class builds version='v120'")
         self.version = version
         assert transformer_type in V120_TYPES, f"transformer_type must be one of {V120_TYPES}"
         self.transformer_type = transformer_type
@@ -237,6 +238,8 @@ class OpenSoraPlanPipeline(VideoSysPipeline):
 
     tokenizer = property(lambda self: getattr(self.text_encoder, "tokenizer", None))
 
+    TEXT_VOCAB, TEXT_MAX_LENGTH = MT5_VOCAB, 512          # (the v1.1 pipeline: T5 v1.1's vocabulary, 300 tokens)
+
     def _build_text_encoder(self, spec, tokenizer):
         """mT5 = t5.T5Encoder(vocab_size=250112); ``"synthetic:<seed>"``: XXL geometry when the transformer takes 4096-wide captions,
         else 2 layers (tests) of the caption width rounded up to the encoder's 128-column granularity, of which the first
@@ -248,15 +251,15 @@ class OpenSoraPlanPipeline(VideoSysPipeline):
             dm = -(-d // 128) * 128
             geo = dict(d_model=4096, d_ff=10240, num_layers=24, num_heads=64) if d == 4096 else \
                 dict(d_model=dm, d_ff=2 * dm, num_layers=2, num_heads=max(dm // 64, 2))
-            enc = T5Encoder(device=self._device, vocab_size=MT5_VOCAB, **geo).init_random_(int(spec.split(":", 1)[1]))
+            enc = T5Encoder(device=self._device, vocab_size=self.TEXT_VOCAB, **geo).init_random_(int(spec.split(":", 1)[1]))
 
             class Narrow(T5TextEncoder):
                 def __call__(self, prompts):
                     emb, mask = super().__call__(prompts)
                     return emb[..., :d].contiguous(), mask
 
-            return Narrow(enc, tokenizer or ByteTokenizer(MT5_VOCAB), max_length=512)
-        return build_text_encoder(spec, tokenizer, device=self._device, caption_channels=d, max_length=512)
+            return Narrow(enc, tokenizer or ByteTokenizer(self.TEXT_VOCAB), max_length=self.TEXT_MAX_LENGTH)
+        return build_text_encoder(spec, tokenizer, device=self._device, caption_channels=d, max_length=self.TEXT_MAX_LENGTH)
 
     def _vae_from_state(self, sd):
         from .vae_open_sora_plan import CausalVAEModelWrapper
@@ -317,8 +320,9 @@ class OpenSoraPlanPipeline(VideoSysPipeline):
         return clean_caption(caption, mid_strip=False)
 
     def encode_prompt(self, *args, **kwargs):
-        """:375-536 is the v1.1 path (T5 v1.1 at 120 tokens, embeddings cut to the prompt): not built."""
-        raise NotImplementedError("OpenSoraPlanPipeline.encode_prompt is the v1.1 text path; v1.2 uses encode_prompt_v120")
+        """:375-536 is the v1.1 path (T5 v1.1 at 300 tokens, embeddings cut to the prompt): OpenSoraPlanV110Pipeline.encode_prompt."""
+        raise NotImplementedError("OpenSoraPlanPipeline.encode_prompt is the v1.1 text path (OpenSoraPlanV110Pipeline.encode_prompt); "
+                                  "v1.2 uses encode_prompt_v120")
 
     def _encode(self, prompts, max_length):
         if self.text_encoder is None:
@@ -599,3 +603,16 @@ def _geometry(frames_lat, h, w):
 
 _V120_GEOMETRY = {"29x480p": _geometry(8, 60, 80), "93x480p": _geometry(24, 60, 80), "29x720p": _geometry(8, 90, 160),
                   "93x720p": _geometry(24, 90, 160)}
+
+
+# ---------------------------------------------------------------------------------------------------- the v1.1 names
+_V110_NAMES = ("OpenSoraPlanV110PABConfig", "OpenSoraPlanV110Config", "OpenSoraPlanV110Pipeline", "PNDMScheduler")
+
+
+def __getattr__(name):
+    """The v1.1 classes live in pipeline_open_sora_plan_v110.py, which imports this module: resolved on first use."""
+    if name in _V110_NAMES:
+        from . import pipeline_open_sora_plan_v110 as v110
+
+        return getattr(v110, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -139,26 +139,35 @@ class CausalVAEDecoder(VaeBlocks):
     """Decode side of the reference ``CausalVAEModel``: ``decode(z)``, z [B, 4, T, H, W] (already divided by 0.18215 unless
     ``in_scale`` says otherwise) -> [B, 3, 4(T-1)+1, 8H, 8W] bf16, with the reference's tiling attributes."""
 
+    # what a decoder of the same family with other upsamplers overrides (vae_open_sora_plan_v110.py)
+    SPATIAL = SPATIAL_UPSAMPLE
+    TILE_DEFAULTS = dict(tile_sample_min_size=256, tile_sample_min_size_t=33, tile_latent_min_size_t=16, tile_overlap_factor=0.125)
+    _check = staticmethod(_check_config)
+
+    @staticmethod
+    def _param_shapes(hidden_size: int) -> Dict[str, tuple]:
+        return decoder_param_shapes(hidden_size)
+
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", hidden_size: Optional[int] = None, **config):
-        _check_config(config)
+        self._check(config)
         super().__init__(device)
         dev = self.device
         sd = state_dict
         hs = sd["decoder.conv_out.conv.weight"].shape[1]
         if hidden_size is not None and hidden_size != hs:
             raise ValueError(f"hidden_size {hidden_size}, but decoder.conv_out.conv.weight has {hs} input channels")
-        missing = sorted(set(decoder_param_shapes(hs)) - set(sd))
+        missing = sorted(set(self._param_shapes(hs)) - set(sd))
         if missing:
             raise KeyError(f"CausalVAE decoder: the state dict lacks {missing[:4]}{' ...' if len(missing) > 4 else ''}")
         self.hidden_size = hs
         self.config = SimpleNamespace(hidden_size=hs, z_channels=Z_CHANNELS, hidden_size_mult=HIDDEN_SIZE_MULT)
         self.dtype = torch.bfloat16
         # CausalVAEModel.__init__ :798-806
-        self.tile_sample_min_size = 256
-        self.tile_sample_min_size_t = 33
+        self.tile_sample_min_size = self.TILE_DEFAULTS["tile_sample_min_size"]
+        self.tile_sample_min_size_t = self.TILE_DEFAULTS["tile_sample_min_size_t"]
         self.tile_latent_min_size = int(self.tile_sample_min_size / (2 ** (len(HIDDEN_SIZE_MULT) - 1)))
-        self.tile_latent_min_size_t = 16
-        self.tile_overlap_factor = 0.125
+        self.tile_latent_min_size_t = self.TILE_DEFAULTS["tile_latent_min_size_t"]
+        self.tile_overlap_factor = self.TILE_DEFAULTS["tile_overlap_factor"]
         self.use_tiling = False
         self.pq = (sd["post_quant_conv.conv.weight"].float().reshape(4, 4).cpu(), sd["post_quant_conv.conv.bias"].float().cpu())
         d = "decoder."
@@ -181,10 +190,18 @@ class CausalVAEDecoder(VaeBlocks):
             for j in range(3):
                 res.append(_CRes(sd, f"{d}up.{lvl}.block.{j}", dev, prev, co))
                 prev = co
-            up = _CConv(sd, f"{d}up.{lvl}.upsample.conv", dev, co, co) if SPATIAL_UPSAMPLE[lvl] else None
-            self.ups.append((res, up, SPATIAL_UPSAMPLE[lvl]))
+            up = _CConv(sd, f"{d}up.{lvl}.upsample.conv", dev, co, co) if self.SPATIAL[lvl] else None
+            self.ups.append((res, up, self.SPATIAL[lvl]))
+            self._level_extra(sd, lvl, co, dev)
         self.norm_out = _CNorm(sd, d + "norm_out", dev, prev)
         self.conv_out = _CConv(sd, d + "conv_out", dev, prev, None, n_pad=128)
+
+    def _level_extra(self, sd, lvl: int, cm: _ChanMap, dev) -> None:
+        """Weights a level holds beside its residual blocks and its spatial upsampler (none in v1.2)."""
+
+    def _after_level(self, x, g: VaeGrid, lvl: int):
+        """What a level runs after its spatial upsampler (nothing in v1.2)."""
+        return x, g
 
     # ------------------------------------------------------------------------------------------------ reference surface
     def enable_tiling(self, use_tiling: bool = True):
@@ -242,7 +259,7 @@ class CausalVAEDecoder(VaeBlocks):
         x, g = self._resblock(x, g, self.mid[0])
         x, g = self._attention(x, g, self.attn)
         x, g = self._resblock(x, g, self.mid[1])
-        for res, up, kind in self.ups:
+        for lvl, (res, up, kind) in zip((3, 2, 1, 0), self.ups):
             for r in res:
                 x, g = self._resblock(x, g, r)
             if kind == "SpatialUpsample2x":                                          # :334-341 (a (1, 3, 3) conv: no front frames)
@@ -256,6 +273,7 @@ class CausalVAEDecoder(VaeBlocks):
                 oops.upsample_trilinear2x(x, g, xu, gu, up.cin)
                 self._front(xu, gu)
                 x, g = self._conv(xu, gu, up), gu.conv_out()
+            x, g = self._after_level(x, g, lvl)
         hN, gN = self._norm_act(x, g, self.norm_out, self.norm_out.C, 2)
         y = self._conv(hN, gN, self.conv_out)
         out = torch.empty(3, g.T, g.H, g.W, dtype=torch.bfloat16, device=self.device)
@@ -403,9 +421,10 @@ class CausalVAEModelWrapper:
 
 
 # ---------------------------------------------------------------------------------------------------- synthetic weights
-def decoder_param_shapes(hidden_size: int = 128) -> Dict[str, tuple]:
+def decoder_param_shapes(hidden_size: int = 128, spatial=SPATIAL_UPSAMPLE, temporal=("",) * 4) -> Dict[str, tuple]:
     """Names and shapes of the decode-side parameters of the reference CausalVAEModel (checked against its own state_dict through
-    tests/golden/osp_vae_small.pt)."""
+    tests/golden/osp_vae_small.pt).  ``spatial`` / ``temporal``: the upsampler class per level (the v1.2 ones by default; the v1.1
+    decoder of vae_open_sora_plan_v110.py passes its own: a ``TimeUpsampleRes2x`` holds ``mix_factor`` and a causal 3 x 3 x 3 conv)."""
     p: Dict[str, tuple] = {}
     hs = hidden_size
 
@@ -432,8 +451,11 @@ def decoder_param_shapes(hidden_size: int = 128) -> Dict[str, tuple]:
         for j in range(3):
             res(f"{d}up.{lvl}.block.{j}", prev, co)
             prev = co
-        if SPATIAL_UPSAMPLE[lvl]:
-            cconv(f"{d}up.{lvl}.upsample.conv", co, co, (1, 3, 3) if SPATIAL_UPSAMPLE[lvl] == "SpatialUpsample2x" else 3)
+        if spatial[lvl]:
+            cconv(f"{d}up.{lvl}.upsample.conv", co, co, (1, 3, 3) if spatial[lvl] == "SpatialUpsample2x" else 3)
+        if temporal[lvl] == "TimeUpsampleRes2x":
+            p[f"{d}up.{lvl}.time_upsample.mix_factor"] = (1,)
+            cconv(f"{d}up.{lvl}.time_upsample.conv", co, co, 3)
     norm(p, d + "norm_out", prev)
     cconv(d + "conv_out", prev, 3, 3)
     cconv("post_quant_conv", Z_CHANNELS, Z_CHANNELS, 1)
