@@ -590,3 +590,69 @@ def splitk_linear_ref(x, w, nsplit, res=None):
         p = p + res.double()
         bound = bound + rnd(p)
     return p, bound
+
+
+# ------------------------------------------------------------------------------------------------ GEMM family: activations, linear_small
+# The activation epilogues of gemm_bf16.hip / gemm2_bf16.hip (EPI_BIAS_GELU) and linear_small_kernel.  An activation's output error is the
+# size of the IMAGE of the argument's error interval, not a global slope times its width: in the tails of gelu_tanh and SiLU the slope is
+# next to zero, and that is where the exp of the kernels' fast forms overflows (tests/gemm_numerics_cases.py).
+
+
+def silu64(x):
+    return x / (1.0 + torch.exp(-x))
+
+
+def _interior_minimum(fn, lo=-3.0, hi=0.0):
+    """The one interior minimum of gelu_tanh / SiLU (both fall from 0 to it and rise from it on) by ternary search in float64; the value
+    there is flat, so the few 1e-9 the argument is uncertain by move f(x*) by nothing a bound can see."""
+    for _ in range(200):
+        a, b = lo + (hi - lo) / 3, hi - (hi - lo) / 3
+        fa, fb = float(fn(torch.tensor(a, dtype=torch.float64))), float(fn(torch.tensor(b, dtype=torch.float64)))
+        lo, hi = (lo, b) if fa < fb else (a, hi)
+    return 0.5 * (lo + hi)
+
+
+GELU_XMIN = _interior_minimum(gelu_new64)    # -0.7525 (the erf form: -0.7518)
+SILU_XMIN = _interior_minimum(silu64)        # -1.2785
+ACTIVATIONS = {"none": (None, None), "silu": (silu64, SILU_XMIN), "gelu": (gelu_new64, GELU_XMIN)}
+
+
+def act_image(act: str, p: torch.Tensor, d: torch.Tensor):
+    """(f(p), max |f(y) - f(p)| over y in [p - d, p + d]) for f = ACTIVATIONS[act], float64.  f is monotone on either side of its one
+    minimum x*, so the image's ends are f(p - d), f(p + d) and, where the interval holds x*, f(x*).  "none": (p, d)."""
+    fn, xmin = ACTIVATIONS[act]
+    if fn is None:
+        return p, d
+    y = fn(p)
+    e = torch.maximum((fn(p - d) - y).abs(), (fn(p + d) - y).abs())
+    inside = (p - d <= xmin) & (xmin <= p + d)
+    fmin = fn(torch.tensor(xmin, dtype=torch.float64, device=p.device))
+    return y, torch.where(inside, torch.maximum(e, (fmin - y).abs()), e)
+
+
+def linear_small_ref(x, w, bias=None, act_in="none", act_out="none"):
+    """linear_small_kernel (gemm_bf16.hip): x [M, K], w [N, K], bias [N] (bf16 values), one wave per output element:
+      xe  = bf16(silu(x)) when act_in is SiLU (nn.SiLU on a bf16 tensor rounds before the Linear), else x: held by the near-tie rule (Tie)
+            with e = |silu(x)| (U_LIBM + U_RCP + 3 2^-24) (expf, the division, the negation / sum / quotient in fp32);
+      s   = sum_k xe_k w_k + bias in fp32 in any order:   e_p = tie.err @ |w|^T + acc(K + 1, sum |xe w| + |bias|);
+      out = bf16(act_out(s)), the activation in fp32:     bound = image of [p - e_p, p + e_p] under act_out (act_image) + rnd(out)
+            + (U_EXP + U_RCP + 8 2^-24) |out| where an activation runs (its fast exp, its reciprocal, the <= 8 fp32 operations around them).
+    Returns (ref, bound [M, N] float64, the Tie of xe or None)."""
+    K = x.shape[1]
+    xd, wd = x.double(), w.double()
+    tie = None
+    terr = torch.zeros_like(xd)
+    if act_in == "silu":
+        v = silu64(xd)
+        tie = Tie(v, v.abs() * (U_LIBM + U_RCP + 3 * U_F32))
+        xd, terr = tie.vb, tie.err
+    else:
+        assert act_in == "none"
+    bd = bias.double() if bias is not None else torch.zeros(w.shape[0], dtype=torch.float64, device=w.device)
+    p = xd @ wd.t() + bd
+    e_p = terr @ wd.abs().t() + acc(K + 1, xd.abs() @ wd.abs().t() + bd.abs())
+    out, e = act_image(act_out, p, e_p)
+    bound = e + rnd(out)
+    if act_out != "none":
+        bound = bound + (U_EXP + U_RCP + 8 * U_F32) * out.abs()
+    return out, bound, tie

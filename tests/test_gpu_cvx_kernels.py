@@ -1,5 +1,10 @@
 """GPU: the CogVideoX kernels (head_dim 64 attention, two-segment LayerNorm-modulate / gate epilogue, patch im2col,
-unpatchify) against plain torch fp32 on bf16-rounded inputs.  Tolerance: max|err| <= 2^-7 * max|ref| per op."""
+unpatchify) against plain torch fp32 on bf16-rounded inputs.  Tolerance: max|err| <= 2^-7 * max|ref| per op.
+
+The max-norm check of the two-segment gate epilogue here (test_gemm_gate2_and_gate_add_rows: one shape on the few-tile kernels) is a smoke
+test, not that epilogue's oracle: vsys_gemm_bf16_gate2 is held element by element against float64 — at segment and sample boundaries
+inside a wave, under every kernel id, and in the 256-row kernels a CogVideoX step runs — by tests/test_gpu_numerics_gemm.py
+(test_two_segment_gate_small, test_two_segment_gate_production_dispatch; cases in tests/gemm_numerics_cases.py)."""
 import math
 
 import pytest

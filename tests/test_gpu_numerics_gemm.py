@@ -15,6 +15,10 @@ Rounding chains (the reference = the model run in bf16; each rounding a worst ca
     rounds W (1 + scale) to bf16 where the model rounds the modulated activations, sums x Wp and x-independent sum_k Wp in fp32
     and combines rstd (acc - mu cs) + cv:  rstd (rnd(W (1+s)) . |x - mu| + acc(x Wp) + |mu| acc(Wp)) + acc(shift W + b)
     + stats (mu / rstd to 2^-20 relative) + rnd(out), then GELU as above.
+
+Second half: the GEMM work only Latte, CogVideoX, the two Open-Sora-Plans and Vchitect-2.0 do (tests/gemm_numerics_cases.py: the tables, the
+per-row two-segment gate, the GELU bound from the activation's image interval, linear_small).  Every one of those tests names the kernel
+its launch reaches (from the restated dispatch rule) and prints the worst |err| / bound.
 """
 import contextlib
 import math
@@ -22,6 +26,7 @@ import math
 import pytest
 import torch
 
+import gemm_numerics_cases as gc
 import numerics as nm
 
 pytestmark = pytest.mark.gpu
@@ -307,3 +312,176 @@ def test_dispatch_branches(ops, case, v):
     tag = f"{name} (M={M} N={N} K={K}, variant {v}: {dispatch_rule(M, N, K, 'bias', v, cu)} | {dispatch_rule(M, N, K, 'gate', v, cu)})"
     check_gemm(out, a, w, b, "store-only " + tag)
     check_gemm(x, a, w, b, "gate + residual " + tag, gate=gate, gate_stride=N, rps=rps, res=res)
+
+
+# ================================================================================================ the other models' sites
+# Tables, operands, references and bounds: tests/gemm_numerics_cases.py (meta-tests and planted defects: tests/test_numerics_cpu.py).
+def nan_out(M, N):
+    return torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=dev())
+
+
+def cus():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def reached(M, N, K, epi, v, want=None, aux=False):
+    """The kernel of this launch by the restated rule; under id 0 it must be the one the case's table promises."""
+    kern = gc.kernel_of(M, N, K, epi, v, cus(), aux)
+    if v == 0 and want is not None:
+        assert kern == gc.expected(want, cus()), f"the table promises {gc.expected(want, cus())}, the rule gives {kern}"
+    return f"id {v}: {kern}"
+
+
+def test_other_models_tables_match_rule():
+    gc.assert_tables_match_rule()
+
+
+@pytest.mark.parametrize("case", range(len(gc.GELU_SITES)), ids=[c[0].replace(" ", "_") for c in gc.GELU_SITES])
+def test_gelu_sites(ops, case):
+    """EPI_BIAS_GELU (fc1 of Latte, CogVideoX, both Open-Sora-Plans, Vchitect) in the production kernel of every (N, K), on both sides of
+    the K <= 1536 branch and on the few-tile kernels, with pre-activations beyond +-12 in every case."""
+    name, M, N, K, want = gc.GELU_SITES[case]
+    a, w, b = gc.gelu_operands(M, N, K, 400 + 3 * case, dev())
+    out = nan_out(M, N)
+    ops.gemm(a, w, b, epilogue=ops.EPI_BIAS_GELU, out=out)
+    gc.check_gemm(out, a, w, b, f"GELU {name} ({M} x {N} x {K}, {reached(M, N, K, 'gelu', 0, want)})", gelu=True, tails=True)
+
+
+_ID8 = {}
+
+
+def _id8(ops, i):
+    """Operands of ID_SHAPES[i] and the bits id 8 stores for them (GELU, store-only): computed once."""
+    if i not in _ID8:
+        M, N, K = gc.ID_SHAPES[i]
+        a, w, b = gc.gelu_operands(M, N, K, 440 + i, dev())
+        with variant(8):
+            _ID8[i] = (a, w, b, ops.gemm(a, w, b, epilogue=ops.EPI_BIAS_GELU, out=nan_out(M, N)), ops.gemm(a, w, b, out=nan_out(M, N)))
+    return _ID8[i]
+
+
+@pytest.mark.parametrize("v", gc.ACCEPTED_IDS)
+def test_every_accepted_id_gelu_and_store_only(ops, v):
+    """Every id vsys_tune_gemm_variant accepts: GELU and store-only element-wise, and the same bits as id 8 (include/videosys_amd.h)."""
+    for i, (M, N, K) in enumerate(gc.ID_SHAPES):
+        a, w, b, gelu8, store8 = _id8(ops, i)
+        with variant(v):
+            out_g = ops.gemm(a, w, b, epilogue=ops.EPI_BIAS_GELU, out=nan_out(M, N))
+            out_s = ops.gemm(a, w, b, out=nan_out(M, N))
+        gc.check_gemm(out_g, a, w, b, f"GELU {M} x {N} x {K}, {reached(M, N, K, 'gelu', v)}", gelu=True, tails=True)
+        gc.check_gemm(out_s, a, w, b, f"store-only {M} x {N} x {K}, {reached(M, N, K, 'bias', v)}")
+        assert torch.equal(out_g, gelu8), f"id {v}: GELU bits differ from id 8 at {M} x {N} x {K}"
+        assert torch.equal(out_s, store8), f"id {v}: store-only bits differ from id 8 at {M} x {N} x {K}"
+
+
+@pytest.mark.parametrize("case", range(len(gc.GATE2_SMALL)), ids=[f"M{c[0]}_rps{c[1]}_split{c[2]}" for c in gc.GATE2_SMALL])
+def test_two_segment_gate_small(ops, case):
+    """vsys_gemm_bf16_gate2 at segment / sample boundaries inside a 16-row block, on wave and tile edges, with many samples in a wave:
+    with and without bias, in place and with out / aux slab on leading dimensions of their own, under every id of GATE2_IDS (and the
+    same bits as id 8).  The modulation row is gate | junk | alternative gate (gate_alt = 2 N)."""
+    M, rps, split, what = gc.GATE2_SMALL[case]
+    N, K = gc.GATE2_N, gc.GATE2_K
+    a, w, b = gc.operands(M, N, K, 500 + 3 * case, dev())
+    mod = gc.randn((-(-M // rps), 3 * N), 530 + case, dev())
+    res = gc.randn((M, N), 540 + case, dev(), 1.0, 0.5)
+    gate = mod[0, :N]
+    for bias in (b, None):
+        for slab in (False, True):
+            bits8 = None
+            for v in (8,) + tuple(i for i in gc.GATE2_IDS if i != 8):
+                rv, rbuf = gc.padded(M, N, N + 8, dev(), res)
+                (ov, obuf), (av, abuf) = (gc.padded(M, N, N + 64, dev()), gc.padded(M, N, N + 136, dev())) if slab else ((rv, rbuf), (None, None))
+                with variant(v):
+                    ops.gemm_gate2(a, w, bias, gate, 3 * N, rps, split, 2 * N, rv, ov, aux=av)
+                tag = (f"gate2 M={M} rps={rps} split={split} bias={bias is not None} {'out + slab' if slab else 'in place'} "
+                       f"({what}; {reached(M, N, K, 'gate', v, aux=slab)})")
+                gc.check_gemm(ov, a, w, bias, tag, gate=gate, gate_stride=3 * N, rps=rps, seg_split=split, gate_alt=2 * N, res=res, aux=av)
+                assert torch.isnan(obuf[:, N:]).all() and (abuf is None or torch.isnan(abuf[:, N:]).all()), f"{tag}: padding columns written"
+                if v == 8:
+                    bits8 = (ov, av)
+                else:
+                    assert torch.equal(ov, bits8[0]) and (av is None or torch.equal(av, bits8[1])), f"{tag}: other bits than id 8"
+            if split in (0, rps):       # one segment only: ops.gemm with the gate pointer (moved on by gate_alt) stores the same bits
+                x = res.clone()
+                ops.gemm(a, w, bias, epilogue=ops.EPI_GATE_RES, gate=mod[0, 2 * N:] if split else gate, gate_stride=3 * N, rows_per_sample=rps,
+                         res=x, out=x)
+                assert torch.equal(x, bits8[0]), f"gate2 with seg_split = {split} differs from ops.gemm with the (moved) gate pointer"
+
+
+@pytest.mark.parametrize("v", [0, 8])
+@pytest.mark.parametrize("case", range(len(gc.GATE2_PROD)), ids=[c[0].replace(" ", "_") for c in gc.GATE2_PROD])
+def test_two_segment_gate_production_dispatch(ops, case, v):
+    """The two-segment gate in the kernels a CogVideoX step runs (>= 400 tiles of 256 rows: schedule 8) and on the long K loop of the 5b
+    fc2 on few tiles; in place, with the slab copy."""
+    name, M, N, K, rps, split, want = gc.GATE2_PROD[case]
+    a, w, b = gc.operands(M, N, K, 600 + 3 * case, dev())
+    mod = gc.randn((-(-M // rps), 3 * N), 630 + case, dev(), 0.7)
+    res = gc.randn((M, N), 640 + case, dev(), 1.0, 0.25)
+    x, aux = res.clone(), nan_out(M, N)
+    with variant(v):
+        ops.gemm_gate2(a, w, b, mod[0, :N], 3 * N, rps, split, 2 * N, x, x, aux=aux)
+    gc.check_gemm(x, a, w, b, f"gate2 {name} ({M} x {N} x {K}, rps {rps}, split {split}; {reached(M, N, K, 'gate', v, want, aux=True)})",
+                  gate=mod[0, :N], gate_stride=3 * N, rps=rps, seg_split=split, gate_alt=2 * N, res=res, aux=aux)
+
+
+@pytest.mark.parametrize("v", [0, 8])
+@pytest.mark.parametrize("rps", gc.SHORT_RPS)
+@pytest.mark.parametrize("M,N,K,want", gc.SHORT_SHAPES, ids=[f"{c[0]}x{c[1]}x{c[2]}" for c in gc.SHORT_SHAPES])
+def test_short_samples(ops, M, N, K, want, rps, v):
+    """ops.gemm(EPI_GATE_RES) with samples shorter than a wave's 64 rows (Vchitect gates per frame and per prompt), down to a gate row
+    per token; the last sample is short wherever rps does not divide M."""
+    a, w, b = gc.operands(M, N, K, 700 + rps, dev())
+    mod = gc.randn((-(-M // rps), N), 710 + rps, dev(), 0.7)
+    res = gc.randn((M, N), 720 + rps, dev(), 1.0, -0.25)
+    x = res.clone()
+    with variant(v):
+        ops.gemm(a, w, b, epilogue=ops.EPI_GATE_RES, gate=mod[0], gate_stride=N, rows_per_sample=rps, res=x, out=x)
+    gc.check_gemm(x, a, w, b, f"short samples {M} x {N} x {K} rps={rps} ({reached(M, N, K, 'gate', v, want)})", gate=mod[0], gate_stride=N, rps=rps,
+                  res=res)
+
+
+@pytest.mark.parametrize("v", [0, 8])
+@pytest.mark.parametrize("case", range(len(gc.REMAINING)), ids=[c[0].replace(" ", "_") for c in gc.REMAINING])
+def test_remaining_store_only_sites(ops, case, v):
+    """The N = 192 proj_out launches (long K loops on few tiles) and the widest store-only GEMM (Open-Sora-Plan's qkv)."""
+    name, M, N, K, want = gc.REMAINING[case]
+    a, w, b = gc.operands(M, N, K, 800 + 3 * case, dev())
+    out = nan_out(M, N)
+    with variant(v):
+        ops.gemm(a, w, b, out=out)
+    gc.check_gemm(out, a, w, b, f"store-only {name} ({M} x {N} x {K}, {reached(M, N, K, 'bias', v, want)})")
+
+
+# ------------------------------------------------------------------------------------------------ linear_small
+def _acts(ops):
+    return {"none": ops.ACT_NONE, "silu": ops.ACT_SILU, "gelu": ops.ACT_GELU_TANH}
+
+
+@pytest.mark.parametrize("name", list(gc.LS_CASES))
+def test_linear_small_elementwise(ops, name):
+    """linear_small_kernel (every model's timestep embedding, caption projection and modulation table) against
+    numerics.linear_small_ref; x, w and out on leading dimensions with slack, whose sentinel must keep its bits."""
+    c = gc.ls_case(name, dev())
+    assert c["tie"] is None or c["tie"].share() <= gc.TIE_CAP
+    out, buf = c["run"](ops.linear_small, _acts(ops))
+    rep = nm.Bound(f"linear_small {name} {gc.LS_CASES[name][:5]}").add(out, c["ref"], c["bound"])
+    print(rep.message())
+    rep.check()
+    assert gc.slack_untouched(buf, c["N"]), f"linear_small {name}: the columns behind N were written"
+    assert c["operands_intact"](), f"linear_small {name}: x or w (or the slack behind their rows) changed"
+
+
+def test_linear_small_out_column_slice_and_row_slice_of_x(ops):
+    """The ``out=`` form writing a column slice of a wider buffer, from the first rows of a taller x (norm_out's temb[:B])."""
+    name = "m3_n72_k4096_silu_in"
+    c = gc.ls_case(name, dev())
+    M, N, K = c["M"], c["N"], c["K"]
+    tall = torch.full((M + 4, K), 3.0, dtype=torch.bfloat16, device=dev())
+    tall[:M] = c["x"]
+    wide = torch.full((M, N + 100), gc.LS_SENTINEL, dtype=torch.bfloat16, device=dev())
+    wide[:, 40:40 + N] = float("nan")
+    ops.linear_small(tall[:M], c["w"], c["b"], act_in=ops.ACT_SILU, out=wide[:, 40:40 + N])
+    rep = nm.Bound(f"linear_small {name}, out = a column slice, x = a row slice").add(wide[:, 40:40 + N], c["ref"], c["bound"])
+    print(rep.message())
+    rep.check()
+    assert bool((wide[:, :40] == gc.LS_SENTINEL).all()) and bool((wide[:, 40 + N:] == gc.LS_SENTINEL).all())

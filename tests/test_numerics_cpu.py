@@ -2,12 +2,16 @@
 rounding fewer than the contract pass; each of four planted GEMM defects fails, and the failure names the tile.  Second half: the
 softmax-attention bound (numerics.attention_ref) against a CPU emulation of the d72 flash contract and its planted defects.  Third part:
 the VAE family's bounds (conv / gemm128, GroupNorm, SpatialNorm, softmax_rows, first layer) against the restatements of
-tests/vae_cpu_emul.py and their planted defects, and the refusal of ops.conv for temporal taps over more than one sample."""
+tests/vae_cpu_emul.py and their planted defects, and the refusal of ops.conv for temporal taps over more than one sample.  Fourth part:
+the GEMM family beyond STDiT3's launches (GELU store, the per-row two-segment gate, linear_small: tests/gemm_numerics_cases.py) against
+the restatements of tests/gemm_cpu_emul.py and their planted defects."""
 import pytest
 import torch
 import torch.nn.functional as F
 
 import attn_families as fam
+import gemm_cpu_emul as gemu
+import gemm_numerics_cases as gc
 import numerics as nm
 import vae_cpu_emul as emu
 import vae_numerics_cases as vc
@@ -426,3 +430,168 @@ def test_conv_refuses_temporal_taps_on_more_than_one_sample():
         ops.conv(torch.zeros(g1.rows, 32, dtype=torch.bfloat16), g1, w[:, :288], None, 32, 1, 3)
     with pytest.raises(ops._lib.VsysError, match="no CPU fallback"):          # what is allowed reaches the device check (still no launch)
         ops.conv(torch.zeros(ops.VaeGrid(2, 1, 4, 4, 1, 0).rows, 32, dtype=torch.bfloat16), ops.VaeGrid(2, 1, 4, 4, 1, 0), w[:, :288], None, 32, 1, 3)
+
+
+# ------------------------------------------------------------------------------------------------ GEMM family: the other models' sites
+# The tables of tests/gemm_numerics_cases.py at scaled-down rows (CPU operands, the same generators): the restatements of
+# tests/gemm_cpu_emul.py pass every bound, every planted defect fails.
+def _bad(reps):
+    return sum(r.bad for r in reps)
+
+
+def test_gemm_tables_match_the_dispatch_rule():
+    gc.assert_tables_match_rule()
+    import test_gpu_numerics_gemm as tg      # the rule of the existing file and its restatement here agree on ids 0 and 8
+
+    for cu in (80, 256, 304):
+        for M, N, K, epi, _ in gc.table_rows():
+            if epi != "gelu":
+                assert tg.dispatch_rule(M, N, K, epi, 0, cu) == gc.dispatch_rule(M, N, K, epi, cu)
+    assert gc.kernel_of(1, 192, 64, "gate", 8, 256) == "sched8 mf32" and tg.dispatch_rule(1, 192, 64, "gate", 8, 256) == "sched8"
+
+
+def test_row_gates_without_a_segment_is_gate_rows_and_with_one_follows_the_definition():
+    import test_gpu_numerics_gemm as tg
+
+    N = 24
+    for M, rps in ((130, 7), (257, 257), (300, 100), (64, 1)):
+        ns = -(-M // rps)
+        mod = gc.randn((ns, 3 * N + 8), M + rps, "cpu")
+        for r0, r1 in ((0, M), (M // 3, M - 1)):
+            assert torch.equal(gc.row_gates(mod[0, N:], mod.stride(0), rps, 0, 0, r0, r1, N),
+                               tg.gate_rows(mod[0, N:], mod.stride(0), rps, r0, r1, N))
+        for split in (1, rps // 2, rps):
+            if split == 0:
+                continue
+            got = gc.row_gates(mod[0, :N], mod.stride(0), rps, split, 2 * N, 0, M, N)
+            for r in range(M):                 # the definition, row by row
+                b = r // rps
+                want = mod[b, 2 * N:3 * N] if r - b * rps < split else mod[b, :N]
+                assert torch.equal(got[r], want.double()), (M, rps, split, r)
+
+
+GELU_CPU = [(260, 384, 1152), (260, 384, 1536), (260, 384, 1600), (132, 384, 3072), (131, 192, 64)]
+
+
+@pytest.mark.parametrize("M,N,K", GELU_CPU)
+def test_gelu_restatement_passes_and_planted_defects_fail(M, N, K):
+    a, w, b = gc.gelu_operands(M, N, K, 7 * K + M, "cpu")
+    gc.check_gemm(gemu.gelu_store(a, w, b), a, w, b, f"GELU restatement {M} x {N} x {K}", gelu=True, tails=True)
+    gc.check_gemm(gemu.gelu_store(a, w, None), a, w, None, f"GELU restatement {M} x {N} x {K}, no bias", gelu=True, tails=True)
+    for defect in ("bias_after", "abs"):
+        assert _bad(gc.gemm_bounds(gemu.gelu_store(a, w, b, defect), a, w, b, defect, gelu=True)) > 0, f"{defect} passes"
+    # a non-finite or a non-zero tail fails: the overflow branch's result replaced by what a global-slope bound would let through
+    out = gemu.gelu_store(a, w, b)
+    p = a.double() @ w.double().t() + b.double()
+    r, c = divmod(int(p.argmin()), N)
+    assert float(p[r, c]) <= -gc.TAIL and float(out[r, c]) == 0.0
+    for wrong in (float("nan"), -2.0**-8):
+        bad = out.clone()
+        bad[r, c] = wrong
+        assert _bad(gc.gemm_bounds(bad, a, w, b, "tail", gelu=True)) == 1
+
+
+def test_erf_gelu_share_outside_the_tanh_bound():
+    """A limit, reported and not asserted to be large: over most of the range a worst-case bound on a bf16 output cannot tell erf GELU from
+    tanh GELU (they differ by at most 4.7e-4).  The share of a GELU case's elements on which the swap is outside the bound is printed for
+    the ledger; it only has to be a share (some elements do tell them apart, most do not)."""
+    M, N, K = 260, 384, 1152
+    a, w, b = gc.gelu_operands(M, N, K, 7 * K + M, "cpu")
+    p = a.float() @ w.float().t() + b.float()
+    out = torch.nn.functional.gelu(p).to(torch.bfloat16)
+    rep = gc.gemm_bounds(out, a, w, b, "erf GELU under the tanh bound", gelu=True)[0]
+    share = rep.bad / rep.total
+    print(f"erf GELU for tanh GELU at {M} x {N} x {K}: {rep.bad} of {rep.total} elements ({100 * share:.2f} %) outside the bound")
+    assert 0.0 < share < 0.5
+
+
+def _gate2_cpu(M, rps, split, bias=True):
+    N, K = gc.GATE2_N, gc.GATE2_K
+    a, w, b = gc.operands(M, N, K, 11 * M + rps + split, "cpu")
+    mod = gc.randn((-(-M // rps), 3 * N), 13 * M + rps, "cpu")       # gate | junk | alternative gate
+    res = gc.randn((M, N), 17 * M + split, "cpu", 1.0, 0.5)
+    return a, w, (b if bias else None), mod, res
+
+
+@pytest.mark.parametrize("M,rps,split,what", gc.GATE2_SMALL, ids=[f"M{c[0]}_rps{c[1]}_split{c[2]}" for c in gc.GATE2_SMALL])
+def test_two_segment_gate_restatement_passes(M, rps, split, what):
+    N = gc.GATE2_N
+    for bias in (True, False):
+        a, w, b, mod, res = _gate2_cpu(M, rps, split, bias)
+        out, aux = gemu.gate_res(a, w, b, mod[0, :N], 3 * N, rps, split, 2 * N, res)
+        gc.check_gemm(out, a, w, b, f"gate2 restatement M={M} rps={rps} split={split} bias={bias} ({what})", gate=mod[0, :N], gate_stride=3 * N,
+                      rps=rps, seg_split=split, gate_alt=2 * N, res=res, aux=aux)
+
+
+# which rows of GATE2_SMALL must catch which defect (module docstring of gemm_cpu_emul.py); the others hold no row the defect moves
+GATE2_CAUGHT = {
+    "le": (0, 1, 2, 3),
+    "wave_first_row": (0, 2, 3),          # (row 1 has every boundary on a wave edge: the one-row form is right there)
+    "alt_on_video": (0, 1, 2, 3, 5),
+    "tile_sample": (0, 2, 3),             # (row 1: the sample boundaries lie on tile edges)
+}
+
+
+@pytest.mark.parametrize("defect", sorted(GATE2_CAUGHT))
+def test_two_segment_gate_planted_defect_fails(defect):
+    N = gc.GATE2_N
+    for i, (M, rps, split, what) in enumerate(gc.GATE2_SMALL):
+        a, w, b, mod, res = _gate2_cpu(M, rps, split)
+        out, aux = gemu.gate_res(a, w, b, mod[0, :N], 3 * N, rps, split, 2 * N, res, defect=defect)
+        reps = gc.gemm_bounds(out, a, w, b, defect, gate=mod[0, :N], gate_stride=3 * N, rps=rps, seg_split=split, gate_alt=2 * N, res=res, aux=aux)
+        if i in GATE2_CAUGHT[defect]:
+            assert reps[0].bad > 0 and reps[1].bad > 0, f"{defect} passes on M={M} rps={rps} split={split}"
+        else:
+            assert _bad(reps) == 0, f"{defect} should not move a row of M={M} rps={rps} split={split}"
+
+
+LS_ACTS = {"none": "none", "silu": "silu", "gelu": "gelu"}
+
+
+@pytest.mark.parametrize("name", list(gc.LS_CASES))
+def test_linear_small_restatement_passes_and_tie_share_is_capped(name):
+    full = gc.ls_case(name)
+    if full["tie"] is not None:
+        share = full["tie"].share()
+        print(f"linear_small {name}: near-tie share {100 * share:.2f} %")
+        assert share <= gc.TIE_CAP
+        if full["M"] * full["K"] <= 64:
+            assert share == 0.0
+    c = gc.ls_case(name, max_rows=5, max_cols=72)
+    out, buf = c["run"](gemu.linear_small, LS_ACTS)
+    rep = nm.Bound(f"linear_small restatement {name}").add(out, c["ref"], c["bound"])
+    print(rep.message())
+    rep.check()
+    assert gc.slack_untouched(buf, c["N"]) and c["operands_intact"]()
+
+
+def test_linear_small_planted_defects():
+    def bad(name, defect):
+        c = gc.ls_case(name, max_rows=5, max_cols=72)
+        out = gemu.linear_small(c["x"], c["w"], c["b"], c["act_in"], c["act_out"], defect=defect)
+        return nm.Bound(defect).add(out, c["ref"], c["bound"]).bad
+
+    # One rounding fewer (the SiLU left in fp32) on the flagged-free cases.  It passes on the one-row case.  It does NOT pass in general,
+    # and is not meant to: the near-tie rule holds an unflagged xe to EXACTLY bf16(silu(x)) (Tie.err = 0), so at K = 8 the unrounded
+    # form's sum_k (silu(x_k) - xe_k) w_k (up to 2^-9 |silu(x_k) w_k| a term) can exceed acc(9, .) + rnd(out) where the sum cancels:
+    # 4 of the 15 elements of m3_n5_k8_silu_in.  The count is printed, the rule is not widened for it.
+    assert gc.ls_case("m1_n3_k8_silu_in")["tie"].share() == 0.0 and bad("m1_n3_k8_silu_in", "silu_unrounded") == 0
+    assert gc.ls_case("m3_n5_k8_silu_in")["tie"].share() == 0.0
+    print(f"SiLU left unrounded on m3_n5_k8_silu_in: {bad('m3_n5_k8_silu_in', 'silu_unrounded')} of 15 elements outside the bound")
+    for name in ("m3_n5_k8_silu_in", "m2_n5_k512_silu_in", "m3_n72_k4096_silu_in", "modulation_table"):
+        assert bad(name, "silu_after") > 0, f"SiLU after the product passes on {name}"
+    for name in ("m2_n5_k520", "m3_n5_k520_silu_in", "m2_n1152_k520_gelu"):
+        assert bad(name, "lane_stride_64") > 0, f"lane stride 64 passes on {name}"
+
+
+def test_activation_image_is_tight_in_the_tails_and_holds_the_minimum():
+    for act, xmin in (("gelu", -0.7525), ("silu", -1.2785)):     # (tanh GELU; the erf form has its minimum at -0.7518)
+        assert abs(nm.ACTIVATIONS[act][1] - xmin) < 1e-4
+        fn = nm.ACTIVATIONS[act][0]
+        p = torch.tensor([-40.0, -16.0, -12.0, xmin + 0.01, 0.0, 3.0, 16.0], dtype=torch.float64)
+        d = torch.tensor([0.2, 0.0625, 0.05, 0.02, 0.01, 0.01, 0.0625], dtype=torch.float64)
+        y, e = nm.act_image(act, p, d)
+        grid = p[:, None] + d[:, None] * torch.linspace(-1, 1, 2001, dtype=torch.float64)[None]
+        brute = (fn(grid) - y[:, None]).abs().amax(dim=1)
+        assert bool((e >= brute - 1e-15).all()) and bool((e <= brute + 1e-9).all())
+        assert float(e[0]) < 1e-12 and (act == "silu" or float(e[2]) < 2.0**-24)     # a global slope would give ~ d there
