@@ -11,6 +11,10 @@ reference code) on CPU; only the leaves below are restated from the published di
   diffusers.models.embeddings.PatchEmbed, get_2d_sincos_pos_embed, get_1d_sincos_pos_embed_from_grid,
       Timesteps / get_timestep_embedding, TimestepEmbedding, PixArtAlphaCombinedTimestepSizeEmbeddings,
       PixArtAlphaTextProjection
+  diffusers.models.embeddings.CombinedTimestepTextProjEmbeddings, PatchEmbed with pos_embed_max_size (cropped_pos_embed),
+      diffusers.models.normalization.AdaLayerNormZero / AdaLayerNormContinuous, diffusers.loaders.PeftAdapterMixin /
+      FromOriginalModelMixin (empty), transformer_2d.Transformer2DModelOutput, diffusers.utils.unscale_lora_layers (a no-op):
+      what the reference's Vchitect-2.0 transformer imports (tools/mint_vchitect.py)
   diffusers.models.lora.LoRACompatibleLinear / LoRACompatibleConv (plain Linear / Conv2d taking an ignored ``scale``)
   diffusers.configuration_utils.ConfigMixin / register_to_config, diffusers.models.modeling_utils.ModelMixin
   diffusers.schedulers.DDIMScheduler (set_timesteps "leading", step with eta = 0, epsilon prediction)
@@ -204,7 +208,9 @@ def get_2d_sincos_pos_embed(embed_dim, grid_size, cls_token=False, extra_tokens=
 
 
 class PatchEmbed(nn.Module):
-    """diffusers.models.embeddings.PatchEmbed (pos_embed_type="sincos", no layer norm, flatten)."""
+    """diffusers.models.embeddings.PatchEmbed (pos_embed_type="sincos", no layer norm, flatten).  With ``pos_embed_max_size`` (the
+    SD3 form Vchitect-2.0 uses) the table has max x max entries at base_size = height // patch, is a PERSISTENT buffer (it is in the
+    checkpoint), and forward adds its centre crop (cropped_pos_embed); without it the class is what Latte and CogVideoX construct."""
 
     def __init__(self, height=224, width=224, patch_size=16, in_channels=3, embed_dim=768, layer_norm=False, flatten=True,
                  bias=True, interpolation_scale=1, pos_embed_type="sincos", pos_embed_max_size=None):
@@ -212,14 +218,30 @@ class PatchEmbed(nn.Module):
         num_patches = (height // patch_size) * (width // patch_size)
         self.proj = nn.Conv2d(in_channels, embed_dim, kernel_size=(patch_size, patch_size), stride=patch_size, bias=bias)
         self.patch_size = patch_size
+        self.pos_embed_max_size = pos_embed_max_size
         self.height, self.width = height // patch_size, width // patch_size
         self.base_size = height // patch_size
         self.interpolation_scale = interpolation_scale
-        pos = get_2d_sincos_pos_embed(embed_dim, int(num_patches**0.5), base_size=self.base_size,
+        grid_size = pos_embed_max_size if pos_embed_max_size else int(num_patches**0.5)
+        pos = get_2d_sincos_pos_embed(embed_dim, grid_size, base_size=self.base_size,
                                       interpolation_scale=self.interpolation_scale)
-        self.register_buffer("pos_embed", torch.from_numpy(pos).float().unsqueeze(0), persistent=False)
+        self.register_buffer("pos_embed", torch.from_numpy(pos).float().unsqueeze(0), persistent=bool(pos_embed_max_size))
+
+    def cropped_pos_embed(self, height, width):
+        """The centre (height // patch) x (width // patch) window of the max x max table, [1, h * w, C]."""
+        m = self.pos_embed_max_size
+        height, width = height // self.patch_size, width // self.patch_size
+        if height > m or width > m:
+            raise ValueError(f"a {height} x {width} token grid does not fit pos_embed_max_size {m}")
+        top, left = (m - height) // 2, (m - width) // 2
+        pos = self.pos_embed.reshape(1, m, m, -1)[:, top:top + height, left:left + width, :]
+        return pos.reshape(1, -1, pos.shape[-1])
 
     def forward(self, latent):
+        if self.pos_embed_max_size is not None:
+            pos = self.cropped_pos_embed(*latent.shape[-2:])
+            latent = self.proj(latent).flatten(2).transpose(1, 2)
+            return (latent + pos).to(latent.dtype)
         height, width = latent.shape[-2] // self.patch_size, latent.shape[-1] // self.patch_size
         latent = self.proj(latent).flatten(2).transpose(1, 2)
         if self.height != height or self.width != width:
@@ -282,11 +304,62 @@ class PixArtAlphaTextProjection(nn.Module):
         super().__init__()
         out_features = out_features or hidden_size
         self.linear_1 = nn.Linear(in_features, hidden_size, bias=True)
-        self.act_1 = nn.GELU(approximate="tanh")
+        self.act_1 = {"gelu_tanh": lambda: nn.GELU(approximate="tanh"), "silu": nn.SiLU}[act_fn]()
         self.linear_2 = nn.Linear(hidden_size, out_features, bias=True)
 
     def forward(self, caption):
         return self.linear_2(self.act_1(self.linear_1(caption)))
+
+
+class CombinedTimestepTextProjEmbeddings(nn.Module):
+    """diffusers.models.embeddings.CombinedTimestepTextProjEmbeddings (the SD3 conditioning): timestep embedding + projected pooled text."""
+
+    def __init__(self, embedding_dim, pooled_projection_dim):
+        super().__init__()
+        self.time_proj = Timesteps(num_channels=256, flip_sin_to_cos=True, downscale_freq_shift=0)
+        self.timestep_embedder = TimestepEmbedding(in_channels=256, time_embed_dim=embedding_dim)
+        self.text_embedder = PixArtAlphaTextProjection(pooled_projection_dim, embedding_dim, act_fn="silu")
+
+    def forward(self, timestep, pooled_projection):
+        proj = self.time_proj(timestep)
+        return self.timestep_embedder(proj.to(dtype=pooled_projection.dtype)) + self.text_embedder(pooled_projection)
+
+
+class AdaLayerNormZero(nn.Module):
+    """diffusers.models.normalization.AdaLayerNormZero called with a ready ``emb`` (no label embedding): linear(silu(emb)) -> six
+    chunks shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp; LayerNorm without affine, eps 1e-6."""
+
+    def __init__(self, embedding_dim, num_embeddings=None):
+        super().__init__()
+        assert num_embeddings is None
+        self.emb = None
+        self.silu = nn.SiLU()
+        self.linear = nn.Linear(embedding_dim, 6 * embedding_dim, bias=True)
+        self.norm = nn.LayerNorm(embedding_dim, elementwise_affine=False, eps=1e-6)
+
+    def forward(self, x, timestep=None, class_labels=None, hidden_dtype=None, emb=None):
+        emb = self.linear(self.silu(emb))
+        shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp = emb.chunk(6, dim=1)
+        x = self.norm(x) * (1 + scale_msa[:, None]) + shift_msa[:, None]
+        return x, gate_msa, shift_mlp, scale_mlp, gate_mlp
+
+
+class AdaLayerNormContinuous(nn.Module):
+    """diffusers.models.normalization.AdaLayerNormContinuous (norm_type "layer_norm"): scale, shift = chunk(linear(silu(c)), 2) —
+    SCALE first — and norm(x) * (1 + scale)[:, None] + shift[:, None]."""
+
+    def __init__(self, embedding_dim, conditioning_embedding_dim, elementwise_affine=True, eps=1e-5, bias=True,
+                 norm_type="layer_norm"):
+        super().__init__()
+        assert norm_type == "layer_norm"
+        self.silu = nn.SiLU()
+        self.linear = nn.Linear(conditioning_embedding_dim, embedding_dim * 2, bias=bias)
+        self.norm = nn.LayerNorm(embedding_dim, eps, elementwise_affine, bias)
+
+    def forward(self, x, conditioning_embedding):
+        emb = self.linear(self.silu(conditioning_embedding).to(x.dtype))
+        scale, shift = torch.chunk(emb, 2, dim=1)
+        return self.norm(x) * (1 + scale)[:, None, :] + shift[:, None, :]
 
 
 class FeedForward(nn.Module):
@@ -642,19 +715,27 @@ def install():
     _mod("diffusers.models.embeddings", ImagePositionalEmbeddings=_Unused, PatchEmbed=PatchEmbed,
          PixArtAlphaCombinedTimestepSizeEmbeddings=PixArtAlphaCombinedTimestepSizeEmbeddings,
          PixArtAlphaTextProjection=PixArtAlphaTextProjection, SinusoidalPositionalEmbedding=_Unused,
+         CombinedTimestepTextProjEmbeddings=CombinedTimestepTextProjEmbeddings,
          get_1d_sincos_pos_embed_from_grid=get_1d_sincos_pos_embed_from_grid, Timesteps=Timesteps,
          TimestepEmbedding=TimestepEmbedding, get_2d_sincos_pos_embed=get_2d_sincos_pos_embed,
          get_3d_sincos_pos_embed=get_3d_sincos_pos_embed)
     _mod("diffusers.models.lora", LoRACompatibleConv=LoRACompatibleConv, LoRACompatibleLinear=LoRACompatibleLinear)
     _mod("diffusers.models.modeling_utils", ModelMixin=ModelMixin)
-    _mod("diffusers.models.normalization", AdaLayerNorm=_Unused, AdaLayerNormContinuous=_Unused, AdaLayerNormZero=_Unused)
+    _mod("diffusers.models.normalization", AdaLayerNorm=_Unused, AdaLayerNormContinuous=AdaLayerNormContinuous,
+         AdaLayerNormZero=AdaLayerNormZero)
     _mod("diffusers.utils", USE_PEFT_BACKEND=False, BaseOutput=BaseOutput, deprecate=deprecate,
-         is_torch_version=lambda *a, **k: True)
+         is_torch_version=lambda *a, **k: True, unscale_lora_layers=lambda model, weight=None: None)
     _mod("diffusers.utils.torch_utils", maybe_allow_in_graph=maybe_allow_in_graph, randn_tensor=randn_tensor)
     # what videosys/models/autoencoders/autoencoder_kl_cogvideox.py imports (:18-24): no arithmetic except get_activation
     loaders = sys.modules.get("diffusers.loaders") or _mod("diffusers.loaders")
     loaders.__dict__.setdefault("__path__", [])
     _mod("diffusers.loaders.single_file_model", FromOriginalModelMixin=type("FromOriginalModelMixin", (), {}))
+    # what videosys/models/transformers/vchitect_transformer_3d.py imports (:16-24) beyond the leaves above: mixins without arithmetic
+    loaders.__dict__.update(FromOriginalModelMixin=sys.modules["diffusers.loaders.single_file_model"].FromOriginalModelMixin,
+                            PeftAdapterMixin=type("PeftAdapterMixin", (), {}))
+    tr = sys.modules.get("diffusers.models.transformers") or _mod("diffusers.models.transformers")
+    tr.__dict__.setdefault("__path__", [])
+    _mod("diffusers.models.transformers.transformer_2d", Transformer2DModelOutput=BaseOutput)
     sys.modules["diffusers.models.activations"].__dict__["get_activation"] = get_activation
     ae = sys.modules.get("diffusers.models.autoencoders") or _mod("diffusers.models.autoencoders")
     ae.__dict__.setdefault("__path__", [])

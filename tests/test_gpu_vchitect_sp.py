@@ -13,7 +13,8 @@ are those of the model with every `*temp*` weight zeroed, as at (2, 2).  At dept
 single-process run and the others must differ (cross keys = row 0 of the local shard).
 
 Within the floor.  Depth 2, per-frame text, against tests/vchitect_sp_ref.py in float64; bound: RMS error <= 1.5 x the RMS distance
-of the same restatement run in bf16 on the CPU from its float64 self."""
+of the same restatement run in bf16 on the CPU from its float64 self.  One comparison is with the reference's own class run with
+sp_size = 2 over gloo (tests/golden/vchitect_sp_small.pt), at 1.5 x that run's bf16 floor."""
 import os
 import threading
 
@@ -206,6 +207,41 @@ def test_depth_two_per_frame_text_within_the_bf16_floor(P):
     for r, outs in enumerate(results):
         assert all(torch.equal(o, results[0][0]) for o in outs), f"rank {r}: the routes / ranks do not agree bit for bit"
     within_floor(results[0][0], want, floor, f"sharded model F={F} P={P} depth 2")
+
+
+def test_sharded_model_against_the_two_process_reference():
+    """The one comparison with the reference's OWN class: tests/golden/vchitect_sp_small.pt holds its run with sp_size = 2 over gloo
+    (tools/mint_vchitect.py: F = 3, temporal pad 1; 16 x 16 latent and L = 7, S + L = 71, spatial pad 1; one text row, as the pipeline
+    calls the model).  Bound: 1.5 x rms(class bf16 - class float64), both sharded runs of the class."""
+    from tools.local_group import LocalWorld
+    from videosys_amd import pab
+    from videosys_amd.vchitect import VchitectXLTransformerModel, synth_state_dict
+
+    pab.set_pab_manager(None)
+    fx = torch.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "vchitect_sp_small.pt"), weights_only=True)
+    meta = fx["meta"]
+    kw, P = meta["kwargs"], meta["P"]
+    sd = {k: v.to(torch.bfloat16).float() for k, v in synth_state_dict(kw["num_layers"], kw["num_attention_heads"],
+          joint_attention_dim=kw["joint_attention_dim"], pooled_projection_dim=kw["pooled_projection_dim"], seed=meta["seed"]).items()}
+    x, enc, pooled = fx["x"].float(), fx["encoder_hidden_states"].float(), fx["pooled"].float()
+    ts = torch.tensor([float(fx["t"])])
+
+    def rank_fn(r, group):
+        torch.cuda.set_device(0)
+        m = VchitectXLTransformerModel(**kw, device=dev()).load_state_dict(sd)
+        outs = []
+        for p2p, route in ROUTES:
+            buf = torch.full((fx["ref_f64"].numel(),), float("nan"), dtype=torch.float32, device=dev())
+            outs.append(shard(m, group, P, r, p2p, route)(x, enc, pooled, ts, out=buf).sample.clone())
+        torch.cuda.synchronize()
+        return outs
+
+    results = LocalWorld(P, timeout=120).run(rank_fn)
+    for r, outs in enumerate(results):
+        assert all(torch.equal(o, results[0][0]) for o in outs), f"rank {r}: the routes / ranks do not agree bit for bit"
+    floor = rms(fx["ref_bf16"], fx["ref_f64"])
+    assert floor == pytest.approx(meta["floor_bf16"], rel=1e-9)
+    within_floor(results[0][0], fx["ref_f64"], floor, f"sharded model against the reference class, F={meta['F']} P={P}")
 
 
 def test_one_frame_per_rank_adds_no_temporal_contribution():

@@ -1,8 +1,12 @@
 """float64 restatement of VchitectAttnProcessor (reference videosys/models/modules/attentions.py:641-949) in plain torch on the CPU —
 TEST INFRASTRUCTURE for tests/test_gpu_vchitect_attention.py, imported the way tests/numerics.py is.  It follows the reference line
 by line from the PROJECTED tensors on (the q / k / v the Linear layers produced; the projections themselves are the GEMM family's
-tests), on bf16-exact inputs widened to float64.  UNPINNED: no fixture of the reference class backs it (the class pulls in diffusers'
-mixins), so it is held against the reference by reading only, as the SVD decoder's restatement is.
+tests), on bf16-exact inputs widened to float64.  PINNED: tests/test_vchitect_pinned_cpu.py holds attention_layer, block_forward and
+model_forward — in the pipeline's call form (B = 1, one text row), at one frame, on a rectangular latent, at B = 2 with one frame, and
+over eight calls under PAB (PabState) — to float64 runs of the reference's own JointTransformerBlock and VchitectXLTransformerModel
+(tests/golden/vchitect_{fwd,pab,layer}_small.pt, tools/mint_vchitect.py), within the class's own fp32-to-float64 distance.  What
+stays a reading of the class: B > 1 with more than one frame, which the class cannot execute (its norm_out does not broadcast);
+model_forward's norm_out at that shape is this project's extension.
 
 Shapes.  B samples, T frames, S video tokens and L text tokens per frame, H heads of 64.  Video tensors [B*T, S, H*64] and text
 tensors [B*T, L, H*64], rows ordered (b, t) as the reference's `(B T)` batch."""
@@ -100,11 +104,24 @@ def combine_bf16(spatial, cross):
     return spatial.to(torch.bfloat16) * 1.1 + cross.to(torch.bfloat16)
 
 
-def attention_layer(sd, hidden_states, encoder_hidden_states, B, T, H, context_pre_only=False, dtype=torch.float64):
-    """VchitectAttnProcessor.__call__ (:802-926) without PAB, on weights ``sd`` (VchitectAttention's names) and inputs [B*T, S, C] /
+class PabState:
+    """What VchitectAttention keeps between calls under PAB (attentions.py:528-534), one entry per block: the three counters and
+    last_temporal = (video AFTER to_out_temporal, text raw), last_cross (after to_out_context), last_spatial (before `* 1.1`)."""
+
+    def __init__(self, depth):
+        from types import SimpleNamespace
+
+        self.blocks = [SimpleNamespace(temporal_count=0, cross_count=0, spatial_count=0, last_temporal=None, last_cross=None, last_spatial=None,
+                                       last_decisions=None) for _ in range(depth)]
+
+
+def attention_layer(sd, hidden_states, encoder_hidden_states, B, T, H, context_pre_only=False, dtype=torch.float64, state=None, timestep=None):
+    """VchitectAttnProcessor.__call__ (:802-926) on weights ``sd`` (VchitectAttention's names) and inputs [B*T, S, C] /
     [B*T, L, C], all computed in ``dtype``: float64 = the reference for the numerics; bfloat16 = the reference's own bf16 run on the
     CPU (nn.Linear, F.scaled_dot_product_attention and the fp32 rotation cast back, as there): its distance to the float64 run is the
-    bf16 floor the HIP layer is held to.  Returns (hidden_states [B*T, S, C], encoder_hidden_states [B*T, L, C])."""
+    bf16 floor the HIP layer is held to.  Returns (hidden_states [B*T, S, C], encoder_hidden_states [B*T, L, C]).
+    ``state`` (one entry of PabState.blocks) with ``timestep`` (`int(timestep[0])`): PAB as :839-896 — a branch whose decision
+    (videosys_amd.pab, the manager set by the caller) is to broadcast takes the cached tensor, one that computes caches its result."""
     import torch.nn.functional as F
 
     lin = lambda x, n: F.linear(x, sd[n + ".weight"].to(dtype), sd[n + ".bias"].to(dtype))
@@ -113,23 +130,48 @@ def attention_layer(sd, hidden_states, encoder_hidden_states, B, T, H, context_p
     heads = lambda x: x.reshape(x.shape[0], -1, H, HD).transpose(1, 2)
     att = lambda q, k, v: F.scaled_dot_product_attention(q, k, v)
     eq, ek, ev = lin(enc, "add_q_proj"), lin(enc, "add_k_proj"), lin(enc, "add_v_proj")
+    SL = S + enc.shape[1]
+    bt = bc = bs = False
+    if state is not None:
+        from videosys_amd import pab
+
+        bt, state.temporal_count = pab.if_broadcast_temporal(timestep, state.temporal_count)
     # temporal (:705-764)
-    q, k, v = (temporal_tokens(lin(hs, n), e, B, T, H) for n, e in (("to_q_temp", eq), ("to_k_temp", ek), ("to_v_temp", ev)))
-    cos, sin = rope_tables(T)
-    rot = lambda x: apply_rotary(x.float() if dtype != torch.float64 else x, cos, sin).to(dtype)       # xq.float() ... type_as(xq)
-    o = att(rot(q).transpose(1, 2), rot(k).transpose(1, 2), v.transpose(1, 2)).transpose(1, 2)
-    SL = o.shape[0] // B
-    o = o.reshape(B, SL, T, H * HD).permute(0, 2, 1, 3).reshape(B * T, SL, H * HD)
-    temp_v, temp_t = lin(o[:, :S], "to_out_temporal"), o[:, S:]
+    if bt:
+        temp_v, temp_t = state.last_temporal
+    else:
+        q, k, v = (temporal_tokens(lin(hs, n), e, B, T, H) for n, e in (("to_q_temp", eq), ("to_k_temp", ek), ("to_v_temp", ev)))
+        cos, sin = rope_tables(T)
+        rot = lambda x: apply_rotary(x.float() if dtype != torch.float64 else x, cos, sin).to(dtype)       # xq.float() ... type_as(xq)
+        o = att(rot(q).transpose(1, 2), rot(k).transpose(1, 2), v.transpose(1, 2)).transpose(1, 2)
+        o = o.reshape(B, SL, T, H * HD).permute(0, 2, 1, 3).reshape(B * T, SL, H * HD)
+        temp_v, temp_t = lin(o[:, :S], "to_out_temporal"), o[:, S:]
+        if state is not None:
+            state.last_temporal = (temp_v, temp_t)
     # cross (:766-800)
-    qc = torch.cat([lin(hs, "to_q_cross"), eq], dim=1)
-    ky, vy = ek[0].unsqueeze(0).reshape(B, -1, H, HD), ev[0].unsqueeze(0).reshape(B, -1, H, HD)
-    qy = qc.reshape(B, T, SL, H, HD).permute(0, 2, 1, 3, 4).reshape(B, SL * T, H, HD)
-    c = att(qy.transpose(1, 2), ky.transpose(1, 2), vy.transpose(1, 2)).transpose(1, 2).reshape(B, SL, T, H * HD)
-    cross = lin(c.permute(0, 2, 1, 3).reshape(B * T, SL, H * HD), "to_out_context")
+    if state is not None:
+        bc, state.cross_count = pab.if_broadcast_cross(timestep, state.cross_count)
+    if bc:
+        cross = state.last_cross
+    else:
+        qc = torch.cat([lin(hs, "to_q_cross"), eq], dim=1)
+        ky, vy = ek[0].unsqueeze(0).reshape(B, -1, H, HD), ev[0].unsqueeze(0).reshape(B, -1, H, HD)
+        qy = qc.reshape(B, T, SL, H, HD).permute(0, 2, 1, 3, 4).reshape(B, SL * T, H, HD)
+        c = att(qy.transpose(1, 2), ky.transpose(1, 2), vy.transpose(1, 2)).transpose(1, 2).reshape(B, SL, T, H * HD)
+        cross = lin(c.permute(0, 2, 1, 3).reshape(B * T, SL, H * HD), "to_out_context")
+        if state is not None:
+            state.last_cross = cross
     # spatial (:667-703)
-    q, k, v = (torch.cat([lin(hs, n), e], dim=1) for n, e in (("to_q", eq), ("to_k", ek), ("to_v", ev)))
-    sp = att(heads(q), heads(k), heads(v)).transpose(1, 2).reshape(B * T, SL, H * HD)
+    if state is not None:
+        bs, state.spatial_count = pab.if_broadcast_spatial(timestep, state.spatial_count)
+        state.last_decisions = (bt, bc, bs)
+    if bs:
+        sp = state.last_spatial
+    else:
+        q, k, v = (torch.cat([lin(hs, n), e], dim=1) for n, e in (("to_q", eq), ("to_k", ek), ("to_v", ev)))
+        sp = att(heads(q), heads(k), heads(v)).transpose(1, 2).reshape(B * T, SL, H * HD)
+        if state is not None:
+            state.last_spatial = sp
     h = sp * 1.1 + cross
     hv, ht = h[:, :S], h[:, S:]
     hv = lin(hv, "to_out.0")
@@ -145,6 +187,14 @@ def attention_layer(sd, hidden_states, encoder_hidden_states, B, T, H, context_p
 
 
 # ------------------------------------------------------------------------------------------------ block and model
+def layer_inputs(seed):
+    """The bf16-exact inputs of tests/golden/vchitect_layer_small.pt (B = 1, F = 3, S = 16, L = 4, dim 192), regenerated from the seed
+    the fixture records: hidden_states [3, 16, 192], encoder_hidden_states [3, 4, 192], temb [3, 192] (float32 holding bf16 values)."""
+    g = torch.Generator().manual_seed(seed + 2)
+    bf = lambda *s: torch.randn(*s, generator=g).to(torch.bfloat16).float()
+    return bf(3, 16, 192), bf(3, 4, 192), bf(3, 192)
+
+
 def sincos_2d(embed_dim, grid, base_size):
     """diffusers get_2d_sincos_pos_embed(embed_dim, grid, base_size=base_size): float64 [grid * grid, embed_dim] (w goes first)."""
     import numpy as np
@@ -167,12 +217,43 @@ def timestep_proj(t, dim=256):
     return torch.cat([torch.cos(e), torch.sin(e)], dim=-1)
 
 
-def model_forward(sd, cfg, hidden_states, encoder_hidden_states, pooled, timestep, dtype=torch.float64):
-    """VchitectXLTransformerModel.forward (vchitect_transformer_3d.py:489-590) with JointTransformerBlock.forward (:114-175), the diffusers
+def block_forward(sd, pre, x, y, temb, B, F, H, last, dtype=torch.float64, state=None, timestep=None):
+    """JointTransformerBlock.forward (vchitect_transformer_3d.py:114-175) on the weights under prefix ``pre``: x [B*F, S, C], y [B*F, L, C],
+    temb [B*F, C] -> (x, y, attention outputs); y comes back unchanged from a context_pre_only block (the reference returns None)."""
+    import torch.nn.functional as Fn
+
+    lin = lambda x, n: Fn.linear(x, sd[n + ".weight"].to(dtype), sd[n + ".bias"].to(dtype))
+    ln = lambda x: Fn.layer_norm(x, x.shape[-1:], eps=1e-6)
+    cur = temb
+    asd = {k[len(pre) + 5:]: v for k, v in sd.items() if k.startswith(pre + "attn.")}
+    sh, sc, g, sh2, sc2, g2 = lin(Fn.silu(cur), pre + "norm1.linear").chunk(6, dim=1)
+    xn = ln(x) * (1 + sc[:, None]) + sh[:, None]
+    if last:
+        csc, csh = lin(Fn.silu(cur), pre + "norm1_context.linear").chunk(2, dim=1)
+        yn = ln(y) * (1 + csc)[:, None] + csh[:, None]
+    else:
+        csh, csc, cg, csh2, csc2, cg2 = lin(Fn.silu(cur), pre + "norm1_context.linear").chunk(6, dim=1)
+        yn = ln(y) * (1 + csc[:, None]) + csh[:, None]
+    av, at = attention_layer(asd, xn, yn, B, F, H, last, dtype, state, timestep)
+    x = x + g.unsqueeze(1) * av
+    xn = ln(x) * (1 + sc2[:, None]) + sh2[:, None]
+    ff = lin(Fn.gelu(lin(xn, pre + "ff.net.0.proj"), approximate="tanh"), pre + "ff.net.2")
+    x = x + g2.unsqueeze(1) * ff
+    if not last:
+        y = y + cg.unsqueeze(1) * at
+        yn = ln(y) * (1 + csc2[:, None]) + csh2[:, None]
+        y = y + cg2.unsqueeze(1) * lin(Fn.gelu(lin(yn, pre + "ff_context.net.0.proj"), approximate="tanh"), pre + "ff_context.net.2")
+    return x, y, (av, at)
+
+
+def model_forward(sd, cfg, hidden_states, encoder_hidden_states, pooled, timestep, dtype=torch.float64, pab_state=None):
+    """VchitectXLTransformerModel.forward (vchitect_transformer_3d.py:489-590) with JointTransformerBlock.forward (block_forward), the diffusers
     leaves restated (PatchEmbed with cropped_pos_embed, CombinedTimestepTextProjEmbeddings, AdaLayerNormZero, AdaLayerNormContinuous,
     FeedForward gelu-approximate), all in ``dtype``.  cfg: dict(num_layers, heads, patch, out_channels, sample_size, pos_embed_max_size).
-    encoder_hidden_states [B*F, L, D].  `cur_temb = temb.repeat(F, 1)` literally (:548); norm_out with the temb of each row's own sample
-    (the reference's line broadcasts only at B = 1, where the two agree)."""
+    encoder_hidden_states [B*F, L, D], or [B, L, D] — the pipeline's form: every frame of a sample reads its row, which is what the
+    broadcast of norm1_context over the F rows of temb does in the class at B = 1.  `cur_temb = temb.repeat(F, 1)` literally (:548);
+    norm_out with the temb of each row's own sample (the reference's line broadcasts only at B = 1, where the two agree).
+    ``pab_state``: a PabState kept across calls (PAB decisions of `int(timestep[0])`); None: no PAB."""
     import torch.nn.functional as Fn
 
     lin = lambda x, n: Fn.linear(x, sd[n + ".weight"].to(dtype), sd[n + ".bias"].to(dtype))
@@ -181,6 +262,8 @@ def model_forward(sd, cfg, hidden_states, encoder_hidden_states, pooled, timeste
     p, H, depth = cfg["patch"], cfg["heads"], cfg["num_layers"]
     C = H * HD
     Hp, Wp = Hh // p, Ww // p
+    if encoder_hidden_states.shape[0] == B and F > 1:
+        encoder_hidden_states = encoder_hidden_states.repeat_interleave(F, dim=0)
     x = Fn.conv2d(hidden_states.reshape(B * F, cin, Hh, Ww).to(dtype), sd["pos_embed.proj.weight"].to(dtype), sd["pos_embed.proj.bias"].to(dtype),
                   stride=p).flatten(2).transpose(1, 2)
     m = cfg["pos_embed_max_size"]
@@ -195,25 +278,8 @@ def model_forward(sd, cfg, hidden_states, encoder_hidden_states, pooled, timeste
     y = lin(encoder_hidden_states.to(dtype), "context_embedder")
     cur = temb.repeat(F, 1)
     for i in range(depth):
-        pre, last = f"transformer_blocks.{i}.", i == depth - 1
-        asd = {k[len(pre) + 5:]: v for k, v in sd.items() if k.startswith(pre + "attn.")}
-        sh, sc, g, sh2, sc2, g2 = lin(Fn.silu(cur), pre + "norm1.linear").chunk(6, dim=1)
-        xn = ln(x) * (1 + sc[:, None]) + sh[:, None]
-        if last:
-            csc, csh = lin(Fn.silu(cur), pre + "norm1_context.linear").chunk(2, dim=1)
-            yn = ln(y) * (1 + csc)[:, None] + csh[:, None]
-        else:
-            csh, csc, cg, csh2, csc2, cg2 = lin(Fn.silu(cur), pre + "norm1_context.linear").chunk(6, dim=1)
-            yn = ln(y) * (1 + csc[:, None]) + csh[:, None]
-        av, at = attention_layer(asd, xn, yn, B, F, H, last, dtype)
-        x = x + g.unsqueeze(1) * av
-        xn = ln(x) * (1 + sc2[:, None]) + sh2[:, None]
-        ff = lin(Fn.gelu(lin(xn, pre + "ff.net.0.proj"), approximate="tanh"), pre + "ff.net.2")
-        x = x + g2.unsqueeze(1) * ff
-        if not last:
-            y = y + cg.unsqueeze(1) * at
-            yn = ln(y) * (1 + csc2[:, None]) + csh2[:, None]
-            y = y + cg2.unsqueeze(1) * lin(Fn.gelu(lin(yn, pre + "ff_context.net.0.proj"), approximate="tanh"), pre + "ff_context.net.2")
+        st = None if pab_state is None else pab_state.blocks[i]
+        x, y, _ = block_forward(sd, f"transformer_blocks.{i}.", x, y, cur, B, F, H, i == depth - 1, dtype, st, int(timestep[0]))
     scale, shift = lin(Fn.silu(temb), "norm_out.linear").repeat_interleave(F, dim=0).chunk(2, dim=1)
     x = lin(ln(x) * (1 + scale)[:, None] + shift[:, None], "proj_out")
     co = cfg["out_channels"]

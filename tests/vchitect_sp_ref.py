@@ -14,7 +14,9 @@ All P ranks run in lockstep in one process; a "rank" is an entry of a list.  Wha
     token, so every real row must come out the same.
   * cross attention keys: row 0 OF THE LOCAL SHARD (attentions.py:781-786); the `cur_frame == 1` rule with the LOCAL frame count.
 
-UNPINNED like vchitect_ref: held against the reference by reading."""
+PINNED at P = 2: tests/test_vchitect_pinned_cpu.py holds model_forward(P = 2) to a float64 run of the reference's own class with
+sp_size = 2 in two gloo processes (tests/golden/vchitect_sp_small.pt, tools/mint_vchitect.py: F = 3 with one padded frame, S + L = 71
+with one padded token), within the class's own fp32-to-float64 distance.  Other P, B > 1 and per-frame text stay readings of the class."""
 from __future__ import annotations
 
 import torch
