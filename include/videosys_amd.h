@@ -783,7 +783,22 @@ int vsys_cfg_pndm_step(const void* model_out_f32, void* e_out_f32, const void* s
 #define VSYS_OP_GEMM_BF16_LN_QKV_KV          57
 #define VSYS_OP_ATTN_TEMPORAL_D64            58
 #define VSYS_OP_SCALE_ADD_ROWS               59
-#define VSYS_OP_COUNT 60
+#define VSYS_OP_ATTN_PREP_KV96               60
+#define VSYS_OP_FLASH_ATTN_D96               61
+#define VSYS_OP_ATTN_PREP_KV96_IMG           62
+#define VSYS_OP_FLASH_ATTN_D96_IMG           63
+#define VSYS_OP_ATTN_PREP_KV_ROPE            64
+#define VSYS_OP_FLASH_ATTN_D72_ROPE          65
+#define VSYS_OP_CLIP_ATTENTION_D64           66
+#define VSYS_OP_SPLITK_REDUCE_BIAS_ACT       67
+#define VSYS_OP_VAE_FIRST_IM2COL_NC          68
+#define VSYS_OP_PIXELS_TO_U8                 69
+#define VSYS_OP_UPSAMPLE_TRILINEAR2X         70
+#define VSYS_OP_CFG_ANCESTRAL_STEP           71
+#define VSYS_OP_PIXELS_TO_U8_TRUNC           72
+#define VSYS_OP_UPSAMPLE_TIME2X              73
+#define VSYS_OP_CFG_PNDM_STEP                74
+#define VSYS_OP_COUNT 75
 /* <<< VSYS_OP codes */
 
 #define VSYS_CMD_MAX_INT 24

@@ -15,6 +15,8 @@ from types import SimpleNamespace
 import pytest
 import torch
 
+from op_table import assert_coded
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VSYS_ERR_SHAPE, VSYS_ERR_ALIGN, VSYS_ERR_ARG = -1, -2, -3
 NEW = ("vsys_clip_attention_d64", "vsys_splitk_reduce_bias_act")
@@ -25,19 +27,19 @@ TINY = dict(hidden_size=128, intermediate_size=256, num_hidden_layers=2, num_att
 # ---------------------------------------------------------------------------------------------------- C ABI
 def test_new_entry_points_in_header_library_and_ctypes_table():
     import __graft_entry__ as G
-    from videosys_amd import _lib, _opcodes
+    from videosys_amd import _lib
 
     hdr = open(os.path.join(ROOT, "include", "videosys_amd.h")).read()
     lib = _lib.load()
+    assert_coded(NEW)                                 # in the launch-program table, with the prototype's arity
     for n in NEW:
         assert re.search(rf"\nint {n}\(", hdr), n
         assert hasattr(lib, n) and n in _lib.SIGNATURES, n
-        assert n not in _opcodes.OPCODES              # outside the launch-program table (csrc/gen/program_gen.py NO_OP)
         proto = re.search(rf"\nint {n}\(([^;]*?)\);", hdr, flags=re.S).group(1)
         assert len(proto.split(",")) == len(_lib.SIGNATURES[n]), n
         comment = hdr[:hdr.index(f"\nint {n}(")].rsplit("/*", 1)[1]
         assert "modeling_clip.py" in comment and "pipeline_vchitect.py:368" in comment, n   # names the third-party code it replaces
-    assert re.search(r"#define VSYS_OP_COUNT 60\b", hdr) and re.search(r"#define VSYS_ABI_VERSION 1\b", hdr)
+    assert re.search(r"#define VSYS_OP_COUNT 75\b", hdr) and re.search(r"#define VSYS_ABI_VERSION 1\b", hdr)
     assert "clip_ops.hip" in G.SOURCES
     src = open(os.path.join(ROOT, "videosys_amd", "csrc", "clip_ops.hip")).read()
     assert "asm" not in src.replace("namespace", "")  # plain HIP C++: no inline assembly in the new kernels

@@ -159,6 +159,15 @@ def test_replayed_steps_equal_eager_steps_bit_for_bit():
     finally:
         del pipe.transformer.use_programs
     assert pipe.step_stats["eager"] == STEPS and torch.equal(a, c), "the replayed steps differ from the eager ones"
+    # the recorded step is ONE command array: the d96 attention launches are commands of it, and nothing is a host action
+    from videosys_amd._opcodes import OPCODES
+
+    (prog, _), = pipe._programs.values()
+    assert len(prog.segments) == 1 and isinstance(prog.segments[0], tuple), "a recorded single-rank step holds a host action"
+    ops = [c.op for c in prog.segments[0][0]]
+    layers = TCFG["num_layers"]
+    assert len(ops) == prog.n_launches and ops.count(OPCODES["vsys_attn_prep_kv96"]) >= layers
+    assert ops.count(OPCODES["vsys_flash_attn_d96"]) == 2 * layers                                  # self- and cross-attention
 
 
 def test_pab_decision_sequence_and_programs():

@@ -128,6 +128,51 @@ def test_sharded_equals_single_process_on_every_rank_and_route(name, P):
         assert not bad, f"model {name}, rank {r} of {P}: (p2p, route) -> (recorded equal, replayed equal, max |diff|): {bad}"
 
 
+def test_recorded_image_step_has_exactly_the_collectives_as_host_actions():
+    """Model A on 2 ranks, the image route over all_to_all_single: the image attention launches are commands of the recorded step
+    (they have op codes), so its host actions are the collectives and nothing else — two all-to-alls per block and the all-gather of
+    the tail, as many collectives per replay — and the replay gives the single-process bits."""
+    from tools.local_group import LocalWorld
+    from videosys_amd import pab, program
+    from videosys_amd._opcodes import OPCODES
+
+    P, depth = 2, 2
+    want = single_process("A")
+    pab.set_pab_manager(None)
+    x, enc, mask = inputs("A")
+
+    def rank_fn(r, group):
+        torch.cuda.set_device(0)
+        calls = {"n": 0}
+        a2a, gather = group.all_to_all_single, group.all_gather_into_tensor
+        group.all_to_all_single = lambda recv, send: (calls.__setitem__("n", calls["n"] + 1), a2a(recv, send))[1]
+        group.all_gather_into_tensor = lambda out, t: (calls.__setitem__("n", calls["n"] + 1), gather(out, t))[1]
+        m = shard(model("A"), group, P, r, False, "image")
+        run(m, x, enc, mask)                  # warm, as record_and_replay
+        calls["n"] = 0
+        with program.Recorder() as rec:
+            out = run(m, x, enc, mask)
+        prog = rec.finish()
+        assert prog is not None, rec.invalid
+        recorded = calls["n"]
+        host = [k for k, seg in enumerate(prog.segments) if not isinstance(seg, tuple)]
+        ops = [c.op for seg in prog.segments if isinstance(seg, tuple) for c in seg[0]]
+        # no two host actions are neighbours: between two collectives lie the commands of the attention they frame
+        apart = all(k > 0 and isinstance(prog.segments[k - 1], tuple) for k in host)
+        out.fill_(float("nan"))
+        calls["n"] = 0
+        prog.run()
+        torch.cuda.synchronize()
+        return (recorded, len(host), apart, calls["n"], ops.count(OPCODES["vsys_attn_prep_kv96_img"]),
+                ops.count(OPCODES["vsys_flash_attn_d96_img"]), len(ops) == prog.n_launches, bool(torch.equal(out, want)))
+
+    for r, res in enumerate(LocalWorld(P, timeout=120).run(rank_fn)):
+        n = 2 * depth + 1
+        assert res == (n, n, True, n, depth, depth, True, True), \
+            (f"rank {r}: (collectives while recording, host actions, commands between them, collectives per replay, image prep / "
+             f"flash commands, every launch a command, replay equals single process) = {res}")
+
+
 def test_pab_schedule_sharded_equals_single_process_and_broadcast_steps_exchange_nothing():
     """Four timesteps, ranges 2 (spatial) and 3 (cross), as tests/test_gpu_osp_model.py: every step on every rank equals the
     single-process step through the same schedule (the caches hold local rows), and a step exchanges twice per block that computes its

@@ -151,6 +151,14 @@ def test_latents_within_the_bf16_floor_and_replay_equals_eager(fx, embeds):
         pipe.transformer.use_programs = True
     assert pipe.step_stats["eager"] == STEPS + 9
     assert torch.equal(out, eager), "the replayed sampler differs from the eager one"
+    # the recorded call is ONE command array: the roped d72 attention launches are commands of it, and nothing is a host action
+    from videosys_amd._opcodes import OPCODES
+
+    (prog, _), = pipe._programs.values()
+    assert len(prog.segments) == 1 and isinstance(prog.segments[0], tuple), "a recorded single-rank call holds a host action"
+    ops = [c.op for c in prog.segments[0][0]]
+    assert len(ops) == prog.n_launches
+    assert ops.count(OPCODES["vsys_attn_prep_kv_rope"]) >= 1 and ops.count(OPCODES["vsys_attn_prep_kv_rope"]) == ops.count(OPCODES["vsys_flash_attn_d72_rope"])
     f64 = restated_loop(fx, pe, ne, z0, torch.float64)
     floor = rms(restated_loop(fx, pe, ne, z0, torch.bfloat16), f64)
     err = rms(out, f64)

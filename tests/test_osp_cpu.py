@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import osp_ref
+from op_table import assert_coded
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "osp_v120_fwd_small.pt")
@@ -193,14 +194,14 @@ def test_alias_and_top_level_names():
         videosys.OpenSoraPlanConfig
 
 
-def test_entry_points_declared_exported_bound_and_outside_the_op_table():
-    from videosys_amd import _lib, _opcodes
+def test_entry_points_declared_exported_bound_and_in_the_op_table():
+    from videosys_amd import _lib
 
     hdr = open(os.path.join(ROOT, "include", "videosys_amd.h")).read()
     lib = _lib.load()
     for n in NEW:
         assert re.search(rf"\nint {n}\(", hdr) and n in _lib.SIGNATURES and hasattr(lib, n)
-        assert n not in _opcodes.OPCODES              # outside the launch-program table (csrc/gen/program_gen.py NO_OP)
+    assert_coded(NEW)                                 # in the launch-program table, with the prototype's arity
     assert "open_sora_plan_v120_transformer_3d.py:" in hdr
 
 

@@ -22,6 +22,7 @@ import pytest
 import torch
 
 import osp_vae_ref as R
+from op_table import assert_coded
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -185,14 +186,15 @@ def test_new_entry_points_in_header_library_and_ctypes_table():
     hdr = open(os.path.join(ROOT, "include", "videosys_amd.h")).read()
     gen = open(os.path.join(ROOT, "videosys_amd", "csrc", "gen", "program_gen.py")).read()
     no_op = re.search(r"\nNO_OP = \{(.*?)\}", gen, flags=re.S).group(1)
+    assert_coded(NEW)                                 # in the launch-program table, with the prototype's arity
     lib = _lib.load()
     for n in NEW:
         assert re.search(rf"\nint {n}\(", hdr), n
         assert hasattr(lib, n) and n in _lib.SIGNATURES, n
-        assert n not in _opcodes.OPCODES and f'"{n}"' in no_op, n       # outside the launch-program table
+        assert f'"{n}"' not in no_op, n
         proto = re.search(rf"\nint {n}\(([^;]*?)\);", hdr, flags=re.S).group(1)
         assert len(proto.split(",")) == len(_lib.SIGNATURES[n]), n
-    assert len(_opcodes.OPCODES) == 59 and "#define VSYS_OP_COUNT 60" in hdr
+    assert len(_opcodes.OPCODES) == 74 and "#define VSYS_OP_COUNT 75" in hdr
     assert "autoencoder_kl_open_sora_plan_v120.py:349-357" in hdr and "pipeline_open_sora_plan.py:1186-1188" in hdr
     import __graft_entry__ as G
 

@@ -17,6 +17,8 @@ from types import SimpleNamespace
 import pytest
 import torch
 
+from op_table import assert_coded
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VSYS_ERR_SHAPE, VSYS_ERR_ALIGN, VSYS_ERR_ARG = -1, -2, -3
 HD = 96
@@ -231,14 +233,14 @@ def test_set_parallel_drops_the_recorded_programs():
 IMG = ("vsys_attn_prep_kv96_img", "vsys_flash_attn_d96_img")
 
 
-def test_image_entry_points_declared_exported_bound_and_outside_the_op_table():
-    from videosys_amd import _lib, _opcodes
+def test_image_entry_points_declared_exported_bound_and_in_the_op_table():
+    from videosys_amd import _lib
 
     hdr = open(os.path.join(ROOT, "include", "videosys_amd.h")).read()
     lib = _lib.load()
     for n in IMG:
         assert re.search(rf"\nint {n}\(", hdr) and n in _lib.SIGNATURES and hasattr(lib, n)
-        assert n not in _opcodes.OPCODES              # outside the launch-program table (csrc/gen/program_gen.py NO_OP)
+    assert_coded(IMG)                                 # in the launch-program table, with the prototype's arity
     src = open(os.path.join(ROOT, "__graft_entry__.py")).read()
     assert '"attention96_img.hip"' in src and "attention96.h" in src
 

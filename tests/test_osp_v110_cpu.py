@@ -9,6 +9,7 @@ import torch
 
 import osp_v110_ref as R
 from conftest import ROOT
+from op_table import assert_coded
 
 FIXTURE = os.path.join(ROOT, "tests", "golden", "osp_v110_fwd_small.pt")
 
@@ -215,8 +216,10 @@ def test_forward_refuses_what_is_not_built(fx, monkeypatch):
         model(x[:, :, :1], timestep=torch.tensor([1, 1]), encoder_hidden_states=enc)
 
 
-def test_new_entry_points_are_bound_without_op_codes():
+def test_new_entry_points_are_bound_with_op_codes():
     from videosys_amd import _opcodes
 
-    for name in ("vsys_attn_prep_kv_rope", "vsys_flash_attn_d72_rope"):
-        assert name in _opcodes.ENTRY_POINTS and name not in _opcodes.OPCODES
+    names = ("vsys_attn_prep_kv_rope", "vsys_flash_attn_d72_rope")
+    for name in names:
+        assert name in _opcodes.ENTRY_POINTS
+    assert_coded(names)

@@ -9,6 +9,7 @@ import re
 import torch
 
 import vchitect_ref as vr
+from op_table import LATER, TOO_WIDE, assert_coded, prototype_counts
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VSYS_ERR_SHAPE, VSYS_ERR_ALIGN, VSYS_ERR_ARG = -1, -2, -3
@@ -37,12 +38,15 @@ def test_op_table_keeps_every_code_and_adds_the_new_entries():
 
     for name, code in OPCODES_BEFORE.items():
         assert _opcodes.OPCODES.get(name) == code, name
-    new = {n: c for n, c in _opcodes.OPCODES.items() if n not in OPCODES_BEFORE}
+    new = {n: c for n, c in _opcodes.OPCODES.items() if n not in OPCODES_BEFORE and n not in LATER}
     assert set(new) == set(NEW)
     assert sorted(new.values()) == [58, 59]
+    # every entry point coded since then, in declaration order, and nothing else
+    assert [(n, _opcodes.OPCODES.get(n)) for n in LATER] == list(zip(LATER, range(60, 75)))
+    assert len(_opcodes.OPCODES) == len(OPCODES_BEFORE) + len(NEW) + len(LATER) == 74
     hdr = open(os.path.join(ROOT, "include", "videosys_amd.h")).read()
     defines = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define VSYS_OP_(\w+)\s+(\d+)", hdr)}
-    assert defines.pop("COUNT") == 60
+    assert defines.pop("COUNT") == 75
     assert defines == {n[5:].upper(): c for n, c in _opcodes.OPCODES.items()}
     assert "#define VSYS_ABI_VERSION 1" in re.sub(r"[ \t]+", " ", hdr)
     m = re.search(r"#define VSYS_CMD_MAX_INT (\d+)\n#define VSYS_CMD_MAX_FLOAT (\d+)", hdr)
@@ -57,13 +61,35 @@ def test_library_exports_and_arity():
     from videosys_amd import _lib, _opcodes
 
     lib = _lib.load()
-    for n in list(OPCODES_BEFORE) + list(NEW):
+    assert_coded(LATER)
+    for n in list(OPCODES_BEFORE) + list(NEW) + list(LATER):
         assert hasattr(lib, n), n
         ni, nf = ctypes.c_int(), ctypes.c_int()
         assert lib.vsys_program_op_info(_opcodes.OPCODES[n], ctypes.byref(ni), ctypes.byref(nf)) == 0
         sig = _lib.SIGNATURES[n][:-1]
         assert (ni.value, nf.value) == (sum(t is not _lib._f32 for t in sig), sum(t is _lib._f32 for t in sig)), n
     assert lib.vsys_abi_version() == 1
+
+
+def test_an_entry_point_has_a_code_exactly_when_it_fits_a_command():
+    """Over every prototype of the header whose last parameter is the stream: in OPCODES if and only if its integer / pointer count is
+    at most VSYS_CMD_MAX_INT (24) and its float count at most VSYS_CMD_MAX_FLOAT (4); exactly one entry point is outside."""
+    from videosys_amd import _opcodes
+
+    hdr = open(os.path.join(ROOT, "include", "videosys_amd.h")).read()
+    launch = {n: kinds[:-1] for n, (kinds, _) in _opcodes.ENTRY_POINTS.items()
+              if re.search(rf"\nint {n}\([^;]*?void\* stream\);", hdr, flags=re.S)}
+    outside = set()
+    for n, kinds in launch.items():
+        ni, nf = len(kinds) - kinds.count("f"), kinds.count("f")
+        assert (ni, nf) == prototype_counts(n), n
+        fits = ni <= 24 and nf <= 4
+        assert (n in _opcodes.OPCODES) == fits, (n, ni, nf)
+        if not fits:
+            outside.add(n)
+    assert outside == {TOO_WIDE}
+    assert prototype_counts(TOO_WIDE) == (26, 0)
+    assert set(_opcodes.OPCODES) == set(launch) - outside
 
 
 def test_host_side_argument_checks():

@@ -20,6 +20,8 @@ import numpy as np
 import pytest
 import torch
 
+from op_table import assert_coded
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VSYS_ERR_SHAPE, VSYS_ERR_ALIGN, VSYS_ERR_ARG = -1, -2, -3
 
@@ -271,14 +273,14 @@ NEW = ("vsys_vae_first_im2col_nc", "vsys_pixels_to_u8")
 
 
 def test_new_entry_points_in_header_library_and_ctypes_table():
-    from videosys_amd import _lib, _opcodes
+    from videosys_amd import _lib
 
     hdr = open(os.path.join(ROOT, "include", "videosys_amd.h")).read()
     lib = _lib.load()
+    assert_coded(NEW)                                 # in the launch-program table, with the prototype's arity
     for n in NEW:
         assert re.search(rf"\nint {n}\(", hdr), n
         assert hasattr(lib, n) and n in _lib.SIGNATURES, n
-        assert n not in _opcodes.OPCODES              # outside the launch-program table (csrc/gen/program_gen.py NO_OP)
         proto = re.search(rf"\nint {n}\(([^;]*?)\);", hdr, flags=re.S).group(1)
         assert len(proto.split(",")) == len(_lib.SIGNATURES[n]), n
     import __graft_entry__ as G

@@ -1,6 +1,6 @@
 """Tensor-level wrappers of the entry points that exist for the CLIP text encoders of Vchitect-2.0 (include/videosys_amd.h:
-vsys_clip_attention_d64, vsys_splitk_reduce_bias_act; csrc/clip_ops.hip), on the launch route of videosys_amd.ops.  Neither has an op
-code: they run once per prompt, outside any recorded step, and go through ctypes.  HIP device tensors only, no eager fallback.
+vsys_clip_attention_d64, vsys_splitk_reduce_bias_act; csrc/clip_ops.hip), on the launch route of videosys_amd.ops
+(torch.ops.vsys.launch, op codes 66 and 67; they run once per prompt and nothing records them).  HIP device tensors only, no eager fallback.
 Guard-band tests: tests/test_gpu_isolation_clip.py."""
 from __future__ import annotations
 

@@ -3,11 +3,13 @@
 (videosys_amd/_opcodes.py: op codes + the argument / return kinds of EVERY entry point, which videosys_amd/_lib.py turns into the
 ctypes table) from the prototypes of include/videosys_amd.h and include/videosys_amd_lab.h.
 
-Every extern "C" entry point whose last parameter is ``void* stream`` gets an op code: existing codes are kept (they are ABI), new
-entry points are numbered after the highest one.  A command carries the entry point's integer / pointer arguments in declaration
-order in a[] and its float arguments in f[] (include/videosys_amd.h "Launch programs"); the generated switch casts them back to the
-prototype's parameter types, so vsys_program_run — and with it torch.ops.vsys.launch / program_run (csrc/torch_binding.cpp) — reaches
-EVERY kernel of the library through the same functions a direct caller binds.
+The rule: every extern "C" entry point whose last parameter is ``void* stream`` and whose arguments fit a vsys_cmd (VSYS_CMD_MAX_INT
+integer / pointer, VSYS_CMD_MAX_FLOAT float) gets an op code; the only exception is vsys_attn_temporal_d64_img with 26 integer /
+pointer arguments (NO_OP below, checked against the header on every run).  Existing codes are kept (they are ABI), new entry points
+are numbered after the highest one.  A command carries the entry point's integer / pointer arguments in declaration order in a[] and
+its float arguments in f[] (include/videosys_amd.h "Launch programs"); the generated switch casts them back to the prototype's
+parameter types, so vsys_program_run — and with it torch.ops.vsys.launch / program_run (csrc/torch_binding.cpp) — reaches every such
+kernel through the same functions a direct caller binds.
 
     python videosys_amd/csrc/gen/program_gen.py          rewrites the three outputs in place (idempotent)
     python videosys_amd/csrc/gen/program_gen.py --check  exit 1 if any output is stale (tests/test_host_cpu.py)
@@ -21,18 +23,10 @@ HDR = os.path.join(ROOT, "include", "videosys_amd.h")
 LAB_HDR = os.path.join(ROOT, "include", "videosys_amd_lab.h")
 INC = os.path.join(ROOT, "videosys_amd", "csrc", "program_ops.inc")
 PYM = os.path.join(ROOT, "videosys_amd", "_opcodes.py")
-# entry points with a stream that stay OUT of the op table: they run once per video outside the denoise step, so nothing records them,
-# and the table's size is pinned where it was when the Vchitect transformer was added (tests/test_vchitect_cpu.py)
-# (vsys_attn_temporal_d64_img: a recorded sequence-parallel step issues it from the host closure of the collective it feeds;
-#  vsys_attn_prep_kv96 / vsys_flash_attn_d96: a recorded Open-Sora-Plan step replays them from host closures, open_sora_plan_ops.py;
-#  vsys_attn_prep_kv96_img / vsys_flash_attn_d96_img: the same, on the exchange image of a sequence-parallel step;
-#  vsys_attn_prep_kv_rope / vsys_flash_attn_d72_rope: the same for Open-Sora-Plan v1.1, open_sora_plan_v110_ops.py;
-#  vsys_cfg_ancestral_step: the Open-Sora-Plan sampler launches it from the host after each replay, its scalars change every step;
-#  vsys_cfg_pndm_step: the same for the v1.1 sampler, whose pointers rotate as well; vsys_upsample_time2x: the v1.1 VAE decode)
-NO_OP = {"vsys_vae_first_im2col_nc", "vsys_pixels_to_u8", "vsys_clip_attention_d64", "vsys_splitk_reduce_bias_act",
-         "vsys_attn_temporal_d64_img", "vsys_attn_prep_kv96", "vsys_flash_attn_d96", "vsys_upsample_trilinear2x",
-         "vsys_cfg_ancestral_step", "vsys_pixels_to_u8_trunc", "vsys_attn_prep_kv96_img", "vsys_flash_attn_d96_img",
-         "vsys_attn_prep_kv_rope", "vsys_flash_attn_d72_rope", "vsys_upsample_time2x", "vsys_cfg_pndm_step"}
+# the launch entry points that do NOT fit a command record and so have no op code (checked in ops_of).  vsys_attn_temporal_d64_img: 26
+# integer / pointer arguments against VSYS_CMD_MAX_INT = 24, and growing the record is an ABI change; a recorded sequence-parallel
+# Vchitect step issues it from the host action of the collective it feeds (vchitect_ops.attn_temporal64_img)
+NO_OP = {"vsys_attn_temporal_d64_img"}
 BEGIN, END = "/* >>> VSYS_OP codes (generated: csrc/gen/program_gen.py) */", "/* <<< VSYS_OP codes */"
 
 
@@ -54,15 +48,28 @@ def parse(h):
     return out
 
 
-def ops_of(protos):
-    """The prototypes that get an op code: last parameter ``void* stream`` and not in NO_OP; (name, kinds without the stream)."""
-    return [(name, kinds[:-1]) for name, kinds, _, launches in protos if launches and name not in NO_OP]
+def counts(kinds):
+    """(integer / pointer arguments, float arguments) of a kind list: the a[] and f[] slots a command needs."""
+    nf = sum(1 for k, _ in kinds if k == "f")
+    return len(kinds) - nf, nf
+
+
+def ops_of(protos, cap_i, cap_f):
+    """The prototypes that get an op code, as (name, kinds without the stream): last parameter ``void* stream`` and at most cap_i
+    integer / pointer and cap_f float arguments.  The ones left out must be exactly NO_OP."""
+    launch = [(name, kinds[:-1]) for name, kinds, _, launches in protos if launches]
+    wide = {name: counts(kinds) for name, kinds in launch if counts(kinds)[0] > cap_i or counts(kinds)[1] > cap_f}
+    if set(wide) != NO_OP:
+        raise SystemExit(f"NO_OP = {sorted(NO_OP)}, but the launch entry points that do not fit a vsys_cmd ({cap_i} integer / {cap_f} float "
+                         f"arguments) are {wide}: every entry point that fits gets a code, one that does not is named there with the reason")
+    return [e for e in launch if e[0] not in wide]
 
 
 def build():
     h = open(HDR).read()
     protos, lab_protos = parse(h), parse(open(LAB_HDR).read())
-    entries = ops_of(protos)
+    cap_i, cap_f = (int(re.search(rf"#define VSYS_CMD_MAX_{w}\s+(\d+)", h).group(1)) for w in ("INT", "FLOAT"))
+    entries = ops_of(protos, cap_i, cap_f)
     old = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define VSYS_OP_(\w+)\s+(\d+)", h) if m.group(1) != "COUNT"}
     codes, nxt = {}, max(old.values(), default=0) + 1
     for name, _ in entries:
@@ -75,24 +82,19 @@ def build():
             nxt += 1
     count = max(codes.values()) + 1
     by_code = sorted(entries, key=lambda e: codes[e[0]])
-    max_i = max(sum(1 for k, _ in kinds if k != "f") for _, kinds in entries)
-    max_f = max(sum(1 for k, _ in kinds if k == "f") for _, kinds in entries)
+    max_i, max_f = (max(counts(kinds)[w] for _, kinds in entries) for w in (0, 1))
     # ---- header block
     lines = [BEGIN]
     for name, _ in by_code:
         lines.append(f"#define VSYS_OP_{name[5:].upper():28s} {codes[name]}")
     lines += [f"#define VSYS_OP_COUNT {count}", END]
     block = "\n".join(lines)
-    if BEGIN in h:
-        h2 = h[:h.index(BEGIN)] + block + h[h.index(END) + len(END):]
-    else:   # first run: replace the hand-written run of defines
-        m = list(re.finditer(r"#define VSYS_OP_\w+[^\n]*\n", h))
-        h2 = h[:m[0].start()] + block + "\n" + h[m[-1].end():]
+    h2 = h[:h.index(BEGIN)] + block + h[h.index(END) + len(END):]
     # ---- dispatch
     inc = ["// GENERATED by csrc/gen/program_gen.py from include/videosys_amd.h — do not edit.",
            f"static_assert(VSYS_CMD_MAX_INT >= {max_i} && VSYS_CMD_MAX_FLOAT >= {max_f}, \"vsys_cmd is too small for the widest entry point\");",
            "#ifdef VSYS_PROGRAM_TABLE", "constexpr OpInfo kOps[VSYS_OP_COUNT] = {", "    {0, 0},"]
-    table = {codes[n]: (sum(1 for k, _ in ks if k != "f"), sum(1 for k, _ in ks if k == "f"), n) for n, ks in entries}
+    table = {codes[n]: counts(ks) + (n,) for n, ks in entries}
     for c in range(1, count):
         ni, nf, n = table.get(c, (0, 0, "(unused)"))
         inc.append(f"    {{{ni}, {nf}}},   // {c} {n}")

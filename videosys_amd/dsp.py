@@ -45,8 +45,9 @@ def group_rank(group) -> int:
 def all_to_all_single(recv, send, group, before=None):
     """Stream-ordered all-to-all on torch's current stream.  A host-side action: under a launch-program recorder it is logged
     and re-issued on every replay (program.host_call); the buffers are the SequenceParallel object's resident staging buffers.
-    ``before``: a callable issued in the same host action, in front of the collective (a launch without an op code that fills
-    ``send``: vchitect_ops.attn_temporal64_img)."""
+    ``before``: a callable issued in the same host action, in front of the collective.  It serves the one launch entry point that
+    does not fit a vsys_cmd and so has no op code, vsys_attn_temporal_d64_img (26 integer / pointer arguments, a command holds 24;
+    vchitect_ops.attn_temporal64_img(defer=True)), which fills ``send``: a replayed step gets no segment of its own for it."""
     from . import program
 
     def issue():
@@ -941,14 +942,13 @@ class UlyssesParallel:
         """The resident send image [P (destination)][B][Nl][C/P] of gather_heads_image, for the caller to fill."""
         return self._buf("g_send", (self.P, B, self._image_len(Lv), C // self.P), like)
 
-    def gather_heads_image(self, send, B, Lv, C, out=None, before=None):
-        """``send``: the caller-filled image of heads_send_image (nothing is packed) -> [B*Nl, C] (all heads, local rows).  ``before``: a
-        launch without an op code that fills ``send``, issued in the collective's host action (all_to_all_single)."""
+    def gather_heads_image(self, send, B, Lv, C, out=None):
+        """``send``: the caller-filled image of heads_send_image (nothing is packed) -> [B*Nl, C] (all heads, local rows)."""
         Nl = self._image_len(Lv)
         _, unpack, sshape, oshape = plan_heads_gather(B, 0, Nl, Lv, C, self.P)
         assert tuple(send.shape) == sshape and send.is_contiguous()
         recv = self._buf("g_recv", sshape, send)
-        all_to_all_single(recv, send, self.group, before=before)
+        all_to_all_single(recv, send, self.group)
         if out is None:
             out = torch.empty(oshape, dtype=send.dtype, device=send.device)
         self.exec(recv, out, unpack)

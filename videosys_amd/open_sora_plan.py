@@ -293,13 +293,12 @@ class OpenSoraT2V:
             ao = oops.flash_attn96(qh[:, :hw], cos, sin, kp, vt, None, self._buf("attn_out_h", (B * N, hw)), B, Hl, N, N)
             return sp.gather_heads(ao, B, 0, N, C, out=out)
         # "image": the kernels read the receive image [P (source)][B][Nl][3][hw] as it lies and write the send image
-        # [P (destination)][B][Nl][hw] of the way back; the flash launch is issued by the host action of the collective it feeds
+        # [P (destination)][B][Nl][hw] of the way back
         img = sp.scatter_heads_image(qkv, B, N, C).view(P * B * Nl, 3 * hw)
         oops.attn_prep_kv96_img(img[:, hw:2 * hw], img[:, 2 * hw:], cos, sin, kp, vt, B, Hl, N, Nl, B * Nl)
         send = sp.heads_send_image(B, N, C, qkv)
-        attend = oops.flash_attn96_img(img[:, :hw], cos, sin, kp, vt, None, send.view(P * B * Nl, hw), B, Hl, N, N, Nl, B * Nl, B * Nl,
-                                       defer=True)
-        return sp.gather_heads_image(send, B, N, C, out=out, before=attend)
+        oops.flash_attn96_img(img[:, :hw], cos, sin, kp, vt, None, send.view(P * B * Nl, hw), B, Hl, N, N, Nl, B * Nl, B * Nl)
+        return sp.gather_heads_image(send, B, N, C, out=out)
 
     def reset_pab_state(self):
         pab.reset_states(self.states)

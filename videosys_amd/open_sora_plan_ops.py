@@ -3,17 +3,17 @@
 vsys_flash_attn_d96_img) and, at the end of the file, the CausalVAE decode and sampler kernels
 (vsys_upsample_trilinear2x, vsys_cfg_ancestral_step, vsys_pixels_to_u8_trunc).  HIP device tensors only, no eager fallback.
 
-No attention entry point has an op code (the op table is pinned, csrc/gen/program_gen.py NO_OP), so the launch goes through ctypes on
-torch's current stream, and under a launch-program recorder it is a ``program.host_call`` closure: the program keeps the tensors
-alive and re-issues the same call, with the same addresses, at the same position of every replay.  The per-sample key counts of the
-cross-attention are read by the kernel from device memory, so a replay carries no count.
+Every entry point here has an op code and goes through ``ops._call`` like the wrappers of ops.py: issued through
+torch.ops.vsys.launch, and under a launch-program recorder logged as a vsys_cmd, so a recorded step replays the attention launches
+inside its vsys_program_run call.  The per-sample key counts of the cross-attention are read by the kernel from device memory, so a
+replay carries no count.
 Element-wise tests: tests/test_gpu_osp_attention.py, tests/test_gpu_osp_attention_img.py; guard bands: tests/test_gpu_isolation_osp.py,
 tests/test_gpu_isolation_osp_img.py."""
 from __future__ import annotations
 
 import torch
 
-from . import _lib, program
+from . import program
 from .ops import VaeGrid, _bf16, _call, _chk, _p, kv_pad_len
 
 HEAD_DIM = 96
@@ -25,21 +25,6 @@ def alloc_kv_buffers96(batch, heads, kv_len, device):
     kp = torch.zeros(batch, heads, kv_pad, HEAD_DIM, dtype=torch.bfloat16, device=device)
     vt = torch.zeros(batch, heads, HEAD_DIM, kv_pad, dtype=torch.bfloat16, device=device)
     return kp, vt
-
-
-def _issue(name, tensors, args, defer=False):
-    """Launch ``name`` now and, under a recorder, at this position of every replay.  ``defer=True``: launch nothing, return the closure
-    (the caller issues it from the host action of the collective it feeds or follows, dsp.all_to_all_single(before=): a replayed step
-    then gets no segment of its own for it)."""
-    fn = getattr(_lib.load(), name)
-    program.keep(tensors)
-
-    def issue():
-        _lib.check(fn(*args, torch.cuda.current_stream().cuda_stream), name)
-
-    if defer:
-        return issue
-    program.host_call(issue)
 
 
 def _tables(rope_cos, rope_sin, rows):
@@ -61,9 +46,8 @@ def attn_prep_kv96(k, v, rope_cos, rope_sin, kp, vt, batch, heads, kv_len):
     assert tuple(kp.shape[-3:]) == (heads, kv_pad, HEAD_DIM) and tuple(vt.shape[-3:]) == (heads, HEAD_DIM, kv_pad)
     assert kp.numel() == vt.numel() == batch * heads * kv_pad * HEAD_DIM
     _tables(rope_cos, rope_sin, kv_len)
-    dp = lambda t: None if t is None else t.data_ptr()
-    _issue("vsys_attn_prep_kv96", (k, v, rope_cos, rope_sin, kp, vt),
-           (dp(k), k.stride(0), dp(v), v.stride(0), dp(rope_cos), dp(rope_sin), dp(kp), dp(vt), batch, heads, kv_len, kv_pad))
+    _call("vsys_attn_prep_kv96", _p(k), k.stride(0), _p(v), v.stride(0), _p(rope_cos), _p(rope_sin), _p(kp), _p(vt), batch, heads, kv_len,
+          kv_pad)
 
 
 def flash_attn96(q, rope_cos, rope_sin, kp, vt, kv_lens, out, batch, heads, q_len, kv_len):
@@ -79,10 +63,8 @@ def flash_attn96(q, rope_cos, rope_sin, kp, vt, kv_lens, out, batch, heads, q_le
     _tables(rope_cos, rope_sin, q_len)
     if kv_lens is not None:
         assert kv_lens.dtype == torch.int32 and kv_lens.is_contiguous() and kv_lens.numel() == batch
-    dp = lambda t: None if t is None else t.data_ptr()
-    _issue("vsys_flash_attn_d96", (q, rope_cos, rope_sin, kp, vt, kv_lens, out),
-           (dp(q), q.stride(0), dp(rope_cos), dp(rope_sin), dp(kp), dp(vt), dp(kv_lens), dp(out), out.stride(0), batch, heads, q_len,
-            kv_len, kv_pad))
+    _call("vsys_flash_attn_d96", _p(q), q.stride(0), _p(rope_cos), _p(rope_sin), _p(kp), _p(vt), _p(kv_lens), _p(out), out.stride(0),
+          batch, heads, q_len, kv_len, kv_pad)
     return out
 
 
@@ -99,7 +81,7 @@ def _image(t, batch, heads, length, seg_len, slab_rows):
     assert t.shape[0] >= (nslab - 1) * slab_rows + (batch - 1) * seg_len + last
 
 
-def attn_prep_kv96_img(k, v, rope_cos, rope_sin, kp, vt, batch, heads, kv_len, seg_len, slab_rows, defer=False):
+def attn_prep_kv96_img(k, v, rope_cos, rope_sin, kp, vt, batch, heads, kv_len, seg_len, slab_rows):
     """attn_prep_kv96 on an exchange image (vsys_attn_prep_kv96_img): token s of sample b is row (s // seg_len) * slab_rows + b * seg_len
     + s % seg_len of k and of v (the receive image [P (source)][B][Nl][...] of the Ulysses all-to-all: seg_len = Nl, slab_rows = B * Nl).
     Same bits as attn_prep_kv96 on the gathered rows; rows that belong to no token are neither read nor written."""
@@ -111,14 +93,11 @@ def attn_prep_kv96_img(k, v, rope_cos, rope_sin, kp, vt, batch, heads, kv_len, s
     assert tuple(kp.shape[-3:]) == (heads, kv_pad, HEAD_DIM) and tuple(vt.shape[-3:]) == (heads, HEAD_DIM, kv_pad)
     assert kp.numel() == vt.numel() == batch * heads * kv_pad * HEAD_DIM
     _tables(rope_cos, rope_sin, kv_len)
-    dp = lambda t: None if t is None else t.data_ptr()
-    return _issue("vsys_attn_prep_kv96_img", (k, v, rope_cos, rope_sin, kp, vt),
-                  (dp(k), k.stride(0), dp(v), v.stride(0), dp(rope_cos), dp(rope_sin), dp(kp), dp(vt), batch, heads, kv_len, kv_pad,
-                   seg_len, slab_rows), defer)
+    _call("vsys_attn_prep_kv96_img", _p(k), k.stride(0), _p(v), v.stride(0), _p(rope_cos), _p(rope_sin), _p(kp), _p(vt), batch, heads,
+          kv_len, kv_pad, seg_len, slab_rows)
 
 
-def flash_attn96_img(q, rope_cos, rope_sin, kp, vt, kv_lens, out, batch, heads, q_len, kv_len, seg_len, q_slab_rows, out_slab_rows,
-                     defer=False):
+def flash_attn96_img(q, rope_cos, rope_sin, kp, vt, kv_lens, out, batch, heads, q_len, kv_len, seg_len, q_slab_rows, out_slab_rows):
     """flash_attn96 with q and out as exchange images (vsys_flash_attn_d96_img): query token s of sample b is row (s // seg_len) *
     slab_rows + b * seg_len + s % seg_len, q and out each with its own slab stride and row stride — q the receive image of the way
     there, out the send image of the way back.  Same bits as flash_attn96 on the gathered rows."""
@@ -130,23 +109,20 @@ def flash_attn96_img(q, rope_cos, rope_sin, kp, vt, kv_lens, out, batch, heads, 
     _tables(rope_cos, rope_sin, q_len)
     if kv_lens is not None:
         assert kv_lens.dtype == torch.int32 and kv_lens.is_contiguous() and kv_lens.numel() == batch
-    dp = lambda t: None if t is None else t.data_ptr()
-    return _issue("vsys_flash_attn_d96_img", (q, rope_cos, rope_sin, kp, vt, kv_lens, out),
-                  (dp(q), q.stride(0), dp(rope_cos), dp(rope_sin), dp(kp), dp(vt), dp(kv_lens), dp(out), out.stride(0), batch, heads,
-                   q_len, kv_len, kv_pad, seg_len, q_slab_rows, out_slab_rows), defer)
+    _call("vsys_flash_attn_d96_img", _p(q), q.stride(0), _p(rope_cos), _p(rope_sin), _p(kp), _p(vt), _p(kv_lens), _p(out), out.stride(0),
+          batch, heads, q_len, kv_len, kv_pad, seg_len, q_slab_rows, out_slab_rows)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ CausalVAE decode and sampler
-# (csrc/vae_osp.hip; no op codes either: the decode is not part of a recorded step and the sampler step is launched by the host
-#  after each replay, so these three go through ctypes on torch's current stream and refuse to run under a recorder.
-#  Element-wise tests: tests/test_gpu_osp_vae_kernels.py; guard bands: tests/test_gpu_isolation_osp_pipeline.py)
+# (csrc/vae_osp.hip.  The two decode kernels are recordable like the other VAE kernels; the sampler step refuses to run under a
+#  recorder, see there.  Element-wise tests: tests/test_gpu_osp_vae_kernels.py; guard bands: tests/test_gpu_isolation_osp_pipeline.py)
 def upsample_trilinear2x(x, gs: VaeGrid, y, gd: VaeGrid, C):
     """Spatial2xTime2x3DUpsample up to its conv: x rows over gs -> the interior rows of gd ((1 if T == 1 else 2T - 1) frames of
     (2H, 2W)); F.interpolate(mode="trilinear") of frame 0 by (1, 2, 2) and of the later frames by (2, 2, 2) among themselves, the eight
     taps accumulated in fp32 and rounded once (include/videosys_amd.h)."""
     _chk(x, y)
     _bf16(x, y)
-    assert program.active() is None, "vsys_upsample_trilinear2x has no op code"
     assert x.shape == (gs.rows, C) and y.shape == (gd.rows, C) and x.is_contiguous() and y.is_contiguous()
     _call("vsys_upsample_trilinear2x", _p(x), gs._c, _p(y), gd._c, gs.n, C)
     return y
@@ -158,7 +134,8 @@ def cfg_ancestral_step(z, model_out, noise, model_in, guidance, dt, sigma_up, in
     bf16(z' * in_scale).  ``noise``: fp32 like z, or None when sigma_up == 0."""
     _chk(z, model_out, noise, model_in)
     _bf16(model_in)
-    assert program.active() is None, "vsys_cfg_ancestral_step has no op code: launch it after the replay"
+    # (dt, sigma_up and guidance are per-call scalars: a recorded copy would replay the values of the step it was recorded on)
+    assert program.active() is None, "vsys_cfg_ancestral_step: its scalars change every call, launch it after the replay"
     Bz, Cin = z.shape[:2]
     thw = z[0, 0].numel()
     assert z.dtype == torch.float32 and model_out.dtype == torch.float32 and z.is_contiguous() and model_out.is_contiguous()
@@ -178,7 +155,6 @@ def pixels_to_u8_trunc(x, g: VaeGrid, out, f0):
     f0 .. f0 + g.n * g.T - 1: trunc(bf16(clamp(bf16(bf16(x / 2) + 0.5), 0, 1) * 255)), the reference pipeline's own post-process."""
     _chk(x, out)
     _bf16(x)
-    assert program.active() is None, "vsys_pixels_to_u8_trunc has no op code"
     assert x.dim() == 2 and x.shape[0] == g.rows and x.stride(1) == 1 and x.shape[1] >= 3
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 4 and tuple(out.shape[1:]) == (g.H, g.W, 3)
     _call("vsys_pixels_to_u8_trunc", _p(x), g._c, g.n, x.stride(0), _p(out), out.shape[0], f0)

@@ -4,8 +4,8 @@ ops.attn_prep_kv) and vsys_flash_attn_d72_rope (Q side, the streaming 32-rows-pe
 temporal upsampler of its CausalVAE and its sampler step (vsys_upsample_time2x, vsys_cfg_pndm_step).  HIP device tensors only, no eager
 fallback.
 
-Neither has an op code (the op table is pinned, csrc/gen/program_gen.py NO_OP): the launch goes through ctypes on torch's current stream
-and, under a launch-program recorder, is a ``program.host_call`` closure, as in open_sora_plan_ops.py.
+Every entry point here has an op code and goes through ``ops._call``, as in open_sora_plan_ops.py: a recorded step replays the two
+attention launches inside its vsys_program_run call.
 Element-wise tests: tests/test_gpu_osp_v110_attention.py, tests/test_gpu_osp_v110_kernels.py; guard bands:
 tests/test_gpu_isolation_osp_v110.py, tests/test_gpu_isolation_osp_v110_pipeline.py."""
 from __future__ import annotations
@@ -15,7 +15,6 @@ import ctypes
 import torch
 
 from . import program
-from .open_sora_plan_ops import _issue
 from .ops import HEAD_DIM, VT_ROWS, VaeGrid, _bf16, _call, _chk, _p, alloc_kv_buffers, kv_pad_len  # noqa: F401  (alloc_kv_buffers, kv_pad_len: re-exported)
 
 PAIRS = HEAD_DIM // 2    # 36 (cos, sin) entries per token: entry p rotates the columns (2p, 2p + 1) of every head
@@ -39,9 +38,8 @@ def attn_prep_kv_rope(k, v, rope_cos, rope_sin, kp, vt, batch, heads, kv_len):
     assert tuple(kp.shape[-3:]) == (heads, kv_pad, HEAD_DIM) and tuple(vt.shape[-3:]) == (heads, VT_ROWS, kv_pad)
     assert kp.numel() == batch * heads * kv_pad * HEAD_DIM and vt.numel() == batch * heads * VT_ROWS * kv_pad and kv_len <= kv_pad
     _tables(rope_cos, rope_sin, kv_len)
-    _issue("vsys_attn_prep_kv_rope", (k, v, rope_cos, rope_sin, kp, vt),
-           (k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), rope_cos.data_ptr(), rope_sin.data_ptr(), kp.data_ptr(), vt.data_ptr(),
-            batch, heads, kv_len, kv_pad))
+    _call("vsys_attn_prep_kv_rope", _p(k), k.stride(0), _p(v), v.stride(0), _p(rope_cos), _p(rope_sin), _p(kp), _p(vt), batch, heads, kv_len,
+          kv_pad)
 
 
 def flash_attn_rope(q, rope_cos, rope_sin, kp, vt, out, batch, heads, q_len, kv_len):
@@ -55,20 +53,18 @@ def flash_attn_rope(q, rope_cos, rope_sin, kp, vt, out, batch, heads, q_len, kv_
     kv_pad = kp.shape[-2]
     assert kp.numel() == batch * heads * kv_pad * HEAD_DIM and vt.numel() == batch * heads * VT_ROWS * kv_pad and kv_len <= kv_pad
     _tables(rope_cos, rope_sin, q_len)
-    _issue("vsys_flash_attn_d72_rope", (q, rope_cos, rope_sin, kp, vt, out),
-           (q.data_ptr(), q.stride(0), rope_cos.data_ptr(), rope_sin.data_ptr(), kp.data_ptr(), vt.data_ptr(), out.data_ptr(), out.stride(0),
-            batch, heads, q_len, kv_len, kv_pad))
+    _call("vsys_flash_attn_d72_rope", _p(q), q.stride(0), _p(rope_cos), _p(rope_sin), _p(kp), _p(vt), _p(out), out.stride(0), batch, heads,
+          q_len, kv_len, kv_pad)
     return out
 
 
 # ------------------------------------------------------------------------------------------------ CausalVAE decode and sampler
-# (csrc/vae_osp.hip; no op codes, as their v1.2 siblings of open_sora_plan_ops.py: ctypes on torch's current stream, refused under a
-#  recorder — the decode is not part of a recorded step and the sampler step is launched by the host after each replay)
+# (csrc/vae_osp.hip; as their v1.2 siblings of open_sora_plan_ops.py: the upsampler is recordable, the sampler step refuses to run
+#  under a recorder, see there)
 def upsample_time2x(x, gs: VaeGrid, y, gd: VaeGrid, C, y_res=None, g_res: VaeGrid = None, alpha: float = 0.0):
     """TimeUpsample2x / TimeUpsampleRes2x up to its conv: x rows over gs -> the interior rows of gd ((1 if T == 1 else 2T - 1) frames of
     the same (H, W)); frame 0 copied, the later frames interpolated by (2, 1, 1) among themselves in fp32, one rounding.  ``y_res`` rows
     over ``g_res`` (same frames, H and W): bf16(alpha * v) from the same fp32 value (include/videosys_amd.h)."""
-    assert program.active() is None, "vsys_upsample_time2x has no op code"
     assert C % 8 == 0 and 0 < C <= 2048, f"C = {C}: a multiple of 8, at most 2048"
     assert (gd.n, gd.T, gd.H, gd.W) == (gs.n, 1 if gs.T == 1 else 2 * gs.T - 1, gs.H, gs.W), "grid_dst does not match grid_src"
     assert x.shape == (gs.rows, C) and y.shape == (gd.rows, C) and x.is_contiguous() and y.is_contiguous()
@@ -90,7 +86,9 @@ def cfg_pndm_step(model_out, model_in, z_out, guidance, c_base, cz, ca=None, bas
     ``cz`` / ``ca``: up to five host floats each (missing ones are 0)."""
     srcs = tuple(srcs) + (None,) * (4 - len(srcs))
     assert len(srcs) == 4, "at most four sources"
-    assert program.active() is None, "vsys_cfg_pndm_step has no op code: launch it after the replay"
+    # (the weights are per-call scalars in a host array and the source / output pointers rotate from call to call: a recorded copy
+    #  would replay the values and addresses of the call it was recorded on)
+    assert program.active() is None, "vsys_cfg_pndm_step: its scalars and pointers change every call, launch it after the replay"
     Bz, Cin = z_out.shape[:2]
     thw = z_out[0, 0].numel()
     assert model_out.dtype == torch.float32 and model_out.is_contiguous()

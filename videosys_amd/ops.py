@@ -40,8 +40,9 @@ def _stream():
 def _call(name: str, *args):
     """One C-ABI launch on torch's current stream (``args`` = the entry point's arguments without the trailing stream); under a
     launch-program recorder (program.py) the launch is also logged for replay.  Route: ``torch.ops.vsys.launch`` (the TORCH_LIBRARY
-    fragment of csrc/torch_binding.cpp: tensors travel as tensors) for every entry point that has a VSYS_OP code — the whole denoise
-    step — and ctypes for the rest (VAE, T5) or when the fragment is not there."""
+    fragment of csrc/torch_binding.cpp: tensors travel as tensors) for every entry point that has a VSYS_OP code, which is every
+    launch entry point that fits a vsys_cmd (all but vsys_attn_temporal_d64_img, 26 integer / pointer arguments against 24:
+    vchitect_ops.attn_temporal64_img issues that one itself); ctypes when the fragment is not there."""
     s = torch.cuda.current_stream()
     rec = program.active()
     sig = _lib.SIGNATURES[name][:-1]

@@ -1,7 +1,7 @@
 """Tensor-level wrappers of the entry points that exist for Vchitect-2.0 (include/videosys_amd.h: vsys_attn_temporal_d64,
 vsys_attn_temporal_d64_img, vsys_scale_add_rows of the transformer; vsys_vae_first_im2col_nc, vsys_pixels_to_u8 of the SD3 VAE decode), on the launch route of
-videosys_amd.ops (torch.ops.vsys.launch / ctypes, recorded by program.py; the two decode kernels have no op code and go through
-ctypes).  HIP device tensors only, no eager fallback.  Guard-band tests: tests/test_gpu_isolation_vchitect.py,
+videosys_amd.ops (torch.ops.vsys.launch / ctypes, recorded by program.py).  The one exception is vsys_attn_temporal_d64_img, whose 26
+integer / pointer arguments do not fit a vsys_cmd (24): see attn_temporal64_img.  HIP device tensors only, no eager fallback.  Guard-band tests: tests/test_gpu_isolation_vchitect.py,
 tests/test_gpu_isolation_vchitect_pipeline.py."""
 from __future__ import annotations
 
@@ -39,9 +39,10 @@ def attn_temporal64_img(q_vid, k_vid, v_vid, q_txt, k_txt, v_txt, rope_cos, rope
     heads*64] rows ordered (slab, b, t % Tl, s) with nslab >= ceil(T / Tl) (an image has one slab per rank, also for the ranks that
     hold only padded frames), *_txt likewise with L; frames past T are neither read nor written, and out_* is the image the return
     collective sends.  Same bits as attn_temporal64 on the un-imaged rows.
-    The entry point has no op code (the op table is pinned): the launch goes through ctypes on torch's current stream, and code
-    under a launch-program recorder issues it from a ``program.host_call`` closure (the collective's), never bare: ``defer=True`` checks
-    the arguments now and returns the closure that launches."""
+    The entry point takes 26 integer / pointer arguments and a vsys_cmd holds VSYS_CMD_MAX_INT = 24, so it is the one launch entry
+    point without an op code (csrc/gen/program_gen.py NO_OP): the launch goes through ctypes on torch's current stream, and code
+    under a launch-program recorder issues it from a ``program.host_call`` closure (the collective's, dsp.all_to_all_single(before=)),
+    never bare: ``defer=True`` checks the arguments now and returns the closure that launches."""
     ts = (q_vid, k_vid, v_vid, q_txt, k_txt, v_txt, out_vid, out_txt)
     _chk(*ts, rope_cos, rope_sin)
     _bf16(*ts)
@@ -66,7 +67,7 @@ def attn_temporal64_img(q_vid, k_vid, v_vid, q_txt, k_txt, v_txt, rope_cos, rope
 
     if defer:
         return issue
-    assert program.active() is None, "vsys_attn_temporal_d64_img has no op code: under a recorder issue it from a host_call closure (defer=True)"
+    assert program.active() is None, "vsys_attn_temporal_d64_img does not fit a vsys_cmd: under a recorder issue it from a host_call closure (defer=True)"
     issue()
     return out_vid, out_txt
 
