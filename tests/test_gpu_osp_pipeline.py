@@ -147,7 +147,7 @@ def test_replayed_steps_equal_eager_steps_bit_for_bit():
     pipe = pipeline()
     e = embeds(pipe, ["a red fox runs over the snow"])
     z0 = start()
-    pipe._programs, pipe._step_bufs = {}, None
+    pipe._steps.entries, pipe._step_bufs = {}, None
     pipe.step_stats = {"recorded": 0, "replayed": 0, "eager": 0}
     a = hip_latents(pipe, e, z0).video.clone()
     assert pipe.step_stats == {"recorded": 1, "replayed": STEPS - 1, "eager": 0}
@@ -162,12 +162,37 @@ def test_replayed_steps_equal_eager_steps_bit_for_bit():
     # the recorded step is ONE command array: the d96 attention launches are commands of it, and nothing is a host action
     from videosys_amd._opcodes import OPCODES
 
-    (prog, _), = pipe._programs.values()
+    (prog, _), = pipe._steps.entries.values()
     assert len(prog.segments) == 1 and isinstance(prog.segments[0], tuple), "a recorded single-rank step holds a host action"
     ops = [c.op for c in prog.segments[0][0]]
     layers = TCFG["num_layers"]
     assert len(ops) == prog.n_launches and ops.count(OPCODES["vsys_attn_prep_kv96"]) >= layers
     assert ops.count(OPCODES["vsys_flash_attn_d96"]) == 2 * layers                                  # self- and cross-attention
+
+
+def test_new_prompt_of_the_same_shape_keeps_the_recorded_step():
+    """The rule of ``_buffers`` (program.StepCache's table): a prompt of the shape of the last one is copied into the resident text
+    buffers and its K / V are refilled in place, so the recorded step stays valid.  Expected from the rule: the first generate()
+    records its first step and replays STEPS - 1, the two after it replay every step; nothing is recorded again and nothing runs
+    eagerly.  Every output equals what a freshly built pipeline gives for that prompt."""
+    from videosys_amd.pipeline_open_sora_plan import OpenSoraPlanPipeline
+
+    pipe = pipeline()
+    ea, eb = embeds(pipe, ["a red fox runs over the snow"]), embeds(pipe, ["two boats leave the harbour at dawn"])
+    assert all(a.shape == b.shape for a, b in zip(ea, eb)) and not torch.equal(ea[0], eb[0])
+    z0 = start()
+    fresh = lambda: OpenSoraPlanPipeline(config(), text_encoder=pipe.text_encoder, device=dev())
+    want = {"a": hip_latents(fresh(), ea, z0).video.clone(), "b": hip_latents(fresh(), eb, z0).video.clone()}
+    assert not torch.equal(want["a"], want["b"])
+    pipe._steps.entries, pipe._step_bufs = {}, None
+    expect = [{"recorded": 1, "replayed": STEPS - 1, "eager": 0}, {"recorded": 0, "replayed": STEPS, "eager": 0},
+              {"recorded": 0, "replayed": STEPS, "eager": 0}]
+    for (name, e), exp in zip((("a", ea), ("b", eb), ("a", ea)), expect):
+        before = dict(pipe.step_stats)
+        got = hip_latents(pipe, e, z0).video.clone()
+        delta = {k: pipe.step_stats[k] - before[k] for k in before}
+        assert delta == exp, (name, delta)
+        assert len(pipe._steps) == 1 and torch.equal(got, want[name]), f"prompt {name}: not the fresh pipeline's latents"
 
 
 def test_pab_decision_sequence_and_programs():

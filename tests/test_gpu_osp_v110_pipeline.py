@@ -116,14 +116,14 @@ def test_latents_within_the_bf16_floor_and_replay_equals_eager(fx, embeds):
     z0 = start()
     pipe = pipeline(fx)
     pipe.step_stats = {"recorded": 0, "replayed": 0, "eager": 0}
-    pipe._programs = {}
+    pipe._steps.entries = {}
     out = run(pipe, pe, ne, z0)
     assert pipe.step_stats == {"recorded": 1, "replayed": STEPS + 8, "eager": 0}, pipe.step_stats
     # the recorded step holds no text path: as many launches as a recording made while the text K / V are resident, and fewer than one
     # made with the transformer's text cache cold (caption projection + a K / V GEMM and a prep launch per layer)
     from videosys_amd import program
 
-    (prog, _), = pipe._programs.values()
+    (prog, _), = pipe._steps.entries.values()
     bufs, ts = pipe._step_bufs, pipe.scheduler.timesteps
 
     def recorded_launches():
@@ -138,7 +138,7 @@ def test_latents_within_the_bf16_floor_and_replay_equals_eager(fx, embeds):
     layers = tcfg(fx)["num_layers"]
     print(f"recorded launches: program {prog.n_launches}, text resident {warm}, text cache cold {cold}")
     assert prog.n_launches == warm and cold >= warm + 2 * layers
-    pipe._programs = {}                                  # (the cold recording made new text K / V: record again on the next call)
+    pipe._steps.entries = {}                                  # (the cold recording made new text K / V: record again on the next call)
     out2 = run(pipe, pe, ne, z0)
     assert torch.equal(out, out2)
     pipe.step_stats = {"recorded": 1, "replayed": STEPS + 8, "eager": 0}
@@ -154,7 +154,7 @@ def test_latents_within_the_bf16_floor_and_replay_equals_eager(fx, embeds):
     # the recorded call is ONE command array: the roped d72 attention launches are commands of it, and nothing is a host action
     from videosys_amd._opcodes import OPCODES
 
-    (prog, _), = pipe._programs.values()
+    (prog, _), = pipe._steps.entries.values()
     assert len(prog.segments) == 1 and isinstance(prog.segments[0], tuple), "a recorded single-rank call holds a host action"
     ops = [c.op for c in prog.segments[0][0]]
     assert len(ops) == prog.n_launches
@@ -165,6 +165,30 @@ def test_latents_within_the_bf16_floor_and_replay_equals_eager(fx, embeds):
     print(f"latents after {STEPS + 9} calls: HIP rms error {err:.4e}, bf16 floor {floor:.4e} (ratio {err / floor:.3f}), rms {rms(f64, 0 * f64):.3f}")
     assert tuple(out.shape) == ZSHAPE and floor < 0.05 * rms(f64, 0 * f64), "the floor is vacuous"
     assert err <= 1.5 * floor
+
+
+def test_new_prompt_of_the_same_shape_drops_the_recorded_call(fx, embeds):
+    """The rule of ``_buffers`` (program.StepCache's table): the recorded call reads the text K / V that ``_prepare_text`` made for
+    one text, and another text gets new ones, so the call is recorded again — also when the first prompt comes back.  Expected from
+    the rule, per generate() of STEPS + 9 calls: 1 recorded (the first call) + STEPS + 8 replayed, three times over; nothing eager.
+    Every output equals what a freshly built pipeline gives for that prompt."""
+    from videosys_amd.pipeline_open_sora_plan_v110 import OpenSoraPlanV110Pipeline
+
+    pipe = pipeline(fx)
+    pb, nb = (t.float().cpu() for t in pipe.encode_prompt("a large red ship on a lake", True, negative_prompt=""))
+    ea, eb = embeds, (pb, nb)
+    assert eb[0].shape == ea[0].shape and eb[1].shape == ea[1].shape and not torch.equal(eb[0], ea[0])
+    z0 = start()
+    fresh = lambda: OpenSoraPlanV110Pipeline(config(fx), text_encoder=pipe.text_encoder, device=dev())
+    want = {"a": run(fresh(), *ea, z0), "b": run(fresh(), *eb, z0)}
+    assert not torch.equal(want["a"], want["b"])
+    pipe._steps.entries, pipe._step_bufs = {}, None
+    for name, e in (("a", ea), ("b", eb), ("a", ea)):
+        before = dict(pipe.step_stats)
+        got = run(pipe, *e, z0)
+        delta = {k: pipe.step_stats[k] - before[k] for k in before}
+        assert delta == {"recorded": 1, "replayed": STEPS + 8, "eager": 0}, (name, delta)
+        assert len(pipe._steps) == 1 and torch.equal(got, want[name]), f"prompt {name}: not the fresh pipeline's latents"
 
 
 def test_callbacks_follow_the_reference_rule(fx, embeds):

@@ -142,7 +142,7 @@ def test_replayed_steps_equal_eager_steps_bit_for_bit():
 
     pipe = pipeline()
     pab.set_pab_manager(None)
-    pipe._step_program = None
+    pipe._steps.entries = {}
     before = dict(pipe.step_stats)
     _, seen = run(pipe, 2, 3, output_type="latent")
     assert pipe.step_stats["recorded"] - before["recorded"] == 1 and pipe.step_stats["replayed"] - before["replayed"] == 2
@@ -168,6 +168,40 @@ def test_replayed_steps_equal_eager_steps_bit_for_bit():
     out = pipe.generate(height=8 * HW, width=8 * HW, frames=2, num_inference_steps=3, guidance_scale=GS, seed=0, latents=z0,
                         output_type="latent", callback_on_step_end=stop, **emb).video
     assert calls == [0] and pipe.interrupt and torch.equal(out, seen[0][2])
+
+
+def test_new_embeddings_of_the_same_shape_drop_the_recorded_pair():
+    """The rule of ``_step_buffers`` (program.StepCache's table): a recorded pair holds the addresses of its resident buffers, and
+    embeddings that differ get new buffers, so the pair is recorded again — also when the first embeddings come back.  Expected from
+    the rule, per generate() of 3 steps: 1 recorded (the first step) + 2 replayed, three times over; nothing eager.  Every output
+    equals what a freshly built pipeline gives for those embeddings."""
+    from videosys_amd import VchitectXLPipeline, pab
+
+    pipe = pipeline()
+    pab.set_pab_manager(None)
+    emb_a, z0 = inputs(2)
+    emb_b = {k: v.flip(-1).contiguous() for k, v in emb_a.items()}
+    assert all(emb_b[k].shape == emb_a[k].shape and not torch.equal(emb_b[k], emb_a[k]) for k in emb_a)
+
+    def latents(p, emb):
+        out = p.generate(height=8 * HW, width=8 * HW, frames=2, num_inference_steps=3, guidance_scale=GS, seed=0, latents=z0,
+                         output_type="latent", **emb).video.clone()
+        torch.cuda.synchronize()
+        return out
+
+    def fresh():
+        return VchitectXLPipeline(config(), text_encoder=pipe.text_encoder, text_encoder_2=pipe.text_encoder_2,
+                                  text_encoder_3=pipe.text_encoder_3, tokenizer=pipe.tokenizer, tokenizer_2=pipe.tokenizer_2)
+
+    want = {"a": latents(fresh(), emb_a), "b": latents(fresh(), emb_b)}
+    assert not torch.equal(want["a"], want["b"])
+    pipe._steps.entries = {}
+    for name, emb in (("a", emb_a), ("b", emb_b), ("a", emb_a)):
+        before = dict(pipe.step_stats)
+        got = latents(pipe, emb)
+        delta = {k: pipe.step_stats[k] - before[k] for k in before}
+        assert delta == {"recorded": 1, "replayed": 2, "eager": 0}, (name, delta)
+        assert len(pipe._steps) == 1 and torch.equal(got, want[name]), f"embeddings {name}: not the fresh pipeline's latents"
 
 
 def test_pab_decisions_of_the_eight_calls():

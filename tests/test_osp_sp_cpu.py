@@ -218,15 +218,17 @@ def test_pipeline_num_gpus_must_be_the_world_size():
 def test_set_parallel_drops_the_recorded_programs():
     from tools.local_group import StubGroup
     from videosys_amd.pipeline_open_sora_plan import OpenSoraPlanPipeline
+    from videosys_amd.program import StepCache
 
     p = OpenSoraPlanPipeline.__new__(OpenSoraPlanPipeline)
     p.transformer = small_model(heads=8)
-    p._programs = {"recorded under one rank": object()}
+    p._steps = StepCache()
+    p._steps.entries = {"recorded under one rank": object()}
     p._set_parallel(parallel_mgr=manager(StubGroup(2, 0), 2))
-    assert p._programs == {} and p.transformer._sp is not None and p.transformer._sp.P == 2
-    p._programs = {"recorded under two ranks": object()}
+    assert p._steps.entries == {} and p.transformer._sp is not None and p.transformer._sp.P == 2
+    p._steps.entries = {"recorded under two ranks": object()}
     p._set_parallel()                                      # the process group of this process: one rank
-    assert p._programs == {} and p.transformer._sp is None
+    assert p._steps.entries == {} and p.transformer._sp is None
 
 
 # ------------------------------------------------------------------------------------------------ C ABI of the image entry points

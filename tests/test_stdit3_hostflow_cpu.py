@@ -245,7 +245,7 @@ def test_step_launch_counts_and_program_replay():
         m(x, t, y, **kw)
         assert m.program_stats["eager"] == 1
         m.reset_text_cache()
-        assert not m._programs
+        assert not m._steps.entries
         # two samples at different timesteps have different modulations: the fold is off for that call (own program key),
         # and VSYS_ADALN_FOLD=0 (model.adaln_fold) keeps the separate LayerNorm-modulate pass everywhere
         m.use_programs = True

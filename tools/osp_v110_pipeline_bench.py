@@ -194,7 +194,7 @@ def main():
         for hbuf in b["hist"]:
             hbuf.normal_()
         model_only()                                     # records (the text K / V are made resident first, outside the recording)
-        res["recorded_launches"] = next(iter(pipe._programs.values()))[0].n_launches
+        res["recorded_launches"] = next(iter(pipe._steps.entries.values()))[0].n_launches
         # the yardstick of tools/osp_v110_bench.py on the SAME model in the SAME run: the bare transformer call, recorded after one eager
         # call and replayed — what profiles/osp_v110_timing.json holds from another run
         from videosys_amd import program

@@ -137,13 +137,13 @@ def ranks_main(args):
                 tr._sp.p2p = None
             for b in tr.transformer_blocks:
                 b.attn.attn_route = "image" if name == "image" else "rows"
-        pipe._step_program = None
+        pipe._steps.clear()
         step()                                  # records the pair of model calls
         step()                                  # first replay
         torch.cuda.synchronize()
-        programs[name] = pipe._step_program
-        prog = pipe._step_program[1]
-        assert prog is not None, f"the {name} step was not recordable"
+        programs[name] = pipe._steps.entries    # (clear() starts a new table: this one keeps its program)
+        assert len(pipe._steps) == 1, f"the {name} step was not recordable"
+        (prog, _), = pipe._steps.entries.values()
         # launches: the recorded ones + the guidance / Euler launch + what host actions launch themselves (the image route's attention,
         # one per block and model call, has no op code and is issued by the closure of the collective it feeds)
         closure_launches = 2 * len(tr.transformer_blocks) if name == "image" else 0
@@ -153,7 +153,7 @@ def ranks_main(args):
     times = {name: [] for name in programs}
     for _ in range(reps):                       # the routes in turn, so that drift hits them alike
         for name, ent in programs.items():
-            pipe._step_program = ent
+            pipe._steps.entries = ent
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             step()

@@ -6,6 +6,7 @@ tables — so the base here holds only what the reference class itself adds (pip
 ``__call__`` forwarding to it, ``set_eval_and_device``; plus the staged cpu_offload and seeding shared by the three pipelines."""
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass, fields
 
 import torch
@@ -49,6 +50,36 @@ class VideoSysPipeline(StagedOffloadMixin):
         if not callable(getattr(scheduler, needs, None)):
             raise TypeError(f"scheduler: expected {what} (it has no `{needs}`): got {type(scheduler).__name__}")
         return scheduler
+
+    @staticmethod
+    def _world_size() -> int:
+        import torch.distributed as dist
+
+        return dist.get_world_size() if dist.is_initialized() else 1
+
+    @classmethod
+    def _parallel_sizes(cls, sp_size):
+        """(dp, sp) of the reference's ``_set_parallel``s: sp = the world size unless given, then dp = world / sp."""
+        world = cls._world_size()
+        if sp_size is None:
+            return 1, world
+        assert world % sp_size == 0, f"world_size {world} must be divisible by sp_size"
+        return world // sp_size, sp_size
+
+    def _decode_group(self):
+        """The ranks that share one video's VAE decode: the sequence-parallel group of the transformer (every one of its ranks holds
+        the same final latents), None on one GPU, with ``shard_vae_decode=False`` or with ``VSYS_VAE_SHARD=0``."""
+        if not getattr(self._config, "shard_vae_decode", True) or os.environ.get("VSYS_VAE_SHARD") == "0":
+            return None
+        sp = getattr(self.transformer, "_sp", None)
+        if sp is not None and sp.P > 1:
+            return sp.group
+        return None
+
+    def _leave(self, video, return_dict: bool):
+        """The end of every generate(): the last offload stage is left, the result goes back as the reference hands it back."""
+        self._enter_stage(None)
+        return VideoSysPipelineOutput(video=video) if return_dict else (video,)
 
     def generate(self, *args, **kwargs):   # pipeline.py:21-23 (abstract there)
         raise NotImplementedError(f"{type(self).__name__} does not define generate()")
@@ -119,8 +150,6 @@ def build_text_encoder(spec, tokenizer=None, *, device, caption_channels: int = 
                                      is None, ``AutoTokenizer.from_pretrained(tokenizer_path or the directory)``
       * a torch module (HF ``T5EncoderModel``) -> its weights on the MI355X encoder, with ``tokenizer``
     A hub id cannot be fetched on an offline box: None."""
-    import os
-
     from .t5 import ByteTokenizer, T5Encoder, T5TextEncoder
 
     if spec is None:
@@ -173,8 +202,6 @@ def build_clip_encoder(spec, tokenizer=None, *, device, geometry: dict, tokenize
                                      that is None and ``tokenizer_path`` is a directory, ``CLIPTokenizer.from_pretrained`` of it
       * a torch module (HF ``CLIPTextModelWithProjection``) -> its weights on the MI355X encoder (the module itself never runs)
       * any other callable        -> itself (an injected encoder)."""
-    import os
-
     from .clip import CLIPTextEncoder, ClipByteTokenizer
 
     if spec is None or isinstance(spec, CLIPTextEncoder):

@@ -268,17 +268,8 @@ class CogVideoXPipeline(VideoSysPipeline):
 
     def _set_parallel(self, dp_size: Optional[int] = None, sp_size: Optional[int] = None, enable_cp: Optional[bool] = False):
         """pipeline_cogvideox.py:195-209: sp = world size unless given (then dp = world / sp)."""
-        import torch.distributed as dist
-
-        world = dist.get_world_size() if dist.is_initialized() else 1
-        if world == 1:
-            return
-        if sp_size is None:
-            sp_size, dp_size = world, 1
-        else:
-            assert world % sp_size == 0, f"world_size {world} must be divisible by sp_size"
-            dp_size = world // sp_size
-        self.transformer.enable_parallel(dp_size, sp_size, enable_cp)
+        if self._world_size() > 1:
+            self.transformer.enable_parallel(*self._parallel_sizes(sp_size), enable_cp)
 
     def _prepare_rotary_positional_embeddings(self, height: int, width: int, num_frames: int):
         """pipeline_cogvideox.py:449-474."""
@@ -474,8 +465,7 @@ class CogVideoXPipeline(VideoSysPipeline):
                 negative_prompt_embeds = back.get("negative_prompt_embeds", negative_prompt_embeds)
         _dsp.check_exchange(self.transformer)   # a timed-out peer-to-peer exchange left stale rows: raise here, not a corrupt video
         if self.vae_decoder is None or output_type in ("latent", "latents"):
-            self._enter_stage(None)
-            return VideoSysPipelineOutput(video=z) if return_dict else (z,)
+            return self._leave(z, return_dict)
         self._enter_stage("vae")
         frames = self.decode_latents(z)   # (:359-364) -> [B, 3, T, H, W]
         self._enter_stage(None)

@@ -183,17 +183,8 @@ class LattePipeline(VideoSysPipeline):
 
     def _set_parallel(self, dp_size: Optional[int] = None, sp_size: Optional[int] = None, enable_cp: Optional[bool] = False):
         """pipeline_latte.py:236-250: sp = world size unless given (then dp = world / sp)."""
-        import torch.distributed as dist
-
-        world = dist.get_world_size() if dist.is_initialized() else 1
-        if world == 1:
-            return
-        if sp_size is None:
-            sp_size, dp_size = world, 1
-        else:
-            assert world % sp_size == 0, f"world_size {world} must be divisible by sp_size"
-            dp_size = world // sp_size
-        self.transformer.enable_parallel(dp_size, sp_size, enable_cp)
+        if self._world_size() > 1:
+            self.transformer.enable_parallel(*self._parallel_sizes(sp_size), enable_cp)
 
     def _text_preprocessing(self, text, clean_caption: bool = False):
         """pipeline_latte.py:519-531: a string or a list of strings -> a list; the IF caption cleaner twice, or lower + strip."""
@@ -355,13 +346,11 @@ class LattePipeline(VideoSysPipeline):
                 callback(step_i, t, z)
         _dsp.check_exchange(self.transformer)   # a timed-out peer-to-peer exchange left stale rows: raise here, not a corrupt video
         if self.vae_decoder is None or output_type in ("latent", "latents"):
-            self._enter_stage(None)
-            return VideoSysPipelineOutput(video=z) if return_dict else (z,)
+            return self._leave(z, return_dict)
         self._enter_stage("vae")
         # (:884-891) one frame: float image frames; else uint8 video through the decoder the config chose
         video = self.decode_latents_image(z) if z.shape[2] == 1 and hasattr(self.vae_decoder, "decode") else self.decode_latents(z)
-        self._enter_stage(None)
-        return VideoSysPipelineOutput(video=video) if return_dict else (video,)
+        return self._leave(video, return_dict)
 
     def save_video(self, video, output_path):
         from .utils import save_video

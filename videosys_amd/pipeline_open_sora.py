@@ -203,21 +203,9 @@ class OpenSoraPipeline(VideoSysPipeline):
 
     def _set_parallel(self, dp_size: Optional[int] = None, sp_size: Optional[int] = None, enable_cp: bool = False):
         """pipeline_open_sora.py:253-267: dp=1, sp=world."""
-        import torch.distributed as dist
-
-        world = dist.get_world_size() if dist.is_initialized() else 1
+        world = self._world_size()
         if world > 1:
             self.transformer.enable_parallel(dp_size or 1, sp_size or world, enable_cp)
-
-    def _decode_group(self):
-        """The ranks that share one video's VAE decode: the sequence-parallel group of the transformer (every one of its ranks holds
-        the same final latents), None on one GPU or with ``shard_vae_decode=False``."""
-        if not getattr(self._config, "shard_vae_decode", True) or os.environ.get("VSYS_VAE_SHARD") == "0":
-            return None
-        sp = getattr(self.transformer, "_sp", None)
-        if sp is not None and sp.P > 1:
-            return sp.group
-        return None
 
     def null(self, n):
         """pipeline_open_sora.py:294-296."""
@@ -383,8 +371,7 @@ class OpenSoraPipeline(VideoSysPipeline):
             if grp is not None and hasattr(vae, "decode_sharded"):
                 # one video over N GPUs: every rank decodes its block of output frames, one all-gather of uint8 frames
                 video = vae.decode_sharded(samples.to(torch.bfloat16), num_frames, grp, to_uint8=True).to("cpu")
-                self._enter_stage(None)
-                return VideoSysPipelineOutput(video=video) if return_dict else (video,)
+                return self._leave(video, return_dict)
             clips.append(vae(samples.to(torch.bfloat16), num_frames=num_frames))
         self._enter_stage(None)
         if not clips:

@@ -228,15 +228,15 @@ class OpenSoraPlanPipeline(VideoSysPipeline):
             text_encoder = config.text_encoder
         self.text_encoder = self._build_text_encoder(text_encoder, tokenizer)
         pab.set_pab_manager(config.pab_config if config.enable_pab else None)
-        self._programs = {}                 # (geometry, text shape, PAB pattern) -> (Program, pred)
+        self._steps = program.StepCache()   # (geometry, text shape, PAB pattern) -> (Program, pred)
         self._step_bufs = None
-        self.step_stats = {"recorded": 0, "replayed": 0, "eager": 0}
         self.pab_trace: List[list] = []     # PAB on: per step of the last generate(), every block's (spatial, cross) decision
         self._set_parallel()
         self._init_stages(config.cpu_offload, self._device, text_encoder=getattr(self.text_encoder, "encoder", None),
                           transformer=self.transformer, vae=getattr(self.vae, "vae", None))
 
     tokenizer = property(lambda self: getattr(self.text_encoder, "tokenizer", None))
+    step_stats = program.stats_property("_steps")
 
     TEXT_VOCAB, TEXT_MAX_LENGTH = MT5_VOCAB, 512          # (the v1.1 pipeline: T5 v1.1's vocabulary, 300 tokens)
 
@@ -285,18 +285,10 @@ class OpenSoraPlanPipeline(VideoSysPipeline):
         model gathering it inside); the text encoder stays replicated, the tiled CausalVAE decode is shared over the same group
         (``_decode_group``).  ``parallel_mgr`` (an extension): an injected manager instead of the process group, as the transformer
         takes it."""
-        import torch.distributed as dist
-
-        self._programs = {}                # a recorded step belongs to the sharding it was recorded under
+        self._steps.clear()                # a recorded step belongs to the sharding it was recorded under
         if parallel_mgr is not None:
             return self.transformer.enable_parallel(parallel_mgr=parallel_mgr)
-        world = dist.get_world_size() if dist.is_initialized() else 1
-        if sp_size is None:
-            sp_size, dp_size = world, 1
-        else:
-            assert world % sp_size == 0, f"world_size {world} must be divisible by sp_size"
-            dp_size = world // sp_size
-        self.transformer.enable_parallel(dp_size, sp_size, enable_cp)
+        self.transformer.enable_parallel(*self._parallel_sizes(sp_size), enable_cp)    # (at one rank too)
 
     # ------------------------------------------------------------------------------------------------ text side
     def mask_text_embeddings(self, emb, mask):
@@ -436,28 +428,16 @@ class OpenSoraPlanPipeline(VideoSysPipeline):
         if use_pab:
             self.pab_trace.append([(s[0], c[0]) for s, c in plan])
         if not getattr(tr, "use_programs", True):
-            self.step_stats["eager"] += 1
-            return self._model(xin, t, enc, mask)
+            return self._steps.eager(lambda: self._model(xin, t, enc, mask))
         key = (tuple(xin.shape), tuple(enc.shape), None if plan is None else tuple((s[0], c[0]) for s, c in plan))
-        ent = self._programs.get(key)
-        if ent is not None:
-            prog, pred = ent
+
+        def refresh(pred):
             tr.step_timesteps(xin.shape[0]).fill_(float(t))       # the one per-step input besides the latents
             if plan is not None:                                   # the counters the eager call would have left
                 for st, (s, c) in zip(tr.states, plan):
                     st.attn_count, st.cross_count = s[1], c[1]
-            prog.run()
-            self.step_stats["replayed"] += 1
-            return pred
-        with program.Recorder() as rec:
-            pred = self._model(xin, t, enc, mask)
-        prog = rec.finish()
-        if prog is not None:
-            self._programs[key] = (prog, pred)
-            self.step_stats["recorded"] += 1
-        else:
-            self.step_stats["eager"] += 1
-        return pred
+
+        return self._steps.run(key, lambda: self._model(xin, t, enc, mask), refresh)
 
     def _buffers(self, z0, enc, mask):
         """Resident inputs of a step — latents z fp32 [B, C, T, h, w], the model input as the step kernel leaves it (bf16 [2B, ...])
@@ -469,7 +449,7 @@ class OpenSoraPlanPipeline(VideoSysPipeline):
             b["enc"].copy_(enc)
             b["mask"].copy_(mask)
             return b
-        self._programs = {}
+        self._steps.clear()
         z = z0.to(device=self._device, dtype=torch.float32).contiguous().clone()
         two = (2 * z.shape[0],) + tuple(z.shape[1:])
         self._step_bufs = dict(z=z, model_in=torch.empty(two, dtype=torch.bfloat16, device=self._device),
@@ -551,23 +531,9 @@ class OpenSoraPlanPipeline(VideoSysPipeline):
                 callback(i, t, z)
         dsp.check_exchange(self.transformer)     # a timed-out peer-to-peer exchange raises here, before anything is decoded
         if self.vae is None or output_type in ("latent", "latents"):
-            self._enter_stage(None)
-            out = z.clone()
-            return VideoSysPipelineOutput(video=out) if return_dict else (out,)
+            return self._leave(z.clone(), return_dict)
         self._enter_stage("vae")
-        video = self.decode_latents(z)[:, :num_frames, :height, :width]
-        self._enter_stage(None)
-        return VideoSysPipelineOutput(video=video) if return_dict else (video,)
-
-    def _decode_group(self):
-        """The ranks that share one video's VAE decode: the sequence-parallel group of the transformer (every one of its ranks holds
-        the same final latents), None on one GPU, with ``shard_vae_decode=False`` or with ``VSYS_VAE_SHARD=0``."""
-        if not getattr(self._config, "shard_vae_decode", True) or os.environ.get("VSYS_VAE_SHARD") == "0":
-            return None
-        sp = getattr(self.transformer, "_sp", None)
-        if sp is not None and sp.P > 1:
-            return sp.group
-        return None
+        return self._leave(self.decode_latents(z)[:, :num_frames, :height, :width], return_dict)
 
     def decode_latents(self, latents):
         """:1184-1190: the VAE on the bf16 latents, then ``((video / 2 + 0.5).clamp(0, 1) * 255).to(uint8)`` on the bf16 tensor

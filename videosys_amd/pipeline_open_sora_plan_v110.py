@@ -285,9 +285,8 @@ class OpenSoraPlanV110Pipeline(OpenSoraPlanPipeline):
             text_encoder = config.text_encoder
         self.text_encoder = self._build_text_encoder(text_encoder, tokenizer)      # T5 v1.1 at 300 tokens (TEXT_VOCAB, TEXT_MAX_LENGTH)
         pab.set_pab_manager(config.pab_config if config.enable_pab else None)
-        self._programs = {}                 # (geometry, text length) -> (Program, pred)
+        self._steps = program.StepCache()   # (geometry, text length) -> (Program, pred)
         self._step_bufs = None
-        self.step_stats = {"recorded": 0, "replayed": 0, "eager": 0}
         self.pab_trace: List[list] = []     # PAB on: per model call of the last generate(), every block's (attention, cross, mlp) decision
         self._set_parallel()
         self._init_stages(config.cpu_offload, self._device, text_encoder=getattr(self.text_encoder, "encoder", None),
@@ -313,7 +312,7 @@ class OpenSoraPlanV110Pipeline(OpenSoraPlanPipeline):
     def _set_parallel(self, dp_size: Optional[int] = None, sp_size: Optional[int] = None, enable_cp: Optional[bool] = False,
                       parallel_mgr=None):
         """:349-363 on one rank: the transformer refuses more (open_sora_plan_v110.LatteT2V.enable_parallel)."""
-        self._programs = {}
+        self._steps.clear()
         self.transformer.enable_parallel(dp_size or 1, sp_size or 1, enable_cp, parallel_mgr=parallel_mgr)
 
     def _decode_group(self):
@@ -401,26 +400,12 @@ class OpenSoraPlanV110Pipeline(OpenSoraPlanPipeline):
         if pab.enable_pab():
             self.pab_trace.append(self._pab_pattern(int(t), all_ts))
         if pab.enable_pab() or not temporal or not getattr(tr, "use_programs", True):
-            self.step_stats["eager"] += 1
-            return self._model(xin, t, enc, all_ts, temporal)
+            return self._steps.eager(lambda: self._model(xin, t, enc, all_ts, temporal))
         key = (tuple(xin.shape), tuple(enc.shape))
-        ent = self._programs.get(key)
-        if ent is not None:
-            prog, pred = ent
-            tr.step_timesteps(xin.shape[0]).fill_(float(t))       # the one per-step input besides the latents
-            prog.run()
-            self.step_stats["replayed"] += 1
-            return pred
-        self._prepare_text(enc)                                   # outside the recording
-        with program.Recorder() as rec:
-            pred = self._model(xin, t, enc, all_ts)
-        prog = rec.finish()
-        if prog is not None:
-            self._programs[key] = (prog, pred)
-            self.step_stats["recorded"] += 1
-        else:
-            self.step_stats["eager"] += 1
-        return pred
+        if key not in self._steps:
+            self._prepare_text(enc)                               # outside the recording
+        # (on a hit) the one per-step input besides the latents
+        return self._steps.run(key, lambda: self._model(xin, t, enc, all_ts), lambda pred: tr.step_timesteps(xin.shape[0]).fill_(float(t)))
 
     def _buffers(self, z0, enc):
         """Resident operands of a call — the two fp32 latent buffers the warm-up ping-pongs between, the ring of four history slots,
@@ -431,11 +416,11 @@ class OpenSoraPlanV110Pipeline(OpenSoraPlanPipeline):
         b = self._step_bufs
         if b is not None and b["z"][0].shape == z0.shape and b["enc"].shape == enc.shape:
             if not torch.equal(b["enc"], enc):
-                self._programs = {}
+                self._steps.clear()
                 b["enc"].copy_(enc)
             b["z"][0].copy_(z0)
             return b
-        self._programs = {}
+        self._steps.clear()
         z = z0.to(device=self._device, dtype=torch.float32).contiguous().clone()
         new = lambda: torch.empty_like(z)
         two = (2 * z.shape[0],) + tuple(z.shape[1:])
@@ -520,10 +505,6 @@ class OpenSoraPlanV110Pipeline(OpenSoraPlanPipeline):
         b["z"] = [cur, other]
         dsp.check_exchange(self.transformer)
         if self.vae is None or output_type in ("latent", "latents"):
-            self._enter_stage(None)
-            out = cur.clone()
-            return VideoSysPipelineOutput(video=out) if return_dict else (out,)
+            return self._leave(cur.clone(), return_dict)
         self._enter_stage("vae")
-        video = self.decode_latents(cur)[:, :num_frames, :height, :width]
-        self._enter_stage(None)
-        return VideoSysPipelineOutput(video=video) if return_dict else (video,)
+        return self._leave(self.decode_latents(cur)[:, :num_frames, :height, :width], return_dict)

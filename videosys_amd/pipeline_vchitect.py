@@ -238,8 +238,7 @@ class VchitectXLPipeline(VideoSysPipeline):
         self.vae_scale_factor = 2 ** (len(self.vae.config.block_out_channels) - 1) if self.vae is not None else 8
         self.tokenizer_max_length = getattr(self.tokenizer, "model_max_length", 77) if self.tokenizer is not None else 77
         self.default_sample_size = self.transformer.config.sample_size
-        self._step_program = None      # (key, Program, z, enc, pooled, pred) of the recorded pair of model calls
-        self.step_stats = {"recorded": 0, "replayed": 0, "eager": 0}
+        self._steps = program.StepCache()   # (latent shape, text shape) -> (Program, (z, enc, pooled, pred)): one entry at a time
         self.pab_trace: List[list] = []   # PAB on: per model call of the last generate(), every block's (temporal, cross, spatial)
         self._set_parallel()
         own_clip = lambda e: e if isinstance(e, CLIPTextEncoder) else None   # (injected objects look after their own weights)
@@ -249,6 +248,7 @@ class VchitectXLPipeline(VideoSysPipeline):
 
     tokenizer_3 = property(lambda self: getattr(self.text_encoder_3, "tokenizer", None))
     vae_decoder = property(lambda self: self.vae)
+    step_stats = program.stats_property("_steps")
 
     def _clip_geometry(self, slot: str) -> dict:
         """Constructor keywords of the ``"synthetic:<seed>"`` encoder of ``slot``: CLIP-L for ``text_encoder``, CLIP-bigG for
@@ -284,20 +284,11 @@ class VchitectXLPipeline(VideoSysPipeline):
         calls generate() with the same seed and gets the same frames, the model gathering its prediction inside); the text encoders
         stay replicated, the VAE decode is shared over the same group by frames (``_decode_group``).  ``parallel_mgr`` (an
         extension): an injected manager instead of the process group, as the transformers take it."""
-        import torch.distributed as dist
-
-        self._step_program = None          # a recorded step belongs to the sharding it was recorded under
+        self._steps.clear()                # a recorded step belongs to the sharding it was recorded under
         if parallel_mgr is not None:
             return self.transformer.enable_parallel(parallel_mgr=parallel_mgr)
-        world = dist.get_world_size() if dist.is_initialized() else 1
-        if world == 1:
-            return
-        if sp_size is None:
-            sp_size, dp_size = world, 1
-        else:
-            assert world % sp_size == 0, f"world_size {world} must be divisible by sp_size"
-            dp_size = world // sp_size
-        self.transformer.enable_parallel(dp_size, sp_size, enable_cp)
+        if self._world_size() > 1:
+            self.transformer.enable_parallel(*self._parallel_sizes(sp_size), enable_cp)
 
     # ------------------------------------------------------------------------------------------------ text side
     def _get_t5_prompt_embeds(self, prompt: Union[str, List[str]] = None, num_images_per_prompt: int = 1, device=None, dtype=None):
@@ -472,33 +463,32 @@ class VchitectXLPipeline(VideoSysPipeline):
         program recorded at the first step of this (geometry, embeddings)."""
         tr = self.transformer
         if pab.enable_pab() or not getattr(tr, "use_programs", True):
-            self.step_stats["eager"] += 1
-            return self._model_pair(z, enc, pooled, pred, t)
-        ent = self._step_program
-        if ent is not None and ent[1] is not None and ent[2] is z:
-            tr.step_timesteps(z.shape[1]).fill_(float(t))     # the one per-step input besides the latents (updated in place)
-            ent[1].run()
-            self.step_stats["replayed"] += 1
-            return
-        with program.Recorder() as rec:
+            return self._steps.eager(lambda: self._model_pair(z, enc, pooled, pred, t))
+
+        def record():
             self._model_pair(z, enc, pooled, pred, t)
-        prog = rec.finish()
-        self._step_program = (None, prog, z, enc, pooled, pred)
-        self.step_stats["recorded" if prog is not None else "eager"] += 1
+            return z, enc, pooled, pred
+
+        # (on a hit) the one per-step input besides the latents, updated in place
+        self._steps.run(self._step_key(z, enc), record, lambda bufs: tr.step_timesteps(z.shape[1]).fill_(float(t)))
+
+    @staticmethod
+    def _step_key(z, enc):
+        return tuple(z.shape), tuple(enc.shape)
 
     def _step_buffers(self, z0, prompt_embeds, pooled):
         """Resident inputs of a step: latents z fp32 [1, F, 16, h, w], enc bf16 [2, F, L, D] (every frame reads its sample's prompt),
         pooled bf16 [2, PD], pred fp32 [2, F, 16, h, w].  A recorded program holds their addresses: the buffers of the last generate()
-        are reused (and the program with them) when geometry and embeddings are the same, else new ones are made."""
+        are reused (and the program with them) when geometry and embeddings are the same, else new ones are made and the program is
+        dropped, so that a key of the cache never names buffers other than the ones in use."""
         F = z0.shape[1]
         enc = prompt_embeds.to(device=self._device, dtype=torch.bfloat16)[:, None].expand(2, F, *prompt_embeds.shape[1:]).contiguous()
         pooled = pooled.to(device=self._device, dtype=torch.bfloat16).contiguous()
-        ent = self._step_program
-        if ent is not None and ent[1] is not None and ent[2].shape == z0.shape and ent[3].shape == enc.shape and \
-                torch.equal(ent[3], enc) and torch.equal(ent[4], pooled):
-            ent[2].copy_(z0)
-            return ent[2], ent[3], ent[4], ent[5]
-        self._step_program = None
+        ent = self._steps.entries.get(self._step_key(z0, enc))
+        if ent is not None and torch.equal(ent[1][1], enc) and torch.equal(ent[1][2], pooled):
+            ent[1][0].copy_(z0)
+            return ent[1]
+        self._steps.clear()
         z = z0.to(device=self._device, dtype=torch.float32).contiguous().clone()
         return z, enc, pooled, torch.empty((2,) + tuple(z.shape[1:]), dtype=torch.float32, device=self._device)
 
@@ -587,23 +577,9 @@ class VchitectXLPipeline(VideoSysPipeline):
 
         dsp.check_exchange(self.transformer)   # a timed-out peer-to-peer exchange left stale rows: raise here, not a corrupt video
         if self.vae is None or output_type in ("latent", "latents"):
-            self._enter_stage(None)
-            out = z.clone()
-            return VideoSysPipelineOutput(video=out) if return_dict else (out,)
+            return self._leave(z.clone(), return_dict)
         self._enter_stage("vae")
-        videos = [self.decode_frames(z, output_type)]                                            # (:980-986)
-        self._enter_stage(None)
-        return VideoSysPipelineOutput(video=videos) if return_dict else (videos,)
-
-    def _decode_group(self):
-        """The ranks that share one video's VAE decode: the sequence-parallel group of the transformer (every one of its ranks holds
-        the same final latents), None on one GPU, with ``shard_vae_decode=False`` or with ``VSYS_VAE_SHARD=0``."""
-        if not getattr(self._config, "shard_vae_decode", True) or os.environ.get("VSYS_VAE_SHARD") == "0":
-            return None
-        sp = getattr(self.transformer, "_sp", None)
-        if sp is not None and sp.P > 1:
-            return sp.group
-        return None
+        return self._leave([self.decode_frames(z, output_type)], return_dict)                    # (:980-986)
 
     def decode_frames(self, latents, output_type: str = "pil"):
         """pipeline_vchitect.py:980-985: `latents / scaling_factor + shift_factor`, every frame through the VAE, then

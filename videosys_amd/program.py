@@ -110,6 +110,71 @@ class Recorder:
         return None if self.invalid else Program(self)
 
 
+class StepCache:
+    """The recorded programs of one denoise loop, filed under the step's invariants: ``run`` records on a miss and refreshes the
+    per-step inputs and replays on a hit.  A step during which something unrecordable ran is filed nowhere and counted as eager,
+    so it is recorded anew at every call (no key is remembered as hopeless).  What must be launched but not recorded runs in the
+    caller before ``run``, guarded by ``key not in cache``.  The four loops, which differ in what they keep resident:
+
+    loop (counters)           | key                           | refresh on a hit                  | cleared by
+    --------------------------+-------------------------------+-----------------------------------+--------------------------------------
+    stdit3.STDiT3             | geometry, fps, the fold and   | copy x and the timestep into the  | load_state_dict; enable_parallel; a
+    (program_stats)           | fused-K/V switches, PAB       | program's own xin / tin (forward  | new text in _encode_text (programs
+                              | pattern, ragged text lengths, | hands back a clone of the         | hold the text K/V addresses);
+                              | parallel layout               | program's output)                 | reset_text_cache
+    OpenSoraPlanPipeline,     | latent shape, text shape, PAB | step_timesteps().fill_(t), then   | _set_parallel; _buffers when a shape
+    v1.2 (step_stats)         | decision pattern              | the PAB counters the eager call   | changes.  A new prompt of the same
+                              |                               | would have left                   | shape refills the text K/V in place:
+                              |                               |                                   | the programs stay
+    OpenSoraPlanV110Pipeline  | latent shape, text shape      | step_timesteps().fill_(t)         | _set_parallel; _buffers when a shape
+    (step_stats)              |                               |                                   | or the text changes (another text
+                              |                               |                                   | gets new K/V tensors)
+    VchitectXLPipeline        | latent shape, text shape; one | step_timesteps().fill_(t)         | _set_parallel; _step_buffers when a
+    (step_stats)              | entry, whose payload is the   |                                   | shape or an embedding changes (it
+                              | resident (z, enc, pooled,     |                                   | then makes new buffers)
+                              | pred)                         |                                   |
+    """
+
+    def __init__(self):
+        self.entries = {}      # key -> (Program, payload): what ``record`` returned, the buffers the program reads and writes
+        self.stats = {"recorded": 0, "replayed": 0, "eager": 0}
+
+    def __contains__(self, key):
+        return key in self.entries
+
+    def __len__(self):
+        return len(self.entries)
+
+    def clear(self):
+        self.entries = {}
+
+    def eager(self, fn):
+        self.stats["eager"] += 1
+        return fn()
+
+    def run(self, key, record: Callable[[], object], refresh: Optional[Callable[[object], None]] = None):
+        ent = self.entries.get(key)
+        if ent is not None:           # replay: ONE C call per launch segment
+            prog, payload = ent
+            if refresh is not None:
+                refresh(payload)
+            prog.run()
+            self.stats["replayed"] += 1
+            return payload
+        with Recorder() as rec:       # first time for this key: run eagerly under the recorder
+            payload = record()
+        prog = rec.finish()
+        if prog is not None:
+            self.entries[key] = (prog, payload)
+        self.stats["recorded" if prog is not None else "eager"] += 1
+        return payload
+
+
+def stats_property(cache: str):
+    """The counters of the StepCache at ``self.<cache>`` under the name the owner's callers read and assign."""
+    return property(lambda self: getattr(self, cache).stats, lambda self, v: setattr(getattr(self, cache), "stats", v))
+
+
 class Program:
     def __init__(self, rec: Recorder):
         self.keep = rec.keep

@@ -141,6 +141,7 @@ class STDiT3:
     """Drop-in for the reference STDiT3 at the operator boundary ``model(z_in, t, **model_args)``."""
 
     config_class = STDiT3Config
+    program_stats = program.stats_property("_steps")
 
     def __init__(self, config: STDiT3Config, device="cuda", dtype=torch.bfloat16):
         if dtype != torch.bfloat16:
@@ -195,8 +196,7 @@ class STDiT3:
         self.fused_kv = ops.FUSED_KV
         self._fold = None          # per-(B, column order) site table + the W' / cs / cv buffers (built on first use)
         self._stats_fresh = False  # "the statistics buffer describes the current x" (within one step)
-        self._programs = {}
-        self.program_stats = dict(recorded=0, replayed=0, eager=0)
+        self._steps = program.StepCache()
         # attribute paths the reference's callers read (scheduling_rflow_open_sora.py:221, pipeline_open_sora.py:295)
         self.x_embedder = SimpleNamespace(proj=SimpleNamespace(weight=torch.empty(0, dtype=dtype)))
         self.y_embedder = SimpleNamespace(y_embedding=None)
@@ -227,7 +227,7 @@ class STDiT3:
         self.y_embedder.y_embedding = self.w["y_embedder.y_embedding"]
         self._text_cache = None
         self._rope_cache = {}
-        self._programs = {}
+        self._steps.clear()
         self._fold = None
         return self
 
@@ -263,7 +263,7 @@ class STDiT3:
             if enable_cp and sp_size % 2 == 0:   # "update cfg parallel" (:470-475): the CFG pair goes to two rank groups
                 sp_size, cp_size = sp_size // 2, 2
             self.parallel_manager = dsp.ParallelManager(dp_size or 1, cp_size, sp_size)
-        self._programs = {}
+        self._steps.clear()
         if self.parallel_manager.sp_size > 1:
             kw = {} if copy_executor is None else {"copy_executor": copy_executor}
             # (a replaced SequenceParallel keeps its few bytes of peer-to-peer flag memory: a peer may still be raising a flag of the old
@@ -340,7 +340,7 @@ class STDiT3:
                 and (mask is None or c["mask_version"] == mask._version)):
             return c
         w = self.w
-        self._programs = {}   # recorded steps hold the previous prompt's K/V addresses
+        self._steps.clear()   # recorded steps hold the previous prompt's K/V addresses
         C, H = self.hidden_size, self.num_heads
         if skip:
             # config.skip_y_embedder (:585-590): ``y`` is ALREADY the y_embedder output, packed [1, sum(y_lens), C], and ``mask``
@@ -457,7 +457,7 @@ class STDiT3:
     def reset_text_cache(self):
         """Forget the per-prompt text projections (and their references to the prompt tensors) and the recorded steps."""
         self._text_cache = None
-        self._programs = {}
+        self._steps.clear()
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
@@ -526,37 +526,30 @@ class STDiT3:
         mlp_action = plan is not None and any(d[2] or d[3] for d in plan)   # stores / replays host-side dict entries: eager
         # (a conditioning mask changes from step to step and selects rows with torch ops: the step is issued eagerly)
         if not (self.use_programs and self._hidden_tap is None and not mlp_action and x_mask is None):
-            self.program_stats["eager"] += 1
             xz = x.to(device=dev, dtype=torch.float32).contiguous()
-            out = self._forward_device(xz, ts_host.to(dev), static, plan, timestep_int, valid_depth, cp, x_mask, fold=fold)
+            out = self._steps.eager(lambda: self._forward_device(xz, ts_host.to(dev), static, plan, timestep_int, valid_depth, cp, x_mask,
+                                                                 fold=fold))
         else:
             sp = self._sp
             key = (B, Tx, Hx, Wx, float(height[0]), float(width[0]), fkey, valid_depth, cp, fold, self.fold_spatial_qkv, self.fused_kv,
                    None if plan is None else tuple(d[:2] + d[5:7] for d in plan),
                    None if static[0]["varlen"] is None else static[0]["varlen"].lens,   # a ragged batch: its per-sample text lengths
                    None if sp is None else (sp.P, sp.rank, self._scatter, self._switch, self._overlap))
-            ent = self._programs.get(key)
-            if ent is not None:       # replay: refresh the two per-step inputs, ONE C call per launch segment
-                prog, xin, tin, out = ent
-                xin.copy_(x, non_blocking=True)
-                tin.copy_(ts_host, non_blocking=True)
-                prog.run()
-                self.program_stats["replayed"] += 1
-                out = out.clone()     # the program owns its output buffer; callers keep what they are handed
-            else:                     # first time for this key: run eagerly under the recorder
+
+            def record():             # the two per-step inputs live in buffers of the program's own
                 xin = torch.empty(B, x.shape[1], Tx, Hx, Wx, dtype=torch.float32, device=dev)
                 tin = torch.empty(B, dtype=torch.float32, device=dev)
                 xin.copy_(x)
                 tin.copy_(ts_host)
-                with program.Recorder() as rec:
-                    out = self._forward_device(xin, tin, static, plan, timestep_int, valid_depth, cp, fold=fold)
-                prog = rec.finish()
-                if prog is not None:
-                    self._programs[key] = (prog, xin, tin, out)
-                    self.program_stats["recorded"] += 1
-                    out = out.clone()
-                else:
-                    self.program_stats["eager"] += 1
+                return xin, tin, self._forward_device(xin, tin, static, plan, timestep_int, valid_depth, cp, fold=fold)
+
+            def refresh(ent):
+                ent[0].copy_(x, non_blocking=True)
+                ent[1].copy_(ts_host, non_blocking=True)
+
+            out = self._steps.run(key, record, refresh)[2]
+            if key in self._steps:    # the program owns its output buffer; callers keep what they are handed
+                out = out.clone()
         return out
 
     def _pab_plan(self, timestep_int, all_timesteps, valid_depth):
