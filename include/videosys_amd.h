@@ -444,6 +444,9 @@ int vsys_flash_attn_d72_rope(const void* q, int64_t q_stride, const void* rope_c
 /* Temporal self-attention over the T frames of every (b, s) token: RMS qk-norm, RoPE (cos/sin fp32 [T, 72], NULL =
  * none), fp32 softmax (attentions.py:75-78,95-97,111-120; open_sora_transformer_3d.py:203-206).
  * q_norm_w == k_norm_w == NULL: no qk-norm (Latte temporal blocks, latte_transformer_3d.py:680-760).
+ * Every T >= 1: up to 64 frames all keys at once (attention_t3.hip), from 65 frames on a block loop with a running maximum
+ * (attention_tlong.hip), any length.  Past 284 frames norm without RoPE is VSYS_ERR_SHAPE and qkv / out must be 16-byte aligned
+ * (VSYS_ERR_ALIGN); a 32-frame block of one token must span less than 2 GiB (31 * S * row_stride * 2 bytes).
  * qkv bf16 rows ordered (b, t, s), row_stride elements per row, q|k|v at column offsets 0|C|2C, head h at h*72. */
 int vsys_attn_temporal_d72(const void* qkv, int64_t row_stride, int64_t C, const void* q_norm_w, const void* k_norm_w,
                            const void* rope_cos_f32, const void* rope_sin_f32, void* out, int64_t out_stride, int64_t B,

@@ -1336,6 +1336,14 @@ int launch_attn_temporal_d72(const bf16_t* qkv, int64_t row_stride, int C, const
   if (B <= 0 || T <= 0 || S <= 0 || heads <= 0) return 0;
   if ((row_stride % 8) || (out_stride % 8) || (C % 8) || ((q_norm_w == nullptr) != (k_norm_w == nullptr))) return VSYS_ERR_SHAPE;
   const size_t per_wave = (size_t)2 * T * HD * sizeof(float);
+  // T > 64 at the default variant: the block-loop MFMA kernel of attention_tlong.hip, any T.  What it does not take (norm without
+  // RoPE, a 32-frame block whose span passes 31 bits, unaligned operands) stays on the VALU kernel below while that one fits
+  // (T <= 284); past that its refusal is this entry point's.  Variant 9 (and every other id) keeps the VALU kernel.
+  if (T > 64 && g_flash_variant_a.load(std::memory_order_relaxed) == 0) {
+    const int rc = launch_attn_temporal_d72_long(qkv, row_stride, C, q_norm_w, k_norm_w, rope_cos, rope_sin, out, out_stride, B, T, S,
+                                                 heads, eps, 0.11785113019775793f, stream);
+    if ((rc != VSYS_ERR_SHAPE && rc != VSYS_ERR_ALIGN) || per_wave > 160 * 1024) return rc;
+  }
   int wpb = 4;
   while (wpb > 1 && per_wave * wpb > 64 * 1024) wpb >>= 1;
   if (per_wave * wpb > 160 * 1024) return VSYS_ERR_SHAPE;

@@ -312,6 +312,10 @@ int launch_attn_temporal_d72_v3(const bf16_t* qkv, int64_t row_stride, int C, co
                                 const float* rope_cos, const float* rope_sin, bf16_t* out, int64_t out_stride, int B, int T, int S,
                                 int heads, float eps, float scale, hipStream_t stream, bool ref_rounding = false,
                                 bool no_v5 = false);   // no_v5: keep the per-lane-load kernel (A/B id 22)
+// T >= 65, any length: block loop with a running maximum (attention_tlong.hip); VSYS_ERR_SHAPE / VSYS_ERR_ALIGN = not taken, nothing launched
+int launch_attn_temporal_d72_long(const bf16_t* qkv, int64_t row_stride, int C, const bf16_t* q_norm_w, const bf16_t* k_norm_w,
+                                  const float* rope_cos, const float* rope_sin, bf16_t* out, int64_t out_stride, int B, int T, int S,
+                                  int heads, float eps, float scale, hipStream_t stream);
 int launch_attn_temporal_d72(const bf16_t* qkv, int64_t row_stride, int C, const bf16_t* q_norm_w, const bf16_t* k_norm_w,
                              const float* rope_cos, const float* rope_sin, bf16_t* out, int64_t out_stride, int B, int T,
                              int S, int heads, float eps, hipStream_t stream);

@@ -530,7 +530,11 @@ def attn_temporal(qkv, C, q_norm_w, k_norm_w, rope_cos, rope_sin, out, B, T, S, 
     Rounding contract (tests/test_gpu_numerics_attention.py): q^ and k^ carry at most the reference's roundings (x rstd, * w, rotation,
     q * 72^-1/2, each to bf16; the default kernels round once), logits and softmax in fp32 with the row sum of the UNROUNDED
     probabilities, the normalised weights p / l rounded to bf16 before the PV product (no running maximum: all T keys at once), fp32
-    accumulation, one rounding of the output."""
+    accumulation, one rounding of the output.
+    T > 64 (tests/test_gpu_temporal_long.py; csrc/attention_tlong.hip, any T): q^ and k^ rounded once, as above; key blocks of 32 with
+    an fp32 running maximum and sum per query row in the exp2 domain; the UNNORMALISED probabilities 2^(s - m) are rounded to bf16
+    before the PV product and summed unrounded, fp32 accumulation (rescaled when the maximum moves), the output divided by the sum and
+    rounded once.  Past 284 frames norm without RoPE and operands that are not 16-byte aligned are refused."""
     _chk(qkv, q_norm_w, k_norm_w, rope_cos, rope_sin, out)
     _bf16(qkv, q_norm_w, k_norm_w, out)
     assert qkv.stride(1) == 1 and out.stride(1) == 1
