@@ -618,6 +618,20 @@ int vsys_regrid(const void* x, const int64_t* grid_src, void* y, const int64_t* 
  * 2t + 1 of the two-front-frames conv. */
 int vsys_subsample(const void* x, const int64_t* grid_src, void* y, const int64_t* grid_dst, int64_t N, int64_t C, int64_t t_stride,
                    int64_t s_stride, int64_t t_first, int64_t s_first, void* stream);
+/* Stride-2 implicit-GEMM convolution of the Open-Sora-Plan v1.2 CausalVAE ENCODER (csrc/conv_down_bf16.hip): x rows [*, ldx] over
+ * grid_src (any pad / tf; only voxels are read), w [cout, 9 kt cin] with k = ((a 3 + kh) 3 + kw) cin + c, bias bf16 [cout] or NULL ->
+ * out DENSE rows [nsamples * To * Ho * Wo, ldo], Ho = H / 2, Wo = W / 2 (rounded down).
+ *   kt = 1  Downsample (autoencoder_kl_open_sora_plan_v120.py:430-464): per frame, F.pad (0, 1, 0, 1) + Conv2d(3, stride 2): tap
+ *           (kh, kw) of output (ho, wo) reads (2 ho + kh, 2 wo + kw), zero at row H and column W; To = T.
+ *   kt = 3  Spatial2xTime2x3DDownsample (:418-427 over CausalConv3d :40-113): the same in space, stride 2 in time behind TWO COPIES OF
+ *           THE FIRST FRAME: tap a of output frame t' reads frame max(2 t' + a - 2, 0); To = (T - 1) / 2 + 1.
+ * With an odd H (W) the zero row (column) is never reached.  cout % 128 == 0, cin % 32 == 0, H, W >= 2, nsamples <= 65535, strides % 8
+ * == 0, x / w / out 16-byte aligned; a tile of 256 output voxels must span less than 2 GiB of source rows (VSYS_ERR_SHAPE).
+ * The stream is the FIRST argument: this entry point is not a command of a launch program (no VSYS_OP code; the table below keeps its
+ * 75 entries) and so does not end in the `void* stream` by which csrc/gen/program_gen.py recognises one.  A recorded program issues it
+ * from a host closure at its place in the launch order (program.host_call), as it does vsys_attn_temporal_d64_img. */
+int vsys_conv_down2_bf16(void* stream, const void* x, int64_t ldx, const int64_t* grid_src, int64_t nsamples, const void* w, int64_t ldw,
+                         const void* bias, void* out, int64_t ldo, int64_t cin, int64_t cout, int64_t kt);
 /* CogVideoXSpatialNorm3D + SiLU (autoencoder_kl_cogvideox.py:165-178,275-276): y = silu(GN(x) * Y + B); yb = [conv_y(zq) |
  * conv_b(zq)] computed at LATENT resolution, rows (n, zt, zh, zw) of 2C columns; the latent voxel of (t, h, w) follows
  * F.interpolate(zq, size=f.shape) including the first-frame split for odd frame counts.  stats from vsys_gn_stats. */

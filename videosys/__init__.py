@@ -41,7 +41,7 @@ _MODULES = {
     "models.transformers.open_sora_plan_v110_transformer_3d": "open_sora_plan_v110",   # LatteT2V (v1.1: use_rope)
     "models.autoencoders.autoencoder_kl_open_sora": "vae_open_sora",    # OpenSoraVAE_V1_2
     "models.autoencoders.autoencoder_kl_cogvideox": "vae_cogvideox",    # AutoencoderKLCogVideoX
-    "models.autoencoders.autoencoder_kl_open_sora_plan_v120": "vae_open_sora_plan",   # CausalVAEModelWrapper, CausalVAEModel (decode side)
+    "models.autoencoders.autoencoder_kl_open_sora_plan_v120": "vae_open_sora_plan",   # CausalVAEModelWrapper, CausalVAEModel (both sides)
     "models.autoencoders.autoencoder_kl_open_sora_plan_v110": "vae_open_sora_plan_v110",   # the v1.1 CausalVAEModelWrapper, CausalVAEModel
     "pipelines.open_sora": "pipeline_open_sora",              # OpenSoraConfig, OpenSoraPABConfig, OpenSoraPipeline
     "pipelines.open_sora.pipeline_open_sora": "pipeline_open_sora",

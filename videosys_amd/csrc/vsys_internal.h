@@ -133,6 +133,20 @@ struct VaeGrid {
   int T, H, W, pad, tf;
   int64_t sample_rows;
 };
+// stride-2 implicit-GEMM convolution of the VAE encoders (conv_down_bf16.hip), filled in by launch_conv_down2
+struct ConvDownParams {
+  const bf16_t* X = nullptr; int64_t ldx = 0;   // source rows over the grid, [*, >= cin]
+  int64_t sample_rows = 0, rows_total = 0;      // rows per sample / of the whole operand
+  const bf16_t* W = nullptr; int64_t ldw = 0;   // [N, taps*cin], k = tap*cin + channel
+  const bf16_t* bias = nullptr;                 // [N] or null
+  bf16_t* out = nullptr; int64_t ldo = 0;       // dense rows [samples * M, N]
+  int M = 0, N = 0, K = 0;                      // M = To*Ho*Wo output voxels per sample
+  int cin = 0, nkc = 0, kt = 0;                 // nkc = cin / 32; kt = 1 (spatial) or 3 (spatio-temporal, causal)
+  int H = 0, Wd = 0, Ho = 0, Wo = 0;
+  int Wp = 0, plane = 0, row00 = 0;             // source row pitch, plane pitch, row of voxel (0, 0, 0) inside a sample
+};
+int launch_conv_down2(const bf16_t* x, int64_t ldx, const VaeGrid& g, int64_t nsamples, const bf16_t* w, int64_t ldw, const bf16_t* bias,
+                      bf16_t* out, int64_t ldo, int64_t cin, int64_t cout, int kt, hipStream_t stream);
 int launch_gn_stats(const bf16_t* x, const VaeGrid& g, int N, int C, int groups, float eps, float* partial, int nblk, float* stats,
                     hipStream_t stream);
 int launch_gn_apply(const bf16_t* x, const VaeGrid& gs, bf16_t* y, const VaeGrid& gd, int N, int C, int groups, const float* stats,

@@ -1,19 +1,21 @@
 """Tensor-level wrappers of the entry points that exist for Open-Sora-Plan v1.2 (include/videosys_amd.h): the head-dim-96 attention
 (vsys_attn_prep_kv96, vsys_flash_attn_d96 and their forms on a sequence-parallel exchange image, vsys_attn_prep_kv96_img,
 vsys_flash_attn_d96_img) and, at the end of the file, the CausalVAE decode and sampler kernels
-(vsys_upsample_trilinear2x, vsys_cfg_ancestral_step, vsys_pixels_to_u8_trunc).  HIP device tensors only, no eager fallback.
+(vsys_upsample_trilinear2x, vsys_cfg_ancestral_step, vsys_pixels_to_u8_trunc) and the CausalVAE encoder's stride-2 convolution
+(vsys_conv_down2_bf16).  HIP device tensors only, no eager fallback.
 
-Every entry point here has an op code and goes through ``ops._call`` like the wrappers of ops.py: issued through
+Every entry point here but the last has an op code and goes through ``ops._call`` like the wrappers of ops.py: issued through
 torch.ops.vsys.launch, and under a launch-program recorder logged as a vsys_cmd, so a recorded step replays the attention launches
 inside its vsys_program_run call.  The per-sample key counts of the cross-attention are read by the kernel from device memory, so a
-replay carries no count.
+replay carries no count.  vsys_conv_down2_bf16 has no op code: ``conv_down2`` calls it through ctypes from a ``program.host_call``
+closure, which a recorded program runs again at the same place of its launch order.
 Element-wise tests: tests/test_gpu_osp_attention.py, tests/test_gpu_osp_attention_img.py; guard bands: tests/test_gpu_isolation_osp.py,
 tests/test_gpu_isolation_osp_img.py."""
 from __future__ import annotations
 
 import torch
 
-from . import program
+from . import _lib, program
 from .ops import VaeGrid, _bf16, _call, _chk, _p, kv_pad_len
 
 HEAD_DIM = 96
@@ -158,4 +160,24 @@ def pixels_to_u8_trunc(x, g: VaeGrid, out, f0):
     assert x.dim() == 2 and x.shape[0] == g.rows and x.stride(1) == 1 and x.shape[1] >= 3
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 4 and tuple(out.shape[1:]) == (g.H, g.W, 3)
     _call("vsys_pixels_to_u8_trunc", _p(x), g._c, g.n, x.stride(0), _p(out), out.shape[0], f0)
+    return out
+
+
+def conv_down2(x, grid: VaeGrid, w, bias, cin, kt, out=None):
+    """Stride-2 3 x 3 (kt = 1, per frame) or causal 3 x 3 x 3 (kt = 3, stride 2 in time as well) convolution of the voxels of ``grid``
+    (rows ``x``, any pad / tf: borders and front frames are NOT read) with one implicit zero row below and one zero column to the right;
+    kt = 3 reads the first frame in place of the two frames in front of it (vsys_conv_down2_bf16, csrc/conv_down_bf16.hip).
+    w [cout, 9 kt cin], k = tap * cin + channel.  Returns the dense rows of ``grid.down2(kt)`` [rows, cout]."""
+    _chk(x, w, bias, out)
+    _bf16(x, w, bias, out)
+    assert x.shape[0] == grid.rows and x.stride(1) == 1 and x.shape[1] >= cin and w.shape[1] == 9 * kt * cin and w.stride(1) == 1
+    og = grid.down2(kt)
+    if out is None:
+        out = torch.empty(og.rows, w.shape[0], dtype=torch.bfloat16, device=x.device)
+    assert out.shape[0] == og.rows and out.stride(1) == 1
+    program.keep((x, w, bias, out, grid))
+    args = (x.data_ptr(), x.stride(0), grid._c, grid.n, w.data_ptr(), w.stride(0), None if bias is None else bias.data_ptr(),
+            out.data_ptr(), out.stride(0), cin, w.shape[0], kt)
+    fn = _lib.load().vsys_conv_down2_bf16
+    program.host_call(lambda: _lib.check(fn(torch.cuda.current_stream().cuda_stream, *args), "vsys_conv_down2_bf16"))
     return out

@@ -687,6 +687,10 @@ class VaeGrid:
         """Grid of a conv's output when this grid is its (padded) input: same rows minus the front frames."""
         return VaeGrid(self.n, self.T, self.H, self.W, self.pad, 0)
 
+    def down2(self, kt):
+        """The dense output grid of ``conv_down2`` over this grid: H / 2 x W / 2 (rounded down), (T - 1) / 2 + 1 frames when kt = 3."""
+        return VaeGrid(self.n, (self.T - 1) // 2 + 1 if kt == 3 else self.T, self.H // 2, self.W // 2, 0, 0)
+
 
 def conv(a, grid: VaeGrid, w, bias, cin, kt, ks, out=None, res=None):
     """Tap-shifted implicit-GEMM conv over the padded grid ``grid`` whose rows are the 2-D tensor ``a``.  ks = spatial kernel

@@ -28,7 +28,12 @@ No kernel changes, no extra launches; at ``hidden_size`` 128 the map is the iden
 The residual block, the staging cache, the attention core (with the mask for key counts that are no multiple of four) and the tile
 stitching are the shared ones of vae_blocks.py; this module adds the channel map, the causal front frames (``_norm_act``), the
 whole-sample GroupNorm around the attention core and the tiling geometry.  Under a group of ranks (``decode(z, group=)``) the
-(sample, temporal chunk, spatial tile) units of a tiled decode are dealt over the ranks and gathered once.  There is no CPU path."""
+(sample, temporal chunk, spatial tile) units of a tiled decode are dealt over the ranks and gathered once.  There is no CPU path.
+
+Encode side (``CausalVAEEncoder``, ``CausalVAEModel.encode``, ``CausalVAEModelWrapper.encode``; Encoder :509-626, :859-870, :1124-1127):
+the mirror configuration (``ENCODER_CONFIG``) on the same blocks; its Downsample and Spatial2xTime2x3DDownsample layers are the
+stride-2 implicit GEMM vsys_conv_down2_bf16 (csrc/conv_down_bf16.hip), which takes its right / bottom zero padding and the
+replicated causal front from its addressing.  ``tiled_encode`` is not built (raises)."""
 from __future__ import annotations
 
 from types import SimpleNamespace
@@ -109,6 +114,8 @@ class _CConv:
     def __init__(self, sd, key, dev, cin: _ChanMap, cout: Optional[_ChanMap], n_pad: Optional[int] = None):
         w = sd[key + ".conv.weight"].to(dev).float()
         b = sd[key + ".conv.bias"].to(dev).float()
+        if w.dim() == 4:                                                            # the Conv2d of the encoder's Downsample: kt = 1
+            w = w.unsqueeze(2)
         self.key, self.kt, self.ks = key, w.shape[2], w.shape[-1]
         w = cin.in_cols(w)
         if cout is not None:
@@ -135,14 +142,58 @@ class _CRes:
         self.sc = _CConv(sd, p + ".nin_shortcut", dev, ci, co) if (p + ".nin_shortcut.conv.weight") in sd else None
 
 
-class CausalVAEDecoder(VaeBlocks):
-    """Decode side of the reference ``CausalVAEModel``: ``decode(z)``, z [B, 4, T, H, W] (already divided by 0.18215 unless
-    ``in_scale`` says otherwise) -> [B, 3, 4(T-1)+1, 8H, 8W] bf16, with the reference's tiling attributes."""
+class _CausalBlocks(VaeBlocks):
+    """What both sides of the CausalVAE are made of on top of vae_blocks.VaeBlocks: the causal front frames, the convolution
+    call, the mid-block attention over all frames of the sample."""
+
+    @staticmethod
+    def _front(rows, g: VaeGrid):
+        """CausalConv3d.forward :94-97: the g.tf frames in front of the conv's input are copies of its first frame."""
+        if g.tf:
+            v = rows.view(g.T + g.tf, g.Hp, g.Wp, rows.shape[1])
+            v[:g.tf].copy_(v[g.tf:g.tf + 1].expand(g.tf, -1, -1, -1))
+
+    def _norm_act(self, x, gx: VaeGrid, norm, C: int, tf: int, silu=True, dense=False):
+        """GroupNorm over all frames of the sample (+ SiLU) into the padded conv-input grid, then the causal front frames.
+        With it the shared ``_resblock`` is ResnetBlock3D.forward :295-315."""
+        y, gd = super()._norm_act(x, gx, norm, C, tf, silu, dense)
+        self._front(y, gd)
+        return y, gd
+
+    def _conv(self, h, gh: VaeGrid, cv: _CConv, res=None):
+        return ops.conv(h, gh, cv.w, cv.b, cv.cin, cv.kt, cv.ks, res=res)
+
+    def _attention(self, x, g: VaeGrid, aw: AttnWeights):
+        """AttnBlock3DFix.forward :375-415 with its residual: one head of width C per frame.  x rows over g (pad 1, no front frames)
+        -> dense rows.  Inside, a frame takes the key count rounded up to the 128-column GEMM tile (pad rows zero on input)."""
+        C, L, n = aw.C, g.H * g.W, g.T
+        Lp = check_attention_keys(g.H, g.W)
+        gf = VaeGrid(n, 1, g.H, g.W, g.pad, 0, sample_rows=g.plane)                 # the same rows, one sample per frame
+        gdn = VaeGrid(n, 1, g.H, g.W, 0, 0, sample_rows=Lp)
+        hn, xd = self._attn_bufs(n, g.H, g.W, C, Lp)
+        gn1 = VaeGrid(1, n, g.H, g.W, 0, 0)
+        stage = torch.empty(gn1.rows, C, dtype=torch.bfloat16, device=self.device)
+        ops.group_norm(x, g, stage, gn1, C, aw.norm.g, aw.norm.b, aw.norm.eps, False)      # statistics over all frames of the sample
+        ops.regrid(stage, VaeGrid(n, 1, g.H, g.W, 0, 0), hn, gdn, C)                       # ... then one frame per Lp rows
+        ops.regrid(x, gf, xd, gdn, C)
+        y = attention_core(hn, xd, n, L, Lp, C, aw)
+        # (a per-frame stride of Lp rows is no grid of ONE sample, and the next GroupNorm runs over the whole sample: frame-dense rows)
+        out = torch.empty(gn1.rows, C, dtype=torch.bfloat16, device=self.device)
+        ops.regrid(y, gdn, out, VaeGrid(n, 1, g.H, g.W, 0, 0), C)
+        return out, gn1
+
+
+class CausalVAEDecoder(_CausalBlocks):
+    """The reference ``CausalVAEModel``.  Decode side: ``decode(z)``, z [B, 4, T, H, W] (already divided by 0.18215 unless
+    ``in_scale`` says otherwise) -> [B, 3, 4(T-1)+1, 8H, 8W] bf16, with the reference's tiling attributes.  Encode side: ``encode(x)``
+    -> the posterior, through ``self.encoder`` (a ``CausalVAEEncoder``), which exists when the state dict holds ``encoder.*`` and
+    ``quant_conv.*``."""
 
     # what a decoder of the same family with other upsamplers overrides (vae_open_sora_plan_v110.py)
     SPATIAL = SPATIAL_UPSAMPLE
     TILE_DEFAULTS = dict(tile_sample_min_size=256, tile_sample_min_size_t=33, tile_latent_min_size_t=16, tile_overlap_factor=0.125)
     _check = staticmethod(_check_config)
+    ENCODER = None                       # the encode side's class (set below the class: CausalVAEEncoder); None: a decode-only family
 
     @staticmethod
     def _param_shapes(hidden_size: int) -> Dict[str, tuple]:
@@ -195,6 +246,8 @@ class CausalVAEDecoder(VaeBlocks):
             self._level_extra(sd, lvl, co, dev)
         self.norm_out = _CNorm(sd, d + "norm_out", dev, prev)
         self.conv_out = _CConv(sd, d + "conv_out", dev, prev, None, n_pad=128)
+        has_enc = self.ENCODER is not None and "encoder.conv_in.conv.weight" in sd
+        self.encoder = self.ENCODER(sd, device=dev, hidden_size=hs, **config) if has_enc else None
 
     def _level_extra(self, sd, lvl: int, cm: _ChanMap, dev) -> None:
         """Weights a level holds beside its residual blocks and its spatial upsampler (none in v1.2)."""
@@ -209,43 +262,6 @@ class CausalVAEDecoder(VaeBlocks):
 
     def disable_tiling(self):
         self.enable_tiling(False)
-
-    # ------------------------------------------------------------------------------------------------ building blocks
-    @staticmethod
-    def _front(rows, g: VaeGrid):
-        """CausalConv3d.forward :94-97: the g.tf frames in front of the conv's input are copies of its first frame."""
-        if g.tf:
-            v = rows.view(g.T + g.tf, g.Hp, g.Wp, rows.shape[1])
-            v[:g.tf].copy_(v[g.tf:g.tf + 1].expand(g.tf, -1, -1, -1))
-
-    def _norm_act(self, x, gx: VaeGrid, norm, C: int, tf: int, silu=True, dense=False):
-        """GroupNorm over all frames of the sample (+ SiLU) into the padded conv-input grid, then the causal front frames.
-        With it the shared ``_resblock`` is ResnetBlock3D.forward :295-315."""
-        y, gd = super()._norm_act(x, gx, norm, C, tf, silu, dense)
-        self._front(y, gd)
-        return y, gd
-
-    def _conv(self, h, gh: VaeGrid, cv: _CConv, res=None):
-        return ops.conv(h, gh, cv.w, cv.b, cv.cin, cv.kt, cv.ks, res=res)
-
-    def _attention(self, x, g: VaeGrid, aw: AttnWeights):
-        """AttnBlock3DFix.forward :375-415 with its residual: one head of width C per frame.  x rows over g (pad 1, no front frames)
-        -> dense rows.  Inside, a frame takes the key count rounded up to the 128-column GEMM tile (pad rows zero on input)."""
-        C, L, n = aw.C, g.H * g.W, g.T
-        Lp = check_attention_keys(g.H, g.W)
-        gf = VaeGrid(n, 1, g.H, g.W, g.pad, 0, sample_rows=g.plane)                 # the same rows, one sample per frame
-        gdn = VaeGrid(n, 1, g.H, g.W, 0, 0, sample_rows=Lp)
-        hn, xd = self._attn_bufs(n, g.H, g.W, C, Lp)
-        gn1 = VaeGrid(1, n, g.H, g.W, 0, 0)
-        stage = torch.empty(gn1.rows, C, dtype=torch.bfloat16, device=self.device)
-        ops.group_norm(x, g, stage, gn1, C, aw.norm.g, aw.norm.b, aw.norm.eps, False)      # statistics over all frames of the sample
-        ops.regrid(stage, VaeGrid(n, 1, g.H, g.W, 0, 0), hn, gdn, C)                       # ... then one frame per Lp rows
-        ops.regrid(x, gf, xd, gdn, C)
-        y = attention_core(hn, xd, n, L, Lp, C, aw)
-        # (a per-frame stride of Lp rows is no grid of ONE sample, and the next GroupNorm runs over the whole sample: frame-dense rows)
-        out = torch.empty(gn1.rows, C, dtype=torch.bfloat16, device=self.device)
-        ops.regrid(y, gdn, out, VaeGrid(n, 1, g.H, g.W, 0, 0), C)
-        return out, gn1
 
     def _decode_tile(self, zt: torch.Tensor, in_scale: float) -> torch.Tensor:
         """zt planar bf16 [4, T, h, w] -> planar bf16 [3, 4(T-1)+1, 8h, 8w]: post_quant_conv + Decoder.forward :713-738."""
@@ -382,8 +398,155 @@ class CausalVAEDecoder(VaeBlocks):
 
     __call__ = decode
 
+    # ------------------------------------------------------------------------------------------------ encode side
+    @torch.no_grad()
+    def encode(self, x: torch.Tensor) -> "DiagonalGaussianDistribution":
+        """CausalVAEModel.encode :859-870: x [B, 3, T, H, W] in [-1, 1] -> the posterior over [B, 4, (T - 1) // 4 + 1, H / 8, W / 8]."""
+        if self.encoder is None:
+            raise RuntimeError("this CausalVAEModel was built from a state dict without encoder.* / quant_conv.* weights (decode only)")
+        if self.use_tiling and (x.shape[-1] > self.tile_sample_min_size or x.shape[-2] > self.tile_sample_min_size
+                                or x.shape[-3] > self.tile_sample_min_size_t):
+            return self.tiled_encode(x)
+        return DiagonalGaussianDistribution(self.encoder.moments(x))
 
-CausalVAEModel = CausalVAEDecoder        # the reference's class name; decode side only
+    def tiled_encode(self, x):
+        raise NotImplementedError("CausalVAEModel.tiled_encode (:918-940) is not built: call disable_tiling() and encode(x), which takes "
+                                  "the whole clip (the mid-block attention limits a frame to 8192 latent pixels, 720 x 720)")
+
+
+class DiagonalGaussianDistribution:
+    """The reference's posterior (:199-238) over moments [B, 8, T, h, w] (mean | logvar) as the encoder leaves them (bf16): ``mean``,
+    ``logvar`` (clamped to [-30, 20]), ``std``, ``var`` in fp32, ``mode()``, ``sample()``.  ``sample`` draws its noise as the reference
+    does — torch.randn on the CPU generator (``generator``: one of the caller's instead of the global one), moved to the device."""
+
+    def __init__(self, parameters: torch.Tensor):
+        self.parameters = parameters
+        mean, logvar = torch.chunk(parameters.float(), 2, dim=1)
+        self.mean, self.logvar = mean, torch.clamp(logvar, -30.0, 20.0)
+        self.std, self.var = torch.exp(0.5 * self.logvar), torch.exp(self.logvar)
+
+    def sample(self, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        return self.mean + self.std * torch.randn(self.mean.shape, generator=generator).to(self.parameters.device)
+
+    def mode(self) -> torch.Tensor:
+        return self.mean
+
+
+ENCODER_CONFIG = dict(encoder_conv_in="CausalConv3d", encoder_conv_out="CausalConv3d", encoder_attention="AttnBlock3DFix",
+                      encoder_resnet_blocks=("ResnetBlock3D",) * 4, encoder_mid_resnet="ResnetBlock3D",
+                      encoder_spatial_downsample=("Downsample", "Spatial2xTime2x3DDownsample", "Spatial2xTime2x3DDownsample", ""),
+                      encoder_temporal_downsample=("",) * 4, double_z=True)
+_IDENT = [1.0] * 4 + [0.0] * 4 + [1.0, 0, 0, 0, 0, 1.0, 0, 0, 0, 0, 1.0, 0, 0, 0, 0, 1.0] + [0.0] * 4   # first-layer params: x as is
+
+
+def _check_encoder_config(kw: dict) -> None:
+    """The encode side of the configuration ``_check_config`` accepts (its mirror: CausalConv3d in and out, AttnBlock3DFix in the mid
+    block, ResnetBlock3D everywhere, Downsample then two Spatial2xTime2x3DDownsample, no temporal downsamplers, double_z)."""
+    _check_config({k: v for k, v in kw.items() if not k.startswith("decoder_")})
+    for k, want in ENCODER_CONFIG.items():
+        if k in kw:
+            got = tuple(kw[k]) if isinstance(kw[k], (list, tuple)) else kw[k]
+            if got != want:
+                raise NotImplementedError(f"CausalVAEModel({k}={kw[k]!r}): this build encodes the Open-Sora-Plan v1.2 configuration only "
+                                          f"({k}={want!r})")
+
+
+class CausalVAEEncoder(_CausalBlocks):
+    """Encode side of the reference ``CausalVAEModel`` (Encoder :509-626 + quant_conv): ``moments(x)``, x [B, 3, T, H, W] in [-1, 1] ->
+    bf16 [B, 8, (T - 1) // 4 + 1, H / 8, W / 8] (mean | logvar).  conv_in is the first-layer im2col + a GEMM, the residual blocks, the
+    attention and conv_out are the decoder's kernels, the two downsampling layer kinds are vsys_conv_down2_bf16 on the rows the block
+    before them wrote (no padded copy, no sampled stride-1 convolution), quant_conv is a GEMM on conv_out's rows.  H and W need not be
+    multiples of 8 (every level halves rounding down, as the reference's padding does)."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", hidden_size: Optional[int] = None, **config):
+        _check_encoder_config(config)
+        super().__init__(device)
+        dev, sd, e = self.device, state_dict, "encoder."
+        hs = sd[e + "conv_in.conv.weight"].shape[0]
+        if hidden_size is not None and hidden_size != hs:
+            raise ValueError(f"hidden_size {hidden_size}, but encoder.conv_in.conv.weight has {hs} output channels")
+        missing = sorted(set(encoder_param_shapes(hs)) - set(sd))
+        if missing:
+            raise KeyError(f"CausalVAE encoder: the state dict lacks {missing[:4]}{' ...' if len(missing) > 4 else ''}")
+        self.hidden_size = hs
+        cm = {c: _ChanMap(c) for c in {hs * m for m in HIDDEN_SIZE_MULT}}
+        first = cm[hs]
+        w_in = torch.zeros(hs, 4, 3, 3, 3, device=dev)                              # column = tap * 4 + channel, channel 3 unused
+        w_in[:, :3] = sd[e + "conv_in.conv.weight"].to(dev).float()
+        w_in = first.out_rows(w_in).permute(0, 2, 3, 4, 1).reshape(first.P, -1)
+        self.conv_in_w = torch.zeros(first.P, _KCOLS, dtype=torch.bfloat16, device=dev)
+        self.conv_in_w[:, :w_in.shape[1]] = w_in.to(torch.bfloat16)
+        self.conv_in_b = first.out_rows(sd[e + "conv_in.conv.bias"]).to(dev).to(torch.bfloat16).contiguous()
+        self.down = []
+        prev = first
+        for lvl, kind in enumerate(ENCODER_CONFIG["encoder_spatial_downsample"]):
+            co = cm[hs * HIDDEN_SIZE_MULT[lvl]]
+            res = []
+            for j in range(2):
+                res.append(_CRes(sd, f"{e}down.{lvl}.block.{j}", dev, prev, co))
+                prev = co
+            key = f"{e}down.{lvl}.downsample" + (".conv" if kind.startswith("Spatial2x") else "")
+            self.down.append((res, _CConv(sd, key, dev, co, co) if kind else None))
+        top = prev
+        self.mid = [_CRes(sd, f"{e}mid.block_{i}", dev, top, top) for i in (1, 2)]
+        a = e + "mid.attn_1."
+        lin = lambda n: _CConv(sd, a + n, dev, top, top)
+        self.attn = AttnWeights.from_convs(_CNorm(sd, a + "norm", dev, top), lin("q"), lin("k"), lin("v"), lin("proj_out"))
+        self.norm_out = _CNorm(sd, e + "norm_out", dev, top)
+        self.conv_out = _CConv(sd, e + "conv_out", dev, top, None, n_pad=128)        # 8 of 128 columns carry the moments
+        self.quant_w = torch.zeros(128, 128, dtype=torch.bfloat16, device=dev)       # quant_conv (1 x 1 x 1) on those 8
+        self.quant_w[:8, :8] = sd["quant_conv.conv.weight"].to(dev).reshape(8, 8).to(torch.bfloat16)
+        self.quant_b = _vec(sd["quant_conv.conv.bias"].to(dev), 128)
+
+    @staticmethod
+    def _front(rows, g: VaeGrid):
+        """The decoder's ``_front`` as a launch (vsys_regrid, destination frame t reads source frame t / 2), so that an encode recorded
+        as a program replays it: the staging buffers are shared by the layers of one geometry."""
+        if g.tf:
+            assert g.tf == 2
+            ops.regrid(rows[2 * g.plane:3 * g.plane], VaeGrid(1, 1, g.H, g.W, g.pad, 0), rows[:2 * g.plane],
+                       VaeGrid(1, 2, g.H, g.W, g.pad, 0), rows.shape[1], tmode=1)
+
+    def _encode_sample(self, xs: torch.Tensor, out: torch.Tensor) -> None:
+        """xs planar bf16 [3, T, H, W] -> out planar bf16 [8, To, h, w]: Encoder.forward :602-626 + quant_conv."""
+        _, T, H, W = xs.shape
+        z4 = torch.cat([xs[:, :1], xs[:, :1], xs], dim=1)                           # conv_in's two copies of the first frame
+        z4 = torch.cat([z4, torch.zeros_like(z4[:1])], dim=0).contiguous()
+        a = ops.vae_first_im2col(z4, 3, _KCOLS, _IDENT)
+        x = ops.gemm128(a, self.conv_in_w, self.conv_in_b)[2 * H * W:]
+        g = VaeGrid(1, T, H, W, 0, 0)
+        for res, down in self.down:
+            for r in res:
+                x, g = self._resblock(x, g, r)
+            if down is not None:                                                     # Downsample :430-464 (kt 1) / Spatial2xTime2x3DDownsample :418-427
+                x, g = oops.conv_down2(x, g, down.w, down.b, down.cin, down.kt), g.down2(down.kt)
+        x, g = self._resblock(x, g, self.mid[0])
+        x, g = self._attention(x, g, self.attn)
+        x, g = self._resblock(x, g, self.mid[1])
+        hN, gN = self._norm_act(x, g, self.norm_out, self.norm_out.C, 2)
+        m = ops.gemm128(self._conv(hN, gN, self.conv_out), self.quant_w, self.quant_b)
+        ops.extract_planar(m, gN.conv_out(), 4, 0, out[:4], 0)                       # mean   (the kernel moves <= 4 channels a call)
+        ops.extract_planar(m[:, 4:], gN.conv_out(), 4, 0, out[4:], 0)                # logvar
+
+    @torch.no_grad()
+    def moments(self, x: torch.Tensor) -> torch.Tensor:
+        """x [B, 3, T, H, W] -> bf16 moments [B, 8, To, H / 8, W / 8].  Under a launch-program recorder the clip is staged by torch
+        copies (``_encode_sample``) BEFORE the first launch: a replay encodes that staged copy again, not a new ``x``."""
+        if not x.is_cuda:
+            raise RuntimeError("CausalVAEEncoder needs a HIP device tensor (no CPU path)")
+        if x.dim() != 5 or x.shape[1] != 3 or x.shape[-1] < 8 or x.shape[-2] < 8:
+            raise ValueError(f"expected a video [B, 3, T, H >= 8, W >= 8], got {tuple(x.shape)}")
+        B, _, T, H, W = x.shape
+        To = ((T - 1) // 2 + 1 - 1) // 2 + 1
+        check_attention_keys(H // 8, W // 8)
+        out = torch.empty(B, 8, To, H // 8, W // 8, dtype=torch.bfloat16, device=self.device)
+        for b in range(B):
+            self._encode_sample(x[b].to(torch.bfloat16), out[b])
+        return out
+
+
+CausalVAEDecoder.ENCODER = CausalVAEEncoder
+CausalVAEModel = CausalVAEDecoder        # the reference's class name: both sides (the encode side when the state dict holds it)
 
 
 class CausalVAEModelWrapper:
@@ -404,10 +567,12 @@ class CausalVAEModelWrapper:
             sd = read_component(model_path if subfolder is None else f"{model_path}/{subfolder}")[1]
             if sd is None:
                 raise FileNotFoundError(f"CausalVAEModelWrapper({model_path!r}): not a local checkpoint directory, a state dict or 'synthetic:<seed>'")
-        self.vae = CausalVAEDecoder(sd, device=device, hidden_size=hidden_size, **kwargs)
+        self.vae = CausalVAEModel(sd, device=device, hidden_size=hidden_size, **kwargs)
 
-    def encode(self, x):
-        raise NotImplementedError("the CausalVAE encoder is not part of this build (decode only)")
+    @torch.no_grad()
+    def encode(self, x: torch.Tensor, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """:1124-1127: vae.encode(x).sample() * 0.18215, fp32 [B, 4, t, h, w] (``generator``: DiagonalGaussianDistribution.sample)."""
+        return self.vae.encode(x).sample(generator) * SCALE
 
     @torch.no_grad()
     def decode(self, x: torch.Tensor, group=None) -> torch.Tensor:
@@ -462,7 +627,45 @@ def decoder_param_shapes(hidden_size: int = 128, spatial=SPATIAL_UPSAMPLE, tempo
     return p
 
 
-def synth_state_dict(seed: int = 0, hidden_size: int = 128) -> Dict[str, torch.Tensor]:
+def encoder_param_shapes(hidden_size: int = 128) -> Dict[str, tuple]:
+    """Names and shapes of the encode-side parameters of the reference CausalVAEModel in the configuration ``ENCODER_CONFIG`` (checked
+    against its own state_dict through tests/golden/osp_vae_encode_small.pt): ``encoder.*`` and ``quant_conv.*``."""
+    p: Dict[str, tuple] = {}
+    hs, e = hidden_size, "encoder."
+
+    def res(name, ci, co):
+        norm(p, name + ".norm1", ci); conv3(p, name + ".conv1", ci, co, 3)
+        norm(p, name + ".norm2", co); conv3(p, name + ".conv2", co, co, 3)
+        if ci != co:
+            conv3(p, name + ".nin_shortcut", ci, co, 1)
+
+    conv3(p, e + "conv_in", 3, hs, 3)
+    prev = hs
+    for lvl, kind in enumerate(ENCODER_CONFIG["encoder_spatial_downsample"]):
+        co = hs * HIDDEN_SIZE_MULT[lvl]
+        for j in range(2):
+            res(f"{e}down.{lvl}.block.{j}", prev, co)
+            prev = co
+        if kind == "Downsample":
+            p[f"{e}down.{lvl}.downsample.conv.weight"], p[f"{e}down.{lvl}.downsample.conv.bias"] = (co, co, 3, 3), (co,)
+        elif kind:
+            conv3(p, f"{e}down.{lvl}.downsample.conv", co, co, 3)
+    res(e + "mid.block_1", prev, prev)
+    norm(p, e + "mid.attn_1.norm", prev)
+    for n in ("q", "k", "v", "proj_out"):
+        conv3(p, f"{e}mid.attn_1.{n}", prev, prev, 1)
+    res(e + "mid.block_2", prev, prev)
+    norm(p, e + "norm_out", prev)
+    conv3(p, e + "conv_out", prev, 2 * Z_CHANNELS, 3)
+    conv3(p, "quant_conv", 2 * Z_CHANNELS, 2 * Z_CHANNELS, 1)
+    return p
+
+
+def synth_state_dict(seed: int = 0, hidden_size: int = 128, encoder: bool = False) -> Dict[str, torch.Tensor]:
     """Deterministic random decoder weights with the reference's names (vae_blocks.synth_weights: bf16-representable fp32, norm
-    scales 1 + N(0, 0.1), norm shifts N(0, 0.1)): no checkpoint can be fetched here."""
-    return synth_weights(decoder_param_shapes(hidden_size), torch.Generator().manual_seed(seed))
+    scales 1 + N(0, 0.1), norm shifts N(0, 0.1)): no checkpoint can be fetched here.  ``encoder``: the encode side as well, drawn
+    AFTER the decoder's (the decoder weights of a seed are the same either way)."""
+    shapes = decoder_param_shapes(hidden_size)
+    if encoder:
+        shapes.update(encoder_param_shapes(hidden_size))
+    return synth_weights(shapes, torch.Generator().manual_seed(seed))

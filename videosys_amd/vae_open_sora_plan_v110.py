@@ -76,6 +76,7 @@ class CausalVAEDecoder(v120.CausalVAEDecoder):
     SPATIAL = SPATIAL_UPSAMPLE
     TILE_DEFAULTS = dict(tile_sample_min_size=256, tile_sample_min_size_t=65, tile_latent_min_size_t=17, tile_overlap_factor=0.25)
     _check = staticmethod(_check_config)
+    ENCODER = None                       # the v1.1 encoder (other downsamplers) is not built: encode() raises
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", hidden_size: Optional[int] = None, **config):
         _check_config(config)
