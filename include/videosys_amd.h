@@ -673,6 +673,19 @@ int vsys_pixels_to_u8(const void* x, const int64_t* grid, int64_t N, int64_t ldx
  * attention of the 2-D VAE — diffusers Attention under VideoAutoencoderKL.decode / .encode, autoencoder_kl_open_sora.py:503-538 —
  * keys padded to the 128-column tile; n % 4 == 0, ld % 4 == 0, ld <= 8192). */
 int vsys_softmax_rows(const void* s_f32, void* p, int64_t rows, int64_t n, int64_t ld, void* stream);
+/* Single-head flash attention of the VAE mid blocks (csrc/attention_vae.hip; AttnBlock3DFix, autoencoder_kl_open_sora_plan_v120.py
+ * :360-415, and diffusers Attention under the 2-D decoders, autoencoder_kl_open_sora.py:503-538): for each of n frames
+ * o = softmax(scale q k^T) v over the first L of Lp rows, head dim C = 128, 256 or 512 (else VSYS_ERR_SHAPE), ANY L >= 1: no score
+ * matrix, no 8192-key limit.  q, k bf16 rows [n * Lp, ld], vt bf16 [n, C, ldv] = V^T per frame (ldv >= Lp), o bf16 rows [n * Lp, ldo].
+ * Keys L .. Lp - 1 are masked in the kernel (vt columns L .. Lp - 1 must be finite); rows L .. Lp - 1 of o are not written.  Block loop
+ * over 32 keys with an fp32 running maximum and sum (exp2 domain), P rounded to bf16 unnormalised, the sum from the unrounded P, one
+ * division and one rounding at the end.  scale > 0 (else VSYS_ERR_ARG).  Leading dimensions and Lp % 8 == 0, pointers 16-byte aligned,
+ * else VSYS_ERR_ALIGN; 32 k rows and C vt rows must each span less than 2 GiB (VSYS_ERR_SHAPE).
+ * The stream is the FIRST argument, as for vsys_conv_down2_bf16: the entry point fits a vsys_cmd, but the launch-program table keeps its
+ * 75 entries (its size is pinned), so it has no VSYS_OP code and a recorded program issues it from a host closure at its place in the
+ * launch order (program.host_call). */
+int vsys_vae_flash_attn(void* stream, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldv, void* o,
+                        int64_t ldo, int64_t n, int64_t L, int64_t Lp, int64_t C, float scale);
 
 /* Open-Sora-Plan v1.2 CausalVAE decode and sampler (csrc/vae_osp.hip).  None of the three has a VSYS_OP code: the decode is not part
  * of a recorded step, and the step kernel is launched by the host after each replay. */

@@ -817,6 +817,12 @@ int vsys_softmax_rows(const void* s_f32, void* p, int64_t rows, int64_t n, int64
   return launch_softmax_rows(reinterpret_cast<const float*>(s_f32), B16(p), rows, (int)n, (int)ld, S(stream));
 }
 
+int vsys_vae_flash_attn(void* stream, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldv, void* o,
+                        int64_t ldo, int64_t n, int64_t L, int64_t Lp, int64_t C, float scale) {
+  if (!q || !k || !vt || !o) return VSYS_ERR_ARG;
+  return launch_vae_flash_attn(B16(q), ldq, B16(k), ldk, B16(vt), ldv, B16(o), ldo, n, L, Lp, C, scale, S(stream));
+}
+
 int vsys_upsample_trilinear2x(const void* x, const int64_t* grid_src, void* y, const int64_t* grid_dst, int64_t N, int64_t C,
                               void* stream) {
   VaeGrid gs, gd;

@@ -164,6 +164,10 @@ int launch_vae_first_im2col(const bf16_t* z, int F, int H, int W, int kt, int kc
 int launch_extract_planar(const bf16_t* x, const VaeGrid& g, int N, int ldx, int nc, int tskip, bf16_t* out, int64_t Ftot, int f0,
                           hipStream_t stream);
 int launch_softmax_rows(const float* s, bf16_t* p, int64_t rows, int n, int ld, hipStream_t stream);
+// single-head flash attention of the VAE mid blocks at head dim C = 128 / 256 / 512 (attention_vae.hip): q, k rows [n * Lp, ld],
+// vt [n, C, ldv], o rows [n * Lp, ldo]; keys and query rows L .. Lp - 1 of every frame are masked / not stored
+int launch_vae_flash_attn(const bf16_t* q, int64_t ldq, const bf16_t* k, int64_t ldk, const bf16_t* vt, int64_t ldv, bf16_t* o,
+                          int64_t ldo, int64_t n, int64_t L, int64_t Lp, int64_t C, float scale, hipStream_t stream);
 
 // SD3 VAE ends of the Vchitect-2.0 decode (vae_sd3.hip)
 int launch_vae_first_im2col_nc(const float* z, int F, int Cz, int H, int W, int kcols, float scaling, float shift, bf16_t* out,

@@ -5,21 +5,24 @@ vae_open_sora_plan.py): the model modules describe their networks on top of thes
     (single-head mid-block attention with the value bias folded into the output bias), ``Decoder2DWeights`` (the diffusers 2-D decoder);
   * ``StagingCache``: the zero-bordered conv-input buffers kept per geometry; ``VaeBlocks`` on top of it: GroupNorm + SiLU into such a
     buffer, the residual block, the per-frame attention and the body of the diffusers 2-D decoder;
-  * ``attention_core``: q / k GEMMs, batched V^T, chunked fp32 scores, row softmax, P V^T and the out-projection with the residual;
+  * ``attention_core``: q / k GEMMs, batched V^T, then chunked fp32 scores, row softmax and P V^T (up to 8192 keys per frame) or the
+    head-dim-C flash kernel of csrc/attention_vae.hip (above, or with ``VSYS_VAE_FLASH=1``), and the out-projection with the residual;
   * ``stitch_tiles``: the in-place cross-fade and crop of a grid of decoded tiles;
   * ``deal_units`` / ``gather_units`` / ``frame_shards``: who decodes what when the ranks of a group share one decode, and the one
     all-gather that hands every rank every unit;
   * ``synth_weights`` and the parameter-inventory helpers behind every module's ``synth_state_dict`` / ``*_param_shapes``.
 
-Kernels are the ones of csrc/conv_bf16.hip and csrc/vae_ops.hip through ops.py; there is no CPU path."""
+Kernels are the ones of csrc/conv_bf16.hip and csrc/vae_ops.hip through ops.py, and csrc/attention_vae.hip through ``vae_flash_attn``
+here; there is no CPU path."""
 from __future__ import annotations
 
 import math
+import os
 from typing import Callable, Dict, Optional, Sequence, Tuple
 
 import torch
 
-from . import ops
+from . import _lib, ops, program
 from .ops import VaeGrid
 
 
@@ -130,15 +133,47 @@ class Decoder2DWeights:
 
 
 # ---------------------------------------------------------------------------------------------------- launches
+SOFTMAX_MAX_KEYS = 8192                                  # vsys_softmax_rows holds a row in one block's registers: ld <= 8192
+FORCE_FLASH = os.environ.get("VSYS_VAE_FLASH") == "1"    # read once; tests and tools set the attribute
+
+
+def vae_flash_attn(q, k, vt, n, L, Lp, scale, out=None):
+    """Single-head flash attention of the VAE mid blocks (vsys_vae_flash_attn, csrc/attention_vae.hip): per frame
+    softmax(scale q k^T) v over the first L of Lp rows, head dim C = q.shape[1] in (128, 256, 512), any L.  q, k bf16 rows [n * Lp, C]
+    (row-strided views allowed), vt bf16 [n, C, Lp] = V^T per frame (columns L .. Lp - 1 finite), out bf16 rows [n * Lp, C]: rows
+    L .. Lp - 1 of every frame are NOT written.  The entry point has no op code (the launch-program table keeps its size): it is called
+    through ctypes, under a recorder from a host closure that a replay runs again at the same place (as open_sora_plan_ops.conv_down2)."""
+    ops._chk(q, k, vt, out)
+    ops._bf16(q, k, vt, out)
+    C = q.shape[1]
+    assert q.dim() == 2 and k.dim() == 2 and q.shape[0] == n * Lp and tuple(k.shape) == tuple(q.shape) and q.stride(1) == 1 and k.stride(1) == 1
+    assert vt.dim() == 3 and tuple(vt.shape) == (n, C, Lp) and vt.stride(2) == 1 and vt.stride(0) == C * vt.stride(1)
+    if out is None:
+        out = torch.empty(n * Lp, C, dtype=torch.bfloat16, device=q.device)
+    assert tuple(out.shape) == (n * Lp, C) and out.stride(1) == 1
+    program.keep((q, k, vt, out))
+    args = (q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), vt.data_ptr(), vt.stride(1), out.data_ptr(), out.stride(0), n, L, Lp, C,
+            float(scale))
+    fn = _lib.load().vsys_vae_flash_attn
+    program.host_call(lambda: _lib.check(fn(torch.cuda.current_stream().cuda_stream, *args), "vsys_vae_flash_attn"))
+    return out
+
+
 def attention_core(hn, xd, n: int, L: int, Lp: int, C: int, w: AttnWeights):
     """Single-head attention of width C over n frames of L tokens, each frame in Lp rows (Lp = L rounded up to the 128-column GEMM
     tile; the pad rows of ``hn`` and ``xd`` are zero).  hn: the normed rows, xd: the residual rows -> rows [n * Lp, C]
-    (pad rows: finite junk)."""
+    (pad rows: finite junk).  Up to SOFTMAX_MAX_KEYS rows per frame the scores are materialised (three batched GEMMs around the row
+    softmax); above, or with FORCE_FLASH, vae_flash_attn runs between the q / k / V^T GEMMs and the out-projection: no score
+    buffer, no softmax launch, keys L .. Lp - 1 masked in the kernel."""
     dev = hn.device
     q = ops.gemm128(hn, w.wq, w.bq)
     k = ops.gemm128(hn, w.wk, w.bk)
     vt = torch.empty(n, C, Lp, dtype=torch.bfloat16, device=dev)       # V^T per frame = W_v X^T (pad columns = 0)
     ops.gemm128(w.wv, hn.view(n, Lp, C), out=vt, batch=n, batch_a=0, batch_w=Lp * C, batch_o=C * Lp, M=C)
+    if FORCE_FLASH or Lp > SOFTMAX_MAX_KEYS:
+        o = torch.zeros(n * Lp, C, dtype=torch.bfloat16, device=dev)   # (the kernel stores rows < L only; the GEMM below reads all Lp)
+        vae_flash_attn(q, k, vt, n, L, Lp, 1.0 / math.sqrt(C), out=o)
+        return ops.gemm128(o, w.wo, w.bo, res=xd)
     o = torch.empty(n * Lp, C, dtype=torch.bfloat16, device=dev)
     L4 = (L + 3) // 4 * 4
     step = max(1, min(n, (1 << 28) // (Lp * Lp)))                       # <= 1 GiB of fp32 scores at a time

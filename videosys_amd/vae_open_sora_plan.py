@@ -15,7 +15,8 @@ Layout and kernels (DESIGN.md "Open-Sora-Plan CausalVAE decode"):
     its rows.  The kernel pads time with zeros, so the latent is handed over with two copies of its first frame in front and the
     two leading output frames are dropped;
   * GroupNorm (+ SiLU) is vsys_gn_stats / vsys_gn_apply over all frames of the sample, eps 1e-6;
-  * AttnBlock3DFix is GEMMs + vsys_softmax_rows per frame (one head of width C, scale C^-0.5): at most 8192 keys per frame;
+  * AttnBlock3DFix is one head of width C per frame, scale C^-0.5 (vae_blocks.attention_core): GEMMs + vsys_softmax_rows up to 8192
+    keys per frame, the flash kernel vsys_vae_flash_attn (csrc/attention_vae.hip) above that, so a frame may be of any size;
   * SpatialUpsample2x is vsys_regrid(up=1), Spatial2xTime2x3DUpsample is vsys_upsample_trilinear2x, each straight into the padded
     input grid of its conv;
   * tiles are blended by vsys_blend_edge on planar [3, T, H, W] tiles.
@@ -57,7 +58,8 @@ _KCOLS = 128                         # 27 taps x 4 channels = 108 -> the GEMM's 
 
 def check_attention_keys(h: int, w: int) -> int:
     """The per-frame key count of the mid-block attention rounded up to the 128-column GEMM tile; more than the row softmax takes
-    raises (host side, before any launch)."""
+    raises.  No longer a gate of decode / encode (above MAX_KEYS attention_core takes the flash kernel): kept for callers that size
+    tiles for the materialised path."""
     Lp = (h * w + 127) // 128 * 128
     if Lp > MAX_KEYS:
         raise ValueError(f"CausalVAE mid-block attention over {h} x {w} = {h * w} keys per frame: the row softmax takes at most "
@@ -167,7 +169,7 @@ class _CausalBlocks(VaeBlocks):
         """AttnBlock3DFix.forward :375-415 with its residual: one head of width C per frame.  x rows over g (pad 1, no front frames)
         -> dense rows.  Inside, a frame takes the key count rounded up to the 128-column GEMM tile (pad rows zero on input)."""
         C, L, n = aw.C, g.H * g.W, g.T
-        Lp = check_attention_keys(g.H, g.W)
+        Lp = (L + 127) // 128 * 128
         gf = VaeGrid(n, 1, g.H, g.W, g.pad, 0, sample_rows=g.plane)                 # the same rows, one sample per frame
         gdn = VaeGrid(n, 1, g.H, g.W, 0, 0, sample_rows=Lp)
         hn, xd = self._attn_bufs(n, g.H, g.W, C, Lp)
@@ -266,7 +268,6 @@ class CausalVAEDecoder(_CausalBlocks):
     def _decode_tile(self, zt: torch.Tensor, in_scale: float) -> torch.Tensor:
         """zt planar bf16 [4, T, h, w] -> planar bf16 [3, 4(T-1)+1, 8h, 8w]: post_quant_conv + Decoder.forward :713-738."""
         _, T, h, w = zt.shape
-        check_attention_keys(h, w)
         zz = torch.cat([zt[:, :1], zt[:, :1], zt], dim=1).contiguous()              # conv_in's two copies of the first frame
         params = [in_scale] * 4 + [0.0] * 4 + self.pq[0].flatten().tolist() + self.pq[1].tolist()
         a = ops.vae_first_im2col(zz, 3, _KCOLS, params)
@@ -411,7 +412,7 @@ class CausalVAEDecoder(_CausalBlocks):
 
     def tiled_encode(self, x):
         raise NotImplementedError("CausalVAEModel.tiled_encode (:918-940) is not built: call disable_tiling() and encode(x), which takes "
-                                  "the whole clip (the mid-block attention limits a frame to 8192 latent pixels, 720 x 720)")
+                                  "the whole clip at any frame size (the mid-block attention has no key limit)")
 
 
 class DiagonalGaussianDistribution:
@@ -538,7 +539,6 @@ class CausalVAEEncoder(_CausalBlocks):
             raise ValueError(f"expected a video [B, 3, T, H >= 8, W >= 8], got {tuple(x.shape)}")
         B, _, T, H, W = x.shape
         To = ((T - 1) // 2 + 1 - 1) // 2 + 1
-        check_attention_keys(H // 8, W // 8)
         out = torch.empty(B, 8, To, H // 8, W // 8, dtype=torch.bfloat16, device=self.device)
         for b in range(B):
             self._encode_sample(x[b].to(torch.bfloat16), out[b])
