@@ -632,6 +632,20 @@ int vsys_subsample(const void* x, const int64_t* grid_src, void* y, const int64_
  * from a host closure at its place in the launch order (program.host_call), as it does vsys_attn_temporal_d64_img. */
 int vsys_conv_down2_bf16(void* stream, const void* x, int64_t ldx, const int64_t* grid_src, int64_t nsamples, const void* w, int64_t ldw,
                          const void* bias, void* out, int64_t ldo, int64_t cin, int64_t cout, int64_t kt);
+/* Time-pooling stride-2 convolution of the CogVideoX VAE ENCODER (csrc/conv_pool_down_bf16.hip): CogVideoXDownsample3D with
+ * compress_time=True (videosys/models/modules/downsampling.py:40-71 under CogVideoXDownBlock3D, autoencoder_kl_cogvideox.py:302-405) in
+ * one launch.  x rows [*, ldx] over grid_src (any pad / tf; only voxels are read) -> out DENSE rows [nsamples * To * Ho * Wo, ldo]:
+ *   To = T / 2 + (T odd); output frame t' pools frames (2 t', 2 t' + 1) for an even T; for an odd T frame 0 stands alone (t' = 0) and
+ *   t' >= 1 pools (2 t' - 1, 2 t');  m = bf16((x[f0] + x[f1]) / 2), the sum in fp32 and ONE rounding, as F.avg_pool1d on bf16;
+ *   out[t', ho, wo] = bias + sum_{kh, kw, c} m[t', 2 ho + kh, 2 wo + kw, c] w[., (3 kh + kw) cin + c], m = 0 at row H and column W
+ *   (F.pad (0, 1, 0, 1) + Conv2d(3, stride 2)); Ho = H / 2, Wo = W / 2 rounded down.
+ * w_half [cout, 9 cin] holds w / 2 (exact in bf16 for normal weights): the kernel multiplies bf16(x[f0] + x[f1]) by it, which is the
+ * same product.  T = 1 gives vsys_conv_down2_bf16's kt = 1 result on w.  cout % 128 == 0, cin % 32 == 0, T >= 1, H, W >= 2,
+ * nsamples <= 65535, strides % 8 == 0, x / w_half / out 16-byte aligned; a tile of 256 output voxels must span less than 2 GiB of
+ * source rows (VSYS_ERR_SHAPE).  The stream is the FIRST argument, as for vsys_conv_down2_bf16: no VSYS_OP code, the launch-program
+ * table keeps its 75 entries, and a recorded program issues the call from a host closure (program.host_call). */
+int vsys_conv_pool_down2_bf16(void* stream, const void* x, int64_t ldx, const int64_t* grid_src, int64_t nsamples, const void* w_half,
+                              int64_t ldw, const void* bias, void* out, int64_t ldo, int64_t cin, int64_t cout);
 /* CogVideoXSpatialNorm3D + SiLU (autoencoder_kl_cogvideox.py:165-178,275-276): y = silu(GN(x) * Y + B); yb = [conv_y(zq) |
  * conv_b(zq)] computed at LATENT resolution, rows (n, zt, zh, zw) of 2C columns; the latent voxel of (t, h, w) follows
  * F.interpolate(zq, size=f.shape) including the first-frame split for odd frame counts.  stats from vsys_gn_stats. */

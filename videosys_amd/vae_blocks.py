@@ -12,8 +12,9 @@ vae_open_sora_plan.py): the model modules describe their networks on top of thes
     all-gather that hands every rank every unit;
   * ``synth_weights`` and the parameter-inventory helpers behind every module's ``synth_state_dict`` / ``*_param_shapes``.
 
-Kernels are the ones of csrc/conv_bf16.hip and csrc/vae_ops.hip through ops.py, and csrc/attention_vae.hip through ``vae_flash_attn``
-here; there is no CPU path."""
+Kernels are the ones of csrc/conv_bf16.hip and csrc/vae_ops.hip through ops.py, csrc/attention_vae.hip through ``vae_flash_attn`` and
+csrc/conv_pool_down_bf16.hip (the time-pooling downsample of the CogVideoX encoder) through ``conv_pool_down2`` here; there is no CPU
+path."""
 from __future__ import annotations
 
 import math
@@ -157,6 +158,40 @@ def vae_flash_attn(q, k, vt, n, L, Lp, scale, out=None):
     fn = _lib.load().vsys_vae_flash_attn
     program.host_call(lambda: _lib.check(fn(torch.cuda.current_stream().cuda_stream, *args), "vsys_vae_flash_attn"))
     return out
+
+
+def pool_down2_grid(grid: VaeGrid) -> VaeGrid:
+    """The dense output grid of ``conv_pool_down2`` over ``grid``: T / 2 frames, plus the lone first frame when T is odd, of
+    H / 2 x W / 2 (rounded down)."""
+    return VaeGrid(grid.n, grid.T // 2 + grid.T % 2, grid.H // 2, grid.W // 2, 0, 0)
+
+
+def conv_pool_down2(x, grid: VaeGrid, w_half, bias, cin, out=None):
+    """CogVideoXDownsample3D(compress_time=True) in one launch (vsys_conv_pool_down2_bf16, csrc/conv_pool_down_bf16.hip): the mean of
+    each frame pair of ``grid`` — frame 0 alone, then (1, 2), (3, 4) ... when T is odd — rounded to bf16 once, under the stride-2 3 x 3
+    convolution with one implicit zero row below and one zero column to the right.  ``x``: rows over ``grid`` (any pad / tf: borders and
+    front frames are NOT read).  ``w_half`` [cout, 9 cin], k = tap * cin + channel, is the layer's weight matrix TIMES 1/2: the 1/2 of the
+    mean is folded into the weights once when they are loaded (``half_weights``; exact in bf16 unless a weight is subnormal) and the
+    kernel multiplies bf16(x[f0] + x[f1]) by it, which is the same product.  Returns the dense rows of ``pool_down2_grid(grid)``
+    [rows, cout].  No op code: issued through ctypes, under a recorder from a host closure (as ``vae_flash_attn``)."""
+    ops._chk(x, w_half, bias, out)
+    ops._bf16(x, w_half, bias, out)
+    assert x.shape[0] == grid.rows and x.stride(1) == 1 and x.shape[1] >= cin and w_half.shape[1] == 9 * cin and w_half.stride(1) == 1
+    og = pool_down2_grid(grid)
+    if out is None:
+        out = torch.empty(og.rows, w_half.shape[0], dtype=torch.bfloat16, device=x.device)
+    assert out.shape[0] == og.rows and out.stride(1) == 1
+    program.keep((x, w_half, bias, out, grid))
+    args = (x.data_ptr(), x.stride(0), grid._c, grid.n, w_half.data_ptr(), w_half.stride(0), None if bias is None else bias.data_ptr(),
+            out.data_ptr(), out.stride(0), cin, w_half.shape[0])
+    fn = _lib.load().vsys_conv_pool_down2_bf16
+    program.host_call(lambda: _lib.check(fn(torch.cuda.current_stream().cuda_stream, *args), "vsys_conv_pool_down2_bf16"))
+    return out
+
+
+def half_weights(w: torch.Tensor) -> torch.Tensor:
+    """bf16 w / 2 for ``conv_pool_down2``: an exponent step, exact for every normal bf16 weight."""
+    return (w.float() * 0.5).to(torch.bfloat16).contiguous()
 
 
 def attention_core(hn, xd, n: int, L: int, Lp: int, C: int, w: AttnWeights):

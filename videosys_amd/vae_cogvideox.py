@@ -1,4 +1,4 @@
-"""CogVideoX causal 3-D VAE decode on MI355X (``AutoencoderKLCogVideoX.tiled_decode``).
+"""CogVideoX causal 3-D VAE on MI355X: decode (``AutoencoderKLCogVideoX.tiled_decode``) and encode.
 
 Mirrors the decode side of the reference ``AutoencoderKLCogVideoX`` (videosys/models/autoencoders/autoencoder_kl_cogvideox.py):
 ``decode`` (:1121-1143) -> ``_decode`` (:1094-1119, frame batches of 2 latent frames whose causal convolutions hand their last
@@ -12,17 +12,26 @@ the conv-input buffer, filled from the layer's cache or with copies of the first
 conv_y(zq) | conv_b(zq) ONCE per norm at latent resolution (a 32-wide GEMM) and applies them inside the GroupNorm/SiLU kernel with
 the nearest-neighbour index map of F.interpolate.  The staging cache, the conv weight holder, the tile stitching and the weight
 synthesiser are the shared ones of vae_blocks.py; the spatial-norm residual block with its conv cache is this module's own.  No CPU path.
+
+The encode side (``encode`` :1071-1092 over ``CogVideoXEncoder3D`` :597-728, ``CogVideoXDownBlock3D`` :302-405 and
+``CogVideoXDownsample3D``, modules/downsampling.py:40-71) is built when the state dict holds ``encoder.*``: the same causal
+convolutions behind plain GroupNorm + SiLU (``zq`` is None there), the per-frame stride-2 convolution of csrc/conv_down_bf16.hip after
+down block 2, and after down blocks 0 and 1 the time-pooling stride-2 convolution of csrc/conv_pool_down_bf16.hip, which averages the
+frame pairs on its way to the MFMAs (no pooled copy of the activation).
 """
 from __future__ import annotations
 
 import math
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 
+from . import open_sora_plan_ops as oops
 from . import ops
 from .ops import VaeGrid
-from .vae_blocks import StagingCache, _Conv, conv3, deal_units, stitch_tiles, synth_weights
+from .vae_blocks import (VaeBlocks, _Conv, _Norm, _vec, conv3, conv_pool_down2, deal_units, half_weights, norm, pool_down2_grid,
+                         stitch_tiles, synth_weights)
+from .vae_open_sora_plan import DiagonalGaussianDistribution
 
 
 class _SNorm:
@@ -46,8 +55,25 @@ class _CRes:
         self.sc = _Conv(sd, p + ".conv_shortcut", dev) if (p + ".conv_shortcut.weight") in sd else None
 
 
-class CogVideoXVAE(StagingCache):
-    """Decode side of AutoencoderKLCogVideoX.  ``decode(z)``: z [B, 16, T, H, W] -> [B, 3, T_out, 8H, 8W] bf16."""
+class _ERes:
+    """Encoder resnet (CogVideoXResnetBlock3D with ``zq`` None): plain GroupNorm (eps 1e-6), causal 3x3x3 convs, 1x1 shortcut."""
+
+    def __init__(self, sd, p, dev):
+        self.n1, self.n2 = _Norm(sd, p + ".norm1", dev, 1e-6), _Norm(sd, p + ".norm2", dev, 1e-6)
+        self.c1, self.c2 = _Conv(sd, p + ".conv1.conv", dev), _Conv(sd, p + ".conv2.conv", dev)
+        self.sc = _Conv(sd, p + ".conv_shortcut", dev) if (p + ".conv_shortcut.weight") in sd else None
+
+
+class AutoencoderKLOutput:
+    """What ``encode`` returns with ``return_dict=True``: ``latent_dist``, the posterior."""
+
+    def __init__(self, latent_dist):
+        self.latent_dist = latent_dist
+
+
+class CogVideoXVAE(VaeBlocks):
+    """AutoencoderKLCogVideoX.  ``decode(z)``: z [B, 16, T, H, W] -> [B, 3, T_out, 8H, 8W] bf16; ``encode(x)``: x [B, 3, T, H, W] ->
+    the posterior over [B, 16, T / 4 (+ 1 for an odd T), H / 8, W / 8], when the state dict holds the ``encoder.*`` tensors."""
 
     num_latent_frames_batch_size = 2
     tile_overlap_factor_height = 1 / 6
@@ -81,6 +107,29 @@ class CogVideoXVAE(StagingCache):
             self.ups.append((res, _Conv(sd, uk, dev) if (uk + ".weight") in sd else None, i < level))
         self.norm_out = _SNorm(sd, d + "norm_out", dev)
         self.conv_out = _Conv(sd, d + "conv_out.conv", dev, n_pad=128)
+        self._enc_missing = sorted(set(encoder_param_shapes()) - set(sd))
+        if not self._enc_missing:
+            self._build_encoder(sd, dev, level)
+
+    def _build_encoder(self, sd, dev, level):
+        """CogVideoXEncoder3D.__init__ :621-692: the first ``level`` down blocks compress time."""
+        e = "encoder."
+        self.enc_conv_in = _Conv(sd, e + "conv_in.conv", dev, cin_pad=32)
+        self.enc_down = []
+        for i in range(4):
+            res = [_ERes(sd, f"{e}down_blocks.{i}.resnets.{j}", dev) for j in range(3)]
+            down = _Conv(sd, f"{e}down_blocks.{i}.downsamplers.0.conv", dev) if i < 3 else None
+            if down is not None and i < level:
+                down.w = half_weights(down.w)                    # the 1/2 of the frame-pair mean (vae_blocks.conv_pool_down2)
+            self.enc_down.append((res, down, i < level))
+        self.enc_mid = [_ERes(sd, f"{e}mid_block.resnets.{i}", dev) for i in range(2)]
+        self.enc_norm_out = _Norm(sd, e + "norm_out", dev, 1e-6)
+        self.enc_conv_out = _Conv(sd, e + "conv_out.conv", dev, n_pad=128)       # 32 of 128 columns carry the moments
+        self.quant_w = None
+        if "quant_conv.weight" in sd:                                            # use_quant_conv (:965); the published config has none
+            self.quant_w = torch.zeros(128, 128, dtype=torch.bfloat16, device=dev)
+            self.quant_w[:32, :32] = sd["quant_conv.weight"].to(dev).reshape(32, 32).to(torch.bfloat16)
+            self.quant_b = _vec(sd["quant_conv.bias"].to(dev), 128)
 
     def enable_tiling(self):
         self.use_tiling = True
@@ -249,6 +298,89 @@ class CogVideoXVAE(StagingCache):
             rows = [[self._decode_tile(zb[:, :, i:i + tl_h, j:j + tl_w].contiguous()) for j in range(0, W, ov_w)] for i in range(0, H, ov_h)]
         return stitch_tiles(rows, be_h, be_w, lim_h, lim_w).contiguous()
 
+    # ------------------------------------------------------------------------------------------------ encode side
+    @staticmethod
+    def _front_first(rows, g: VaeGrid):
+        """The two frames in front of a causal conv's input = copies of its first frame (fake_context_parallel_forward :112-117 with
+        an empty cache), as a launch (vsys_regrid, destination frame t reads source frame t / 2) so that a recorded encode replays it."""
+        ops.regrid(rows[2 * g.plane:3 * g.plane], VaeGrid(1, 1, g.H, g.W, g.pad, 0), rows[:2 * g.plane],
+                   VaeGrid(1, 2, g.H, g.W, g.pad, 0), rows.shape[1], tmode=1)
+
+    def _enc_conv(self, h, gh: VaeGrid, cv: _Conv, res=None):
+        self._front_first(h, gh)
+        return ops.conv(h, gh, cv.w, cv.b, cv.cin, 3, 3, res=res)
+
+    def _enc_resnet(self, x, gx: VaeGrid, r: _ERes):
+        """CogVideoXResnetBlock3D.forward :267-299 with zq None; x rows over gx (any layout) -> rows over the conv-output grid."""
+        h, gh = self._norm_act(x, gx, r.n1, r.c1.cin, 2)
+        y = self._enc_conv(h, gh, r.c1)
+        go = gh.conv_out()
+        h2, gh2 = self._norm_act(y, go, r.n2, r.c2.cin, 2)
+        if gx.pad != 1 or gx.tf != 0:       # the residual is added row-for-row in the conv-output layout
+            xr = torch.empty(go.rows, x.shape[1], dtype=torch.bfloat16, device=self.device)
+            ops.regrid(x, gx, xr, go, x.shape[1])
+            x = xr
+        res = x if r.sc is None else ops.gemm128(x, r.sc.w, r.sc.b)
+        return self._enc_conv(h2, gh2, r.c2, res=res), go
+
+    def _encode_sample(self, xs: torch.Tensor, out: torch.Tensor) -> None:
+        """xs planar bf16 [3, T, H, W] -> out planar bf16 [32, To, h, w] (mean | logvar): CogVideoXEncoder3D.forward :694-728 and the
+        optional quant_conv (:1087-1088)."""
+        _, T, H, W = xs.shape
+        xrows = torch.zeros(T * H * W, 32, dtype=torch.bfloat16, device=self.device)       # the clip staged channels-last, cin 3 -> 32
+        xrows[:, :3] = xs.permute(1, 2, 3, 0).reshape(-1, 3)
+        gp = VaeGrid(1, T, H, W, 1, 2)
+        xin = self._padded_buf(gp, 32)
+        ops.regrid(xrows, VaeGrid(1, T, H, W, 0, 0), xin, gp, 32)
+        x, g = self._enc_conv(xin, gp, self.enc_conv_in), gp.conv_out()
+        for res, down, compress_time in self.enc_down:
+            for r in res:
+                x, g = self._enc_resnet(x, g, r)
+            if down is None:
+                continue
+            if compress_time:                                   # CogVideoXDownsample3D, compress_time=True: pooled in the kernel
+                x, g = conv_pool_down2(x, g, down.w, down.b, down.cin), pool_down2_grid(g)
+            else:                                               # F.pad (0, 1, 0, 1) + Conv2d(stride 2) per frame
+                x, g = oops.conv_down2(x, g, down.w, down.b, down.cin, 1), g.down2(1)
+        for r in self.enc_mid:
+            x, g = self._enc_resnet(x, g, r)
+        hN, gN = self._norm_act(x, g, self.enc_norm_out, self.enc_conv_out.cin, 2)
+        m = self._enc_conv(hN, gN, self.enc_conv_out)
+        if self.quant_w is not None:
+            m = ops.gemm128(m, self.quant_w, self.quant_b)
+        for c in range(0, 32, 4):                               # (the kernel moves <= 4 channels a call)
+            ops.extract_planar(m[:, c:], gN.conv_out(), 4, 0, out[c:c + 4], 0)
+
+    @torch.no_grad()
+    def moments(self, x: torch.Tensor) -> torch.Tensor:
+        """x [B, 3, T, H, W] -> bf16 moments [B, 32, To, H / 8, W / 8] (mean | logvar).  Under a launch-program recorder the clip is
+        staged by torch copies before the first launch: a replay encodes that staged copy again, not a new ``x``."""
+        if self._enc_missing:
+            raise RuntimeError(f"this CogVideoXVAE was built from a state dict without encoder weights (decode only); missing "
+                               f"{self._enc_missing[:4]}{' ...' if len(self._enc_missing) > 4 else ''}")
+        if not x.is_cuda:
+            raise RuntimeError("CogVideoXVAE.encode needs a HIP device tensor (no CPU path)")
+        if x.dim() != 5 or x.shape[1] != 3 or x.shape[-1] < 8 or x.shape[-2] < 8:
+            raise ValueError(f"expected a video [B, 3, T, H >= 8, W >= 8], got {tuple(x.shape)}")
+        B, _, T, H, W = x.shape
+        To = T
+        for _res, down, compress_time in self.enc_down:
+            To = To // 2 + To % 2 if (down is not None and compress_time) else To
+        out = torch.empty(B, 32, To, H // 8, W // 8, dtype=torch.bfloat16, device=self.device)
+        for b in range(B):
+            self._encode_sample(x[b].to(torch.bfloat16), out[b])
+        return out
+
+    def encode(self, x: torch.Tensor, return_dict: bool = True):
+        """AutoencoderKLCogVideoX.encode :1071-1092: x [B, 3, T, H, W] -> ``AutoencoderKLOutput(latent_dist=posterior)``, or the
+        1-tuple ``(posterior,)``; the posterior (vae_open_sora_plan.DiagonalGaussianDistribution) holds ``mean``, ``logvar``,
+        ``mode()`` and ``sample(generator=)`` in fp32.  All frames go through in ONE pass, as in the reference (GroupNorm spans every
+        frame), and every causal convolution starts from a FRESH state — the first frame replicated.  The reference's ``encode``
+        never clears its ``conv_cache``, so a second call there reads the tail of the first call's clip; that is not reproduced:
+        equal inputs give equal bits here."""
+        posterior = DiagonalGaussianDistribution(self.moments(x))
+        return AutoencoderKLOutput(posterior) if return_dict else (posterior,)
+
     def decode_latents(self, latents: torch.Tensor, group=None) -> torch.Tensor:
         """pipeline_cogvideox.py:359-364: latents [B, T, 16, H, W] -> frames [B, 3, T_out, 8H, 8W] (``group``: see decode)."""
         z = latents.permute(0, 2, 1, 3, 4)
@@ -259,7 +391,7 @@ class CogVideoXVAE(StagingCache):
 
 
 # ---------------------------------------------------------------------------------------------------- synthetic weights
-AutoencoderKLCogVideoX = CogVideoXVAE   # the reference's class name (autoencoder_kl_cogvideox.py); decode side only
+AutoencoderKLCogVideoX = CogVideoXVAE   # the reference's class name (autoencoder_kl_cogvideox.py): decode, and encode with encoder.*
 
 
 def decoder_param_shapes() -> Dict[str, tuple]:
@@ -306,6 +438,42 @@ _SYNTH_RULES = ((".conv_y.conv.weight", lambda r, fan_in: r / math.sqrt(fan_in) 
                 (".conv_b.conv.bias", lambda r, fan_in: 0.02 * r))
 
 
-def synth_state_dict(seed: int = 0) -> Dict[str, torch.Tensor]:
-    """Deterministic random decode-side weights (vae_blocks.synth_weights with the rules above; bf16-representable fp32)."""
-    return synth_weights(decoder_param_shapes(), torch.Generator().manual_seed(seed), rules=_SYNTH_RULES)
+def encoder_param_shapes() -> Dict[str, tuple]:
+    """Encode-side parameters of the reference AutoencoderKLCogVideoX in its published configuration (no quant_conv), in state-dict
+    order (checked against the reference's own names and shapes through tests/golden/cogvideox_vae_encode_small.pt)."""
+    p: Dict[str, tuple] = {}
+
+    def res(name, ci, co):
+        norm(p, name + ".norm1", ci)
+        norm(p, name + ".norm2", co)
+        conv3(p, name + ".conv1", ci, co, 3)
+        conv3(p, name + ".conv2", co, co, 3)
+        if ci != co:
+            p[name + ".conv_shortcut.weight"] = (co, ci, 1, 1, 1)
+            p[name + ".conv_shortcut.bias"] = (co,)
+
+    e = "encoder."
+    conv3(p, e + "conv_in", 3, 128, 3)
+    prev = 128
+    for i, co in enumerate((128, 256, 256, 512)):
+        for j in range(3):
+            res(f"{e}down_blocks.{i}.resnets.{j}", prev, co)
+            prev = co
+        if i < 3:
+            p[f"{e}down_blocks.{i}.downsamplers.0.conv.weight"] = (co, co, 3, 3)
+            p[f"{e}down_blocks.{i}.downsamplers.0.conv.bias"] = (co,)
+    for i in range(2):
+        res(f"{e}mid_block.resnets.{i}", 512, 512)
+    norm(p, e + "norm_out", 512)
+    conv3(p, e + "conv_out", 512, 32, 3)
+    return p
+
+
+def synth_state_dict(seed: int = 0, encoder: bool = False) -> Dict[str, torch.Tensor]:
+    """Deterministic random decode-side weights (vae_blocks.synth_weights with the rules above; bf16-representable fp32).
+    ``encoder``: the ``encoder.*`` tensors as well, drawn from a generator of their own (seeded from ``seed``), so the decoder tensors
+    of a seed keep their bits."""
+    sd = synth_weights(decoder_param_shapes(), torch.Generator().manual_seed(seed), rules=_SYNTH_RULES)
+    if encoder:
+        sd.update(synth_weights(encoder_param_shapes(), torch.Generator().manual_seed(seed + 0x5EED0)))
+    return sd
