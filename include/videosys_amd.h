@@ -646,6 +646,20 @@ int vsys_conv_down2_bf16(void* stream, const void* x, int64_t ldx, const int64_t
  * table keeps its 75 entries, and a recorded program issues the call from a host closure (program.host_call). */
 int vsys_conv_pool_down2_bf16(void* stream, const void* x, int64_t ldx, const int64_t* grid_src, int64_t nsamples, const void* w_half,
                               int64_t ldw, const void* bias, void* out, int64_t ldo, int64_t cin, int64_t cout);
+/* Temporal downsampler of the Open-Sora-Plan v1.1 CausalVAE ENCODER (csrc/conv_time_down_bf16.hip): TimeDownsampleRes2x
+ * (autoencoder_kl_open_sora_plan_v110.py:1557-1575) in one launch, TimeDownsample2x (:1533-1542) with w_s == NULL.  x rows [*, ldx] over
+ * grid_src (any pad / tf; only voxels are read) -> out DENSE rows [nsamples * To * H * W, ldo], To = (T - 1) / 2 + 1 (T = 1 and T = 2
+ * give one frame; an even T leaves its last frame unread).  Tap (a, kh, kw) of output (t', h, w) reads frame max(2 t' + a - 2, 0) at
+ * (h + kh - 1, w + kw - 1), zero outside 0..H-1 / 0..W-1; w_s [C, 27 C], k = ((a 3 + kh) 3 + kw) C + c.  All in fp32, one rounding:
+ *   out = bf16(acc + bias_s + a3 * ((x0 + x1) + x2))       acc over w_s; x0..x2 the three source frames at the output's (h, w, column)
+ * with w_s = bf16((1 - alpha) w), bias_s = bf16((1 - alpha) b) (scaled in fp32 before their one rounding), a3 = fp32(alpha / 3),
+ * alpha = sigmoid(mix_factor).  w_s == NULL (bias_s and a3 unused): out = bf16(((x0 + x1) + x2) * fp32(1 / 3)).
+ * C % 128 == 0 with weights, C % 8 == 0 without; T >= 1, H, W >= 2, nsamples <= 65535, a tile of 256 output voxels must span less than
+ * 2 GiB of source rows (VSYS_ERR_SHAPE); strides % 8 == 0, x / w_s / out 16-byte aligned (VSYS_ERR_ALIGN); 0 <= a3 <= fp32(1 / 3)
+ * (VSYS_ERR_ARG).  The stream is the FIRST argument, as for vsys_conv_down2_bf16: no VSYS_OP code, the launch-program table keeps its
+ * 75 entries, and a recorded program issues the call from a host closure (program.host_call). */
+int vsys_conv_time_down2_bf16(void* stream, const void* x, int64_t ldx, const int64_t* grid_src, int64_t nsamples, const void* w_s, int64_t ldw,
+                              const void* bias_s, void* out, int64_t ldo, int64_t C, float a3);
 /* CogVideoXSpatialNorm3D + SiLU (autoencoder_kl_cogvideox.py:165-178,275-276): y = silu(GN(x) * Y + B); yb = [conv_y(zq) |
  * conv_b(zq)] computed at LATENT resolution, rows (n, zt, zh, zw) of 2C columns; the latent voxel of (t, h, w) follows
  * F.interpolate(zq, size=f.shape) including the first-frame split for odd frame counts.  stats from vsys_gn_stats. */

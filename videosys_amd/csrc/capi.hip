@@ -763,6 +763,14 @@ int vsys_conv_pool_down2_bf16(void* stream, const void* x, int64_t ldx, const in
   return launch_conv_pool_down2(B16(x), ldx, gs, nsamples, B16(w_half), ldw, B16(bias), B16(out), ldo, cin, cout, S(stream));
 }
 
+int vsys_conv_time_down2_bf16(void* stream, const void* x, int64_t ldx, const int64_t* grid_src, int64_t nsamples, const void* w_s, int64_t ldw,
+                              const void* bias_s, void* out, int64_t ldo, int64_t C, float a3) {
+  VaeGrid gs;
+  if (!x || !out || !to_grid(grid_src, gs)) return VSYS_ERR_ARG;       // (w_s == NULL is the pool-only mode)
+  if (!fits_int(ldx, ldw, ldo, nsamples, C)) return VSYS_ERR_SHAPE;
+  return launch_conv_time_down2(B16(x), ldx, gs, nsamples, B16(w_s), ldw, B16(bias_s), B16(out), ldo, C, a3, S(stream));
+}
+
 int vsys_spatial_norm_apply(const void* x, const int64_t* grid_src, void* y, const int64_t* grid_dst, int64_t N, int64_t C,
                             int64_t groups, const void* stats_f32, const void* gamma, const void* beta, const void* yb, int64_t zT,
                             int64_t zH, int64_t zW, void* stream) {

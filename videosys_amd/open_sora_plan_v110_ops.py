@@ -1,11 +1,12 @@
 """Tensor-level wrappers of the entry points that exist for Open-Sora-Plan v1.1 (include/videosys_amd.h): the head-dim-72 spatial
 attention with a per-token rotation of interleaved column pairs, vsys_attn_prep_kv_rope (K side, writes the (kp, vt) pair of
 ops.attn_prep_kv) and vsys_flash_attn_d72_rope (Q side, the streaming 32-rows-per-wave flash kernel), and, at the end of the file, the
-temporal upsampler of its CausalVAE and its sampler step (vsys_upsample_time2x, vsys_cfg_pndm_step).  HIP device tensors only, no eager
-fallback.
+temporal upsampler of its CausalVAE and its sampler step (vsys_upsample_time2x, vsys_cfg_pndm_step) and the temporal downsampler of the
+CausalVAE's encoder (vsys_conv_time_down2_bf16).  HIP device tensors only, no eager fallback.
 
-Every entry point here has an op code and goes through ``ops._call``, as in open_sora_plan_ops.py: a recorded step replays the two
-attention launches inside its vsys_program_run call.
+Every entry point here but the last has an op code and goes through ``ops._call``, as in open_sora_plan_ops.py: a recorded step replays
+the two attention launches inside its vsys_program_run call.  vsys_conv_time_down2_bf16 has no op code: ``conv_time_down2`` calls it
+through ctypes from a ``program.host_call`` closure, as ``open_sora_plan_ops.conv_down2`` does.
 Element-wise tests: tests/test_gpu_osp_v110_attention.py, tests/test_gpu_osp_v110_kernels.py; guard bands:
 tests/test_gpu_isolation_osp_v110.py, tests/test_gpu_isolation_osp_v110_pipeline.py."""
 from __future__ import annotations
@@ -14,7 +15,7 @@ import ctypes
 
 import torch
 
-from . import program
+from . import _lib, program
 from .ops import HEAD_DIM, VT_ROWS, VaeGrid, _bf16, _call, _chk, _p, alloc_kv_buffers, kv_pad_len  # noqa: F401  (alloc_kv_buffers, kv_pad_len: re-exported)
 
 PAIRS = HEAD_DIM // 2    # 36 (cos, sin) entries per token: entry p rotates the columns (2p, 2p + 1) of every head
@@ -111,3 +112,32 @@ def cfg_pndm_step(model_out, model_in, z_out, guidance, c_base, cz, ca=None, bas
     _call("vsys_cfg_pndm_step", _p(model_out), _p(e_out), *[_p(t) for t in srcs], _p(base), _p(z_out), _p(aux_out), _p(model_in), Bz, Cin,
           2 * Cin, thw, coef)
     return z_out, model_in
+
+
+# ------------------------------------------------------------------------------------------------ CausalVAE encode
+def time_down2_grid(grid: VaeGrid) -> VaeGrid:
+    """The dense output grid of ``conv_time_down2`` over ``grid``: (T - 1) // 2 + 1 frames of the same H x W."""
+    return VaeGrid(grid.n, (grid.T - 1) // 2 + 1, grid.H, grid.W, 0, 0)
+
+
+def conv_time_down2(x, grid: VaeGrid, w_s, bias_s, C, a3, out=None):
+    """TimeDownsampleRes2x in one launch (vsys_conv_time_down2_bf16, csrc/conv_time_down_bf16.hip): the 3 x 3 x 3 convolution of the voxels
+    of ``grid`` (rows ``x``, any pad / tf: borders and front frames are NOT read) with stride 2 in time behind two copies of the first
+    frame and one implicit zero row / column on every side, plus a3 times the sum of the same three frames at the output's own voxel and
+    column.  ``w_s`` [C, 27 C] (k = tap * C + channel) and ``bias_s`` hold (1 - alpha) w and (1 - alpha) b, ``a3`` = alpha / 3.
+    ``w_s`` None: TimeDownsample2x, the mean of the three frames alone (``bias_s`` and ``a3`` are not used).  Returns the dense rows
+    of ``time_down2_grid(grid)`` [rows, C].  No op code: issued through ctypes, under a recorder from a host closure."""
+    _chk(x, w_s, bias_s, out)
+    _bf16(x, w_s, bias_s, out)
+    assert x.shape[0] == grid.rows and x.stride(1) == 1 and x.shape[1] >= C
+    assert w_s is None or (tuple(w_s.shape) == (C, 27 * C) and w_s.stride(1) == 1)
+    og = time_down2_grid(grid)
+    if out is None:
+        out = torch.empty(og.rows, C, dtype=torch.bfloat16, device=x.device)
+    assert out.shape[0] == og.rows and out.shape[1] >= C and out.stride(1) == 1
+    program.keep((x, w_s, bias_s, out, grid))
+    args = (x.data_ptr(), x.stride(0), grid._c, grid.n, None if w_s is None else w_s.data_ptr(), 0 if w_s is None else w_s.stride(0),
+            None if bias_s is None else bias_s.data_ptr(), out.data_ptr(), out.stride(0), C, float(a3))
+    fn = _lib.load().vsys_conv_time_down2_bf16
+    program.host_call(lambda: _lib.check(fn(torch.cuda.current_stream().cuda_stream, *args), "vsys_conv_time_down2_bf16"))
+    return out

@@ -459,14 +459,29 @@ class CausalVAEEncoder(_CausalBlocks):
     before them wrote (no padded copy, no sampled stride-1 convolution), quant_conv is a GEMM on conv_out's rows.  H and W need not be
     multiples of 8 (every level halves rounding down, as the reference's padding does)."""
 
+    # what an encoder of the same family with other downsamplers overrides (vae_open_sora_plan_v110.py)
+    SPATIAL = ENCODER_CONFIG["encoder_spatial_downsample"]
+    _check = staticmethod(_check_encoder_config)
+
+    @staticmethod
+    def _param_shapes(hidden_size: int) -> Dict[str, tuple]:
+        return encoder_param_shapes(hidden_size)
+
+    def _level_extra(self, sd, lvl: int, cm: _ChanMap, dev) -> None:
+        """Weights a level holds beside its residual blocks and its spatial downsampler (none in v1.2)."""
+
+    def _after_level(self, x, g: VaeGrid, lvl: int):
+        """What a level runs after its spatial downsampler (nothing in v1.2)."""
+        return x, g
+
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", hidden_size: Optional[int] = None, **config):
-        _check_encoder_config(config)
+        self._check(config)
         super().__init__(device)
         dev, sd, e = self.device, state_dict, "encoder."
         hs = sd[e + "conv_in.conv.weight"].shape[0]
         if hidden_size is not None and hidden_size != hs:
             raise ValueError(f"hidden_size {hidden_size}, but encoder.conv_in.conv.weight has {hs} output channels")
-        missing = sorted(set(encoder_param_shapes(hs)) - set(sd))
+        missing = sorted(set(self._param_shapes(hs)) - set(sd))
         if missing:
             raise KeyError(f"CausalVAE encoder: the state dict lacks {missing[:4]}{' ...' if len(missing) > 4 else ''}")
         self.hidden_size = hs
@@ -480,14 +495,15 @@ class CausalVAEEncoder(_CausalBlocks):
         self.conv_in_b = first.out_rows(sd[e + "conv_in.conv.bias"]).to(dev).to(torch.bfloat16).contiguous()
         self.down = []
         prev = first
-        for lvl, kind in enumerate(ENCODER_CONFIG["encoder_spatial_downsample"]):
+        for lvl, kind in enumerate(self.SPATIAL):
             co = cm[hs * HIDDEN_SIZE_MULT[lvl]]
             res = []
             for j in range(2):
                 res.append(_CRes(sd, f"{e}down.{lvl}.block.{j}", dev, prev, co))
                 prev = co
-            key = f"{e}down.{lvl}.downsample" + (".conv" if kind.startswith("Spatial2x") else "")
+            key = f"{e}down.{lvl}.downsample" + (".conv" if kind.startswith("Spatial") else "")      # (Downsample holds a plain Conv2d)
             self.down.append((res, _CConv(sd, key, dev, co, co) if kind else None))
+            self._level_extra(sd, lvl, co, dev)
         top = prev
         self.mid = [_CRes(sd, f"{e}mid.block_{i}", dev, top, top) for i in (1, 2)]
         a = e + "mid.attn_1."
@@ -516,11 +532,12 @@ class CausalVAEEncoder(_CausalBlocks):
         a = ops.vae_first_im2col(z4, 3, _KCOLS, _IDENT)
         x = ops.gemm128(a, self.conv_in_w, self.conv_in_b)[2 * H * W:]
         g = VaeGrid(1, T, H, W, 0, 0)
-        for res, down in self.down:
+        for lvl, (res, down) in enumerate(self.down):
             for r in res:
                 x, g = self._resblock(x, g, r)
             if down is not None:                                                     # Downsample :430-464 (kt 1) / Spatial2xTime2x3DDownsample :418-427
                 x, g = oops.conv_down2(x, g, down.w, down.b, down.cin, down.kt), g.down2(down.kt)
+            x, g = self._after_level(x, g, lvl)
         x, g = self._resblock(x, g, self.mid[0])
         x, g = self._attention(x, g, self.attn)
         x, g = self._resblock(x, g, self.mid[1])
@@ -627,9 +644,11 @@ def decoder_param_shapes(hidden_size: int = 128, spatial=SPATIAL_UPSAMPLE, tempo
     return p
 
 
-def encoder_param_shapes(hidden_size: int = 128) -> Dict[str, tuple]:
+def encoder_param_shapes(hidden_size: int = 128, spatial=ENCODER_CONFIG["encoder_spatial_downsample"], temporal=("",) * 4) -> Dict[str, tuple]:
     """Names and shapes of the encode-side parameters of the reference CausalVAEModel in the configuration ``ENCODER_CONFIG`` (checked
-    against its own state_dict through tests/golden/osp_vae_encode_small.pt): ``encoder.*`` and ``quant_conv.*``."""
+    against its own state_dict through tests/golden/osp_vae_encode_small.pt): ``encoder.*`` and ``quant_conv.*``.  ``spatial`` /
+    ``temporal``: the downsampler class per level (the v1.2 ones by default; the v1.1 encoder of vae_open_sora_plan_v110.py passes its
+    own: ``SpatialDownsample2x`` is a causal (1, 3, 3) conv, a ``TimeDownsampleRes2x`` holds ``mix_factor`` and a plain 3 x 3 x 3 Conv3d)."""
     p: Dict[str, tuple] = {}
     hs, e = hidden_size, "encoder."
 
@@ -641,7 +660,7 @@ def encoder_param_shapes(hidden_size: int = 128) -> Dict[str, tuple]:
 
     conv3(p, e + "conv_in", 3, hs, 3)
     prev = hs
-    for lvl, kind in enumerate(ENCODER_CONFIG["encoder_spatial_downsample"]):
+    for lvl, kind in enumerate(spatial):
         co = hs * HIDDEN_SIZE_MULT[lvl]
         for j in range(2):
             res(f"{e}down.{lvl}.block.{j}", prev, co)
@@ -649,7 +668,10 @@ def encoder_param_shapes(hidden_size: int = 128) -> Dict[str, tuple]:
         if kind == "Downsample":
             p[f"{e}down.{lvl}.downsample.conv.weight"], p[f"{e}down.{lvl}.downsample.conv.bias"] = (co, co, 3, 3), (co,)
         elif kind:
-            conv3(p, f"{e}down.{lvl}.downsample.conv", co, co, 3)
+            conv3(p, f"{e}down.{lvl}.downsample.conv", co, co, (1, 3, 3) if kind == "SpatialDownsample2x" else 3)
+        if temporal[lvl] == "TimeDownsampleRes2x":
+            p[f"{e}down.{lvl}.time_downsample.mix_factor"] = (1,)
+            conv3(p, f"{e}down.{lvl}.time_downsample", co, co, 3)                    # a plain nn.Conv3d: ``time_downsample.conv.*``
     res(e + "mid.block_1", prev, prev)
     norm(p, e + "mid.attn_1.norm", prev)
     for n in ("q", "k", "v", "proj_out"):
