@@ -17,48 +17,37 @@
 // vae_blocks.conv_pool_down2), so the loop forms s = bf16(x0 + x1) and bf16(s) / 2 = bf16(s / 2) = m exactly (a power-of-two scale
 // commutes with the rounding).  The lone frame gives s = bf16(a + a) = 2 a exactly, so (2 a)(w / 2) = a w: no branch.
 //
-// Split: that of conv_down_bf16.hip — a tile is 256 consecutive output voxels (t', ho, wo) of one sample x 128 output channels; every
-// DMA lane owns one output voxel per 16-row group and computes ONCE the byte offset of the source row its tap (0, 0) reads in the FIRST
-// frame of its pair, relative to the tile's lowest source row (its first voxel's: the map rises with the voxel index for even and odd
-// T alike), where the buffer resource starts.  A tap is a tile-wide row shift kh row_pitch + kw, the second frame of the pair one
-// plane_pitch further — PER LANE, since a tile may hold voxels of output frame 0 (lone: shift dropped, both images hold frame 0) and of
-// output frame 1 (a pair).  Bottom row / right column taps that leave the grid clamp the ADDRESS to the neighbouring tap and zero the
-// FRAGMENT in registers by a select, so nothing but voxels of the grid is ever read.
+// The tile engine — split, geometry, padding by clamped address + zeroed fragment, epilogue — is conv_tile16.h.  Particular to this
+// kernel:
+//   * reference tap (0, 0) in the FIRST frame of the voxel's pair; the tile's lowest source row is its first voxel's (the map rises with
+//     the voxel index for even and odd T alike).  A tap is the row shift kh row_pitch + kw, the second frame of the pair one plane_pitch
+//     further — PER LANE, since a tile may hold voxels of output frame 0 (lone: shift dropped, both images hold frame 0) and of output
+//     frame 1 (a pair).  Bottom row / right column taps clamp and zero as in conv_down_bf16.hip;
+//   * its own pipeline: each k-tile (spatial tap, 32-channel chunk) is fetched as TWO A images, one per frame of the pair, and one W
+//     image.  Two stages of (2 A images + 1 W image) = 2 x 40 KiB = 80 KiB of LDS: stage t + 1 is in flight while stage t is multiplied
+//     (three A stages of two images would not fit twice in 160 KiB).  A wave reads the two fragments of a 16-voxel block from the two
+//     images, unpacks them to fp32, adds, rounds to bf16 once (v_cvt_pk_bf16_f32), applies the padding select and feeds four MFMAs.
 //
-// Data movement: each k-tile (spatial tap, 32-channel chunk) is fetched by LDS-DMA as TWO images of 256 rows x 64 bytes, one per frame
-// of the pair, with the 16-byte chunk swizzle of conv_down_bf16.hip on the source side; the weight panel is one image of 128 x 64
-// bytes.  Two stages of (2 A images + 1 W image) = 2 x 40 KiB = 80 KiB of LDS: stage t + 1 is in flight while stage t is multiplied
-// (three A stages of two images would not fit twice in 160 KiB).  A wave reads the two fragments of a 16-voxel block from the two
-// images, unpacks them to fp32, adds, rounds to bf16 once (v_cvt_pk_bf16_f32), applies the padding select and feeds four
-// v_mfma_f32_16x16x32_bf16 (the wave's 64 output channels); fp32 accumulators, bias added in the epilogue, bf16 stores of whole
-// 128-byte row segments through a per-wave LDS image, as conv_down_bf16.hip.
-//
-// Geometry and resources (gfx950, pinned by tests/test_build_resources_conv_pool_down.py): 4 waves (2 x 2), wave tile 128 voxels x 64
-// channels = 8 x 4 accumulators of 16 x 16, BK = 32; 256 threads, 180 VGPRs (128 of them accumulators), 81920 bytes of static LDS,
-// NO scratch, two workgroups per CU.  Per k-tile and wave: 32 MFMAs against 8 x (16 unpack + 8 add + 4 convert + 4 select) vector
+// Resources (gfx950, pinned by tests/test_build_resources_conv_pool_down.py): 180 VGPRs (128 of them accumulators), 81920 bytes of static
+// LDS, NO scratch, two workgroups per CU.  Per k-tile and wave: 32 MFMAs against 8 x (16 unpack + 8 add + 4 convert + 4 select) vector
 // instructions — the vector work is of the order of the matrix time, so the kernel is bound by the sum of the two pipes where
-// conv_down2 is bound by the matrix pipe alone.  The file is compiled without packed fp32 instructions (__graft_entry__.py
-// SOURCE_FLAGS), as conv_down_bf16.hip is: the pair sums and the bias adds stay single fp32 adds whatever the compiler would pair.
+// conv_down2 is bound by the matrix pipe alone.  Compiled without packed fp32 instructions, as conv_down_bf16.hip is: the pair sums
+// and the bias adds stay single fp32 adds whatever the compiler would pair.
 //
-// Refused before any launch (launch_conv_pool_down2): VSYS_ERR_SHAPE for T < 1, H or W < 2, cout % 128, cin % 32, a grid whose
-// sample_rows is below its frames, more than 65535 samples, and a tile whose source span — 256 consecutive output voxels with their
-// taps in both frames — or whose weight panel reaches 2 GiB (tile-relative offsets are 32-bit); VSYS_ERR_ALIGN for strides that are no
-// multiple of 8 elements or pointers off the 16-byte grid.
-#include "common.h"
-#include "vsys_internal.h"
+// Refused before any launch (launch_conv_pool_down2): VSYS_ERR_SHAPE for cout % 128, cin % 32, what ct16::refuse_grid refuses, and a
+// tile whose source span — 256 consecutive output voxels with their taps in both frames — or whose weight panel reaches 2 GiB
+// (tile-relative offsets are 32-bit); VSYS_ERR_ALIGN as ct16::refuse_align.
+#include "conv_tile16.h"
 
 namespace vsys {
 namespace {
 
-constexpr int BM = 256, BN = 128, BK = 32;
-constexpr int A_IMG = BM * BK * 2;            // 16384: one frame image of a k-tile
-constexpr int W_IMG = BN * BK * 2;            // 8192
-constexpr int STAGE = 2 * A_IMG + W_IMG;      // 40960: frame 0 image | frame 1 image | weight image
-constexpr int LDS_BYTES = 2 * STAGE;          // 81920
-constexpr int OUT_ROW_BYTES = 64 * 2 + 16;
-constexpr int OUT_WAVE_BYTES = 64 * OUT_ROW_BYTES;  // 9216 per wave and pass
-static_assert(4 * OUT_WAVE_BYTES <= LDS_BYTES, "epilogue image must fit in the staging buffers");
-static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
+using namespace ct16;
+
+constexpr int STAGE = 2 * A_SLOT + W_SLOT;    // 40960: frame 0 image | frame 1 image | weight image
+constexpr int POOL_LDS_BYTES = 2 * STAGE;     // 81920
+static_assert(4 * OUT_WAVE_BYTES <= POOL_LDS_BYTES, "epilogue image must fit in the staging buffers");
+static_assert(2 * POOL_LDS_BYTES <= 160 * 1024, "two workgroups per CU");
 
 // bf16(a + b) element-wise, the sum in fp32; zeros instead where the tap is padding
 __device__ __forceinline__ bf16x8 pair_sum(bf16x8 a, bf16x8 b, bool z) {
@@ -74,17 +63,8 @@ __device__ __forceinline__ bf16x8 pair_sum(bf16x8 a, bf16x8 b, bool z) {
 
 __global__ __launch_bounds__(256, 2) void conv_pool_down2_kernel(ConvDownParams p) {
 #if __HIP_DEVICE_COMPILE__  // buffer-resource types exist in the device pass only
-  __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];   // static: the code object carries the figure
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int l15 = lane & 15, lq = lane >> 4;
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-
-  const int nbn = p.N / BN;
-  const int tile = xcd_remap(blockIdx.x, gridDim.x);
-  const int bm = tile / nbn, bn = tile - bm * nbn;
-  const int row0 = bm * BM, col0 = bn * BN;
-  const int64_t zb = blockIdx.y;
+  __shared__ __attribute__((aligned(16))) char smem[POOL_LDS_BYTES];   // static: the code object carries the figure
+  const Tile tl = make_tile(p.N, p.ldw);
 
   // output voxel r of the sample -> source row, inside the sample, that tap (0, 0) reads in the FIRST frame of its pair; flags:
   // 1 the lone first frame (odd T, t' = 0: the second image reads the same frame), 2 bottom output row whose kh = 2 tap is the zero
@@ -99,39 +79,18 @@ __global__ __launch_bounds__(256, 2) void conv_pool_down2_kernel(ConvDownParams 
     return p.row00 + f0 * p.plane + 2 * ho * p.Wp + 2 * wo;
   };
   int f_unused;
-  const int base_row = __builtin_amdgcn_readfirstlane(src_of(row0, f_unused));   // row0 < M; the map rises with the voxel index
+  const int base_row = __builtin_amdgcn_readfirstlane(src_of(tl.row0, f_unused));   // row0 < M; the map rises with the voxel index
 
   const int ldx2 = (int)p.ldx * 2;
   const int hstep = p.Wp * ldx2, tstep = p.plane * ldx2;
-  const int dchunk = ((lane & 3) ^ ((0x78 >> (2 * ((lane >> 4) & 3))) & 3)) * 16;
-  int a_off[4], a_flags[4], b_off[2];
+  int a_off[4], a_flags[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = row0 + wave_u * 64 + i * 16 + (lane >> 2);
-    const int rl = r < p.M ? r : p.M - 1;  // rows past M re-read the last voxel (never stored)
-    a_off[i] = (src_of(rl, a_flags[i]) - base_row) * ldx2 + dchunk;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) b_off[i] = (wave_u * 32 + i * 16 + (lane >> 2)) * (int)p.ldw * 2 + dchunk;
-  // which of this lane's eight fragment voxels (16 i + l15 of the wave's 128) lose their kh = 2 / kw = 2 tap to the zero row / column
-  int mask_bot = 0, mask_right = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int r = row0 + wm * 128 + i * 16 + l15;
-    int f;
-    (void)src_of(r < p.M ? r : p.M - 1, f);
-    mask_bot |= ((f >> 1) & 1) << i;
-    mask_right |= ((f >> 2) & 1) << i;
-  }
+  for (int i = 0; i < 4; ++i) a_off[i] = (src_of(tl.dma_voxel(i, p.M), a_flags[i]) - base_row) * ldx2 + tl.dchunk;
+  // edges: bottom (kh = 2), right (kw = 2)
+  const auto mask = frag_masks<2>(tl, p.M, [&](int r) { int f; (void)src_of(r, f); return f; });
 
-  const int64_t abs_row = zb * p.sample_rows + base_row;
-  const int64_t a_bytes = ((p.rows_total - 1 - abs_row) * p.ldx + p.cin) * 2;   // to the end of the operand's last row
-  const int64_t b_bytes = ((int64_t)(p.N - 1 - col0) * p.ldw + p.K) * 2;
-  const auto rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void*)(p.X + abs_row * p.ldx), 0,
-                                                        (int)(a_bytes < 0x7fffffff ? a_bytes : 0x7fffffff), 0x00020000);
-  const auto rsrc_b = __builtin_amdgcn_make_buffer_rsrc((void*)(p.W + (int64_t)col0 * p.ldw), 0,
-                                                        (int)(b_bytes < 0x7fffffff ? b_bytes : 0x7fffffff), 0x00020000);
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
+  const auto rsrc_a = rows_rsrc(p.X, tl.zb * p.sample_rows + base_row, p.rows_total, p.ldx, p.cin);
+  const auto rsrc_b = rows_rsrc(p.W, tl.col0, p.N, p.ldw, p.K);
   // byte offset of this lane's source row, first frame of the pair, for tap (b, c) of DMA group i: the tile-wide row shift, clamped where
   // the tap leaves the grid; the second frame lies one plane further unless the voxel belongs to the lone first frame
   auto a_voff = [&](int i, int b, int c) -> int {
@@ -140,46 +99,28 @@ __global__ __launch_bounds__(256, 2) void conv_pool_down2_kernel(ConvDownParams 
     const int wc = (c == 2 && (f & 4)) ? 1 : c;
     return a_off[i] + hb * hstep + wc * ldx2;
   };
-  auto dma_a = [&](int i, int voff, int kc, int stage) {
-    char* dst = smem + stage * STAGE + (wave_u * 64 + i * 16) * 64;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (lds_ptr_t)dst, 16, voff, kc * (BK * 2), 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (lds_ptr_t)(dst + A_IMG), 16, voff + ((a_flags[i] & 1) ? 0 : tstep), kc * (BK * 2), 0, 0);
-  };
-  auto dma_w = [&](int i, int t, int stage) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (lds_ptr_t)(smem + stage * STAGE + 2 * A_IMG + (wave_u * 32 + i * 16) * 64), 16,
-                                             b_off[i], t * (BK * 2), 0, 0);
-  };
-  auto fetch = [&](int b, int c, int kc, int t, int stage) {
+  auto fetch = [&](const KTile& k, int t, int stage) {
+    char* img = smem + stage * STAGE;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) dma_a(i, a_voff(i, b, c), kc, stage);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) dma_w(i, t, stage);
-  };
-  // k-tile counters (kh, kw, channel chunk), carried: cin / 32 need not be a power of two
-  auto advance = [&](int& b, int& c, int& kc) {
-    if (++kc == p.nkc) {
-      kc = 0;
-      if (++c == 3) { c = 0; ++b; }
+    for (int i = 0; i < 4; ++i) {
+      const int voff = a_voff(i, k.b, k.c);
+      dma_a(rsrc_a, img, tl, i, voff, k.kc);
+      dma_a(rsrc_a, img + A_SLOT, tl, i, voff + ((a_flags[i] & 1) ? 0 : tstep), k.kc);
     }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) dma_w(rsrc_b, img + 2 * A_SLOT, tl, i, t);
   };
 
-  const int fsw = (lq ^ ((0x78 >> (2 * ((l15 >> 2) & 3))) & 3)) << 4;
-  const int xo = (wm * 128 + l15) * 64 + fsw;               // + i*1024 for token block i, + A_IMG for the second frame
-  const int wo_ = 2 * A_IMG + (wn * 64 + l15) * 64 + fsw;   // + j*1024 for column block j
+  const int xo = tl.frag_x();                  // + i*1024 for token block i, + A_SLOT for the second frame
+  const int wo_ = 2 * A_SLOT + tl.frag_w();    // + j*1024 for column block j
 
   f32x4 acc16[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc16[i][j][r] = 0.f;
+  zero_acc(acc16);
 
   const int nt = p.K / BK;
-  int pb = 0, pc = 0, pk = 0;   // the k-tile being fetched
-  int mb = 0, mc = 0, mk = 0;   // the k-tile being multiplied
-  fetch(pb, pc, pk, 0, 0);
-  advance(pb, pc, pk);
+  KTile pf, mul;   // the k-tile being fetched / being multiplied; no time tap: a stays 0 while k-tiles remain
+  fetch(pf, 0, 0);
+  pf.advance(p.nkc);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_barrier();
@@ -188,9 +129,9 @@ __global__ __launch_bounds__(256, 2) void conv_pool_down2_kernel(ConvDownParams 
   int st = 0;
   for (int t = 0; t < nt; ++t) {
     // stage st ^ 1 was last read in iteration t - 1, which every wave left through the barrier below
-    if (t + 1 < nt) fetch(pb, pc, pk, t + 1, st ^ 1);
+    if (t + 1 < nt) fetch(pf, t + 1, st ^ 1);
     __builtin_amdgcn_sched_barrier(0);
-    const int mz = (mb == 2 ? mask_bot : 0) | (mc == 2 ? mask_right : 0);   // fragment voxels whose tap is padding
+    const int mz = (mul.b == 2 ? mask.m[0] : 0) | (mul.c == 2 ? mask.m[1] : 0);   // fragment voxels whose tap is padding
     const char* ab = smem + st * STAGE;
     const bf16x8 w0 = *reinterpret_cast<const bf16x8*>(ab + wo_);
     const bf16x8 w1 = *reinterpret_cast<const bf16x8*>(ab + wo_ + 1024);
@@ -198,13 +139,13 @@ __global__ __launch_bounds__(256, 2) void conv_pool_down2_kernel(ConvDownParams 
     const bf16x8 v1 = *reinterpret_cast<const bf16x8*>(ab + wo_ + 3072);
     // two token blocks in flight: the fragments of block i + 1 are read while block i is summed and multiplied
     bf16x8 fa = *reinterpret_cast<const bf16x8*>(ab + xo);
-    bf16x8 fb = *reinterpret_cast<const bf16x8*>(ab + xo + A_IMG);
+    bf16x8 fb = *reinterpret_cast<const bf16x8*>(ab + xo + A_SLOT);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       bf16x8 na = fa, nb = fb;
       if (i < 7) {
         na = *reinterpret_cast<const bf16x8*>(ab + xo + (i + 1) * 1024);
-        nb = *reinterpret_cast<const bf16x8*>(ab + xo + (i + 1) * 1024 + A_IMG);
+        nb = *reinterpret_cast<const bf16x8*>(ab + xo + (i + 1) * 1024 + A_SLOT);
       }
       const bf16x8 x = pair_sum(fa, fb, (mz >> i) & 1);
       acc16[i][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, x, acc16[i][0], 0, 0, 0);
@@ -219,77 +160,30 @@ __global__ __launch_bounds__(256, 2) void conv_pool_down2_kernel(ConvDownParams 
     __builtin_amdgcn_s_barrier();  // stage t + 1 has landed everywhere; nobody reads stage t any more
     __builtin_amdgcn_sched_barrier(0);
     st ^= 1;
-    advance(pb, pc, pk);
-    advance(mb, mc, mk);
+    pf.advance(p.nkc);
+    mul.advance(p.nkc);
   }
 
-  // bf16 output through a per-wave LDS image (two passes of 64 rows), so the global stores are whole 128-byte row segments; element
-  // (voxel 16 i + l15, channel 16 j + 4 lq + r) sits in acc16[i][j][r]
-  const int ncol0 = col0 + wn * 64;
-  bf16_t* ob = p.out + zb * (int64_t)p.M * p.ldo;
-  char* img = smem + wave * OUT_WAVE_BYTES;
-  uint2 bb16[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    bb16[j] = p.bias != nullptr ? *reinterpret_cast<const uint2*>(p.bias + ncol0 + j * 16 + 4 * lq) : make_uint2(0, 0);
-#pragma unroll
-  for (int ih = 0; ih < 2; ++ih) {
-    const int wrow0 = row0 + wm * 128 + ih * 64;
-#pragma unroll
-    for (int i2 = 0; i2 < 4; ++i2) {
-      const int i = ih * 4 + i2;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float v[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = acc16[i][j][r];
-        v[0] += bflo(bb16[j].x); v[1] += bfhi(bb16[j].x); v[2] += bflo(bb16[j].y); v[3] += bfhi(bb16[j].y);
-        uint2 o;
-        o.x = pack2bf(v[0], v[1]);
-        o.y = pack2bf(v[2], v[3]);
-        *reinterpret_cast<uint2*>(img + (i2 * 16 + l15) * OUT_ROW_BYTES + (j * 16 + 4 * lq) * 2) = o;
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    uint4 val[8];
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int q = lane + 64 * it;
-      val[it] = *reinterpret_cast<const uint4*>(img + (q >> 3) * OUT_ROW_BYTES + (q & 7) * 16);
-    }
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int q = lane + 64 * it;
-      const int64_t grow = wrow0 + (q >> 3);
-      if (grow < p.M) *reinterpret_cast<uint4*>(ob + grow * p.ldo + ncol0 + (q & 7) * 8) = val[it];
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // image reads done before the next pass overwrites it
-    __builtin_amdgcn_wave_barrier();
-  }
+  store_tile_bf16(smem, tl, acc16, p.bias, p.out, p.ldo, p.M, NoHook());
 #endif
 }
-
-inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 }  // namespace
 
 int launch_conv_pool_down2(const bf16_t* x, int64_t ldx, const VaeGrid& g, int64_t nsamples, const bf16_t* w_half, int64_t ldw,
                            const bf16_t* bias, bf16_t* out, int64_t ldo, int64_t cin, int64_t cout, hipStream_t stream) {
-  if (g.T < 1 || g.H < 2 || g.W < 2 || g.pad < 0 || g.tf < 0 || nsamples < 0 || nsamples > 65535) return VSYS_ERR_SHAPE;
+  SrcGrid s;
+  if (int e = refuse_grid(g, nsamples, s)) return e;
   if (cout <= 0 || cout % BN != 0 || cin <= 0 || cin % BK != 0 || cin > (1 << 20) || cout > (1 << 20)) return VSYS_ERR_SHAPE;
-  const int64_t Hp = g.H + 2 * g.pad, Wp = g.W + 2 * g.pad, plane = Hp * Wp;
-  if ((g.T + g.tf) * plane > g.sample_rows || g.sample_rows > 0x7fffffff) return VSYS_ERR_SHAPE;
   if (nsamples == 0) return 0;
   const int64_t To = g.T / 2 + (g.T & 1), Ho = g.H / 2, Wo = g.W / 2;
   const int64_t K = 9 * cin;
   if (ldx < cin || ldo < cout || ldw < K) return VSYS_ERR_SHAPE;
-  if ((ldx % 8) || (ldw % 8) || (ldo % 8)) return VSYS_ERR_ALIGN;
-  if (!aligned16(x) || !aligned16(w_half) || !aligned16(out) || (reinterpret_cast<uintptr_t>(bias) & 7)) return VSYS_ERR_ALIGN;
+  if (int e = refuse_align(x, ldx, w_half, ldw, bias, out, ldo)) return e;
   // tile-relative operand offsets are 32-bit (buffer addressing): the widest source span of BM consecutive output voxels — two columns a
   // voxel, two rows a wrapped output row, two planes a wrapped output frame — with the last tap's shift and the second frame's plane
   const int64_t q = BM - 1;
-  const int64_t span = 2 * q + (q + Wo - 1) / Wo * 2 * Wp + (q + Ho * Wo - 1) / (Ho * Wo) * 2 * plane + plane + 2 * Wp + 2;
+  const int64_t span = 2 * q + (q + Wo - 1) / Wo * 2 * s.Wp + (q + Ho * Wo - 1) / (Ho * Wo) * 2 * s.plane + s.plane + 2 * s.Wp + 2;
   if ((span + 1) * ldx * 2 >= 0x7fffffff || ldw * 256 + K * 2 >= 0x7fffffff) return VSYS_ERR_SHAPE;
   const int64_t M = To * Ho * Wo;
   const int64_t nbm = (M + BM - 1) / BM, nbn = cout / BN;
@@ -298,8 +192,8 @@ int launch_conv_pool_down2(const bf16_t* x, int64_t ldx, const VaeGrid& g, int64
   p.X = x; p.ldx = ldx; p.sample_rows = g.sample_rows; p.rows_total = nsamples * g.sample_rows;
   p.W = w_half; p.ldw = ldw; p.bias = bias; p.out = out; p.ldo = ldo;
   p.M = (int)M; p.N = (int)cout; p.K = (int)K; p.cin = (int)cin; p.nkc = (int)(cin / BK); p.kt = g.T & 1;   // kt: T is odd
-  p.H = g.H; p.Wd = g.W; p.Ho = (int)Ho; p.Wo = (int)Wo; p.Wp = (int)Wp; p.plane = (int)plane;
-  p.row00 = (int)((g.tf * Hp + g.pad) * Wp + g.pad);
+  p.H = g.H; p.Wd = g.W; p.Ho = (int)Ho; p.Wo = (int)Wo; p.Wp = (int)s.Wp; p.plane = (int)s.plane;
+  p.row00 = (int)s.row00;
   hipLaunchKernelGGL(conv_pool_down2_kernel, dim3((unsigned)(nbm * nbn), (unsigned)nsamples), dim3(256), 0, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : VSYS_ERR_LAUNCH;
 }

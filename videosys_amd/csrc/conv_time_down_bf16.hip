@@ -13,54 +13,34 @@
 // fp32, then their one rounding to bf16, as the decoder's TimeUpsampleRes2x does) and passes a3 = fp32(alpha / 3).
 //   w == NULL: TimeDownsample2x, out = bf16(((x0 + x1) + x2) * fp32(1 / 3)): no matrix work, the bandwidth kernel at the end of the file.
 //
-// Split: per-lane DMA addresses from an output-voxel -> source-row map, as conv_down_bf16.hip.  A tile is 256 consecutive output voxels
-// (t', h, w) of ONE sample x 128 output channels.  Every DMA lane owns one output voxel per 16-row group and computes ONCE the byte offset
-// of the source row of its CENTRE tap in time tap 0, (f(t', 0), h, w), relative to the tile's lowest source row, where the buffer
-// resource starts.  A tap is then the tile-wide row shift a plane_pitch + (kh - 1) row_pitch + (kw - 1) rows.  The map rises with the
-// voxel index — a tile crosses output frames, each of which jumps TWO source planes — except at one place: output frames 0 and 1 both
-// start at source frame 0, so a tile that begins in output frame 0 and reaches frame 1 has its lowest row at the sample's first voxel.
-// Every other tile's lowest row is one row pitch and one row below its first voxel's centre (its tap (., 0, 0)), but never below the
-// sample's first voxel.
+// The tile engine — split, geometry, staging pipeline, padding by clamped address + zeroed fragment, epilogue — is conv_tile16.h.
+// Particular to this kernel:
+//   * reference tap: the CENTRE tap in time tap 0, (f(t', 0), h, w).  A tap is the tile-wide row shift a plane_pitch + (kh - 1) row_pitch +
+//     (kw - 1) rows.  The map rises with the voxel index — a tile crosses output frames, each of which jumps TWO source planes — except
+//     at one place: output frames 0 and 1 both start at source frame 0, so a tile that begins in output frame 0 and reaches frame 1 has
+//     its lowest row at the sample's first voxel.  Every other tile's lowest row is one row pitch and one row below its first voxel's
+//     centre (its tap (., 0, 0)), but never below the sample's first voxel;
+//   * ALL FOUR spatial edges pad from the addressing (kh = 0 at h = 0, kh = 2 at h = H - 1, kw = 0 at w = 0, kw = 2 at w = W - 1): the
+//     address is clamped to the centre tap (kh = 1 / kw = 1, always a voxel) and the fragment zeroed.  On output frame 0 the temporal
+//     shift is dropped: every a reads frame 0;
+//   * the pooled residual is no separate pass: in the epilogue (its hook) the lane that owns (voxel, column quad) of the accumulator tile
+//     FETCHES the three source values itself — three 8-byte loads of rows whose 128-column segment is the centre-tap k-tiles the main
+//     loop of this very tile pulled through L2.  Keeping them from the staged A image was the alternative and is not taken: the image
+//     of a k-tile holds 32 channels of ONE tap for 256 voxels, the residual columns of a tile are 128 channels of THREE taps, which pass
+//     through the three A slots at 12 different k-tiles; holding them would take 3 x 256 x 128 x 2 = 192 KiB of LDS, more than a CU has,
+//     or 48 more registers a lane beside 128 accumulators.  The fetch costs 96 8-byte L2 hits per lane after 27 C / 32 k-tiles of 32
+//     MFMAs.  The adds stay single fp32 operations (no packed fp32: conv_tile16.h) and the a3 multiply-add is an explicit fma.
+// 65536 bytes of static LDS, at most 222 VGPRs, no scratch: pinned by tests/test_build_resources_conv_time_down.py.
 //
-// Edges: ALL FOUR spatial edges pad from the addressing.  On the voxels whose tap leaves the grid (kh = 0 at h = 0, kh = 2 at h = H - 1,
-// kw = 0 at w = 0, kw = 2 at w = W - 1) the ADDRESS is clamped to the centre tap (kh = 1 / kw = 1, always a voxel) and the FRAGMENT is
-// replaced by zeros in registers before its MFMAs (a select: whatever the clamped row holds never reaches a result).  On output frame 0
-// the temporal shift is dropped: every a reads frame 0.  The source is read where it lies (any VaeGrid: the padded output grid of the
-// spatial downsampler, a dense one), no padded copy is made and nothing but voxels of the grid is ever read.
-//
-// The pooled residual is no separate pass: in the epilogue the lane that owns (voxel, column quad) of the accumulator tile FETCHES the
-// three source values itself — three 8-byte loads of rows whose 128-column segment is the centre-tap k-tiles the main loop of this
-// very tile pulled through L2.  Keeping them from the staged A image was the alternative and is not taken: the image of a k-tile holds
-// 32 channels of ONE tap for 256 voxels, the residual columns of a tile are 128 channels of THREE taps, which pass through the three A
-// slots at 12 different k-tiles; holding them would take 3 x 256 x 128 x 2 = 192 KiB of LDS, more than a CU has, or 48 more registers a
-// lane beside 128 accumulators.  The fetch costs 96 8-byte L2 hits per lane after 27 C / 32 k-tiles of 32 MFMAs.
-//
-// Geometry: that of conv_down_bf16.hip.  4 waves (2 x 2), wave tile 128 voxels x 64 channels = 8 x 4 accumulators of 16 x 16,
-// v_mfma_f32_16x16x32_bf16, BK = 32, A by LDS-DMA with the 16-byte chunk swizzle on the source side, three A slots + two W slots =
-// 65536 bytes of STATIC LDS (the code object carries the figure), 256 threads, two workgroups per CU, no scratch (pinned by
-// tests/test_build_resources_conv_time_down.py).  k runs tap-major, (a, kh, kw) outermost to innermost, then the C / 32 channel chunks.
-// The file is compiled without packed fp32 instructions (__graft_entry__.py SOURCE_FLAGS): the epilogue's adds stay single fp32
-// operations, so the output bits do not depend on how the compiler would pair them; the a3 multiply-add is an explicit fma.
-//
-// Refused before any launch (launch_conv_time_down2): VSYS_ERR_SHAPE for C % 128 with weights or C % 8 without, T < 1, H or W < 2, a grid
-// whose sample_rows is below its frames, more than 65535 samples, a tile whose source span or a weight panel that reaches 2 GiB
-// (tile-relative offsets are 32-bit); VSYS_ERR_ALIGN for strides that are no multiple of 8 elements or pointers off the 16-byte grid;
-// VSYS_ERR_ARG for a3 outside [0, fp32(1 / 3)].
-#include "common.h"
-#include "vsys_internal.h"
+// Refused before any launch (launch_conv_time_down2): VSYS_ERR_SHAPE for C % 128 with weights or C % 8 without, what ct16::refuse_grid
+// refuses, a tile whose source span or a weight panel that reaches 2 GiB (tile-relative offsets are 32-bit); VSYS_ERR_ALIGN as
+// ct16::refuse_align; VSYS_ERR_ARG for a3 outside [0, fp32(1 / 3)].
+#include "conv_tile16.h"
 
 namespace vsys {
 namespace {
 
-constexpr int BM = 256, BN = 128, BK = 32;
-constexpr int A_SLOT = BM * BK * 2;   // 16384
-constexpr int W_SLOT = BN * BK * 2;   // 8192
-constexpr int W_BASE = 3 * A_SLOT;    // 49152
-constexpr int LDS_BYTES = W_BASE + 2 * W_SLOT;  // 65536
-constexpr int OUT_ROW_BYTES = 64 * 2 + 16;
-constexpr int OUT_WAVE_BYTES = 64 * OUT_ROW_BYTES;  // 9216 per wave and pass
-static_assert(4 * OUT_WAVE_BYTES <= LDS_BYTES, "epilogue image must fit in the staging buffers");
-static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
+using namespace ct16;
 
 struct TimeDownParams {
   const bf16_t* X = nullptr; int64_t ldx = 0;   // source rows over the grid, [*, >= C]
@@ -76,12 +56,6 @@ struct TimeDownParams {
 
 enum : int { F_FIRST = 1, F_TOP = 2, F_BOTTOM = 4, F_LEFT = 8, F_RIGHT = 16 };
 
-__device__ __forceinline__ bf16x8 zero_if(bf16x8 v, bool z) {
-  uint4 u = __builtin_bit_cast(uint4, v);
-  u.x = z ? 0u : u.x; u.y = z ? 0u : u.y; u.z = z ? 0u : u.z; u.w = z ? 0u : u.w;
-  return __builtin_bit_cast(bf16x8, u);
-}
-
 // output voxel r of the sample -> source row of (f(t', 0), h, w) inside the sample; flags: first output frame, and the four edges
 __device__ __forceinline__ int src_of(const TimeDownParams& p, int r, int& flags) {
   const int HW = p.H * p.Wd;
@@ -94,16 +68,8 @@ __device__ __forceinline__ int src_of(const TimeDownParams& p, int r, int& flags
 __global__ __launch_bounds__(256, 2) void conv_time_down2_kernel(TimeDownParams p) {
 #if __HIP_DEVICE_COMPILE__  // buffer-resource types exist in the device pass only
   __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int l15 = lane & 15, lq = lane >> 4;
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-
-  const int nbn = p.C / BN;
-  const int tile = xcd_remap(blockIdx.x, gridDim.x);
-  const int bm = tile / nbn, bn = tile - bm * nbn;
-  const int row0 = bm * BM, col0 = bn * BN;
-  const int64_t zb = blockIdx.y;
+  const Tile tl = make_tile(p.C, p.ldw);
+  const int row0 = tl.row0;
 
   // the tile's lowest source row: tap (., 0, 0) of its first voxel (row0 < M: the grid has ceil(M / BM) row tiles), not below the sample's
   // first voxel; the sample's first voxel when the tile runs from output frame 0 into output frame 1, which starts at source frame 0 again
@@ -115,221 +81,60 @@ __global__ __launch_bounds__(256, 2) void conv_time_down2_kernel(TimeDownParams 
 
   const int ldx2 = (int)p.ldx * 2;
   const int hstep = p.Wp * ldx2, tstep = p.plane * ldx2;
-  const int dchunk = ((lane & 3) ^ ((0x78 >> (2 * ((lane >> 4) & 3))) & 3)) * 16;
   // per DMA group: the centre row's offset and the five shifts a tap may add, each already 0 where the tap is clamped (edges) or the
   // temporal shift dropped (output frame 0) — plain integers a lane, so no lane mask is carried through the loop
-  int a_off[4], d_t[4], d_up[4], d_dn[4], d_lf[4], d_rt[4], b_off[2];
+  int a_off[4], d_t[4], d_up[4], d_dn[4], d_lf[4], d_rt[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int r = row0 + wave_u * 64 + i * 16 + (lane >> 2);
-    const int rl = r < p.M ? r : p.M - 1;  // rows past M re-read the last voxel (never stored)
     int f;
-    a_off[i] = (src_of(p, rl, f) - base_row) * ldx2 + dchunk;
+    a_off[i] = (src_of(p, tl.dma_voxel(i, p.M), f) - base_row) * ldx2 + tl.dchunk;
     d_t[i] = (f & F_FIRST) ? 0 : tstep;
     d_up[i] = (f & F_TOP) ? 0 : -hstep;
     d_dn[i] = (f & F_BOTTOM) ? 0 : hstep;
     d_lf[i] = (f & F_LEFT) ? 0 : -ldx2;
     d_rt[i] = (f & F_RIGHT) ? 0 : ldx2;
   }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) b_off[i] = (wave_u * 32 + i * 16 + (lane >> 2)) * (int)p.ldw * 2 + dchunk;
-  // which of this lane's eight fragment voxels (16 i + l15 of the wave's 128) lose their kh = 0 / kh = 2 / kw = 0 / kw = 2 tap to the padding
-  int mask_top = 0, mask_bot = 0, mask_left = 0, mask_right = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int r = row0 + wm * 128 + i * 16 + l15;
-    int f;
-    (void)src_of(p, r < p.M ? r : p.M - 1, f);
-    mask_top |= ((f >> 1) & 1) << i;
-    mask_bot |= ((f >> 2) & 1) << i;
-    mask_left |= ((f >> 3) & 1) << i;
-    mask_right |= ((f >> 4) & 1) << i;
-  }
+  // edges: top (kh = 0), bottom (kh = 2), left (kw = 0), right (kw = 2)
+  const auto mask = frag_masks<4>(tl, p.M, [&](int r) { int f; (void)src_of(p, r, f); return f; });
 
-  const int64_t abs_row = zb * p.sample_rows + base_row;
-  const int64_t a_bytes = ((p.rows_total - 1 - abs_row) * p.ldx + p.C) * 2;   // to the end of the operand's last row
-  const int64_t b_bytes = ((int64_t)(p.C - 1 - col0) * p.ldw + p.K) * 2;
-  const auto rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void*)(p.X + abs_row * p.ldx), 0,
-                                                        (int)(a_bytes < 0x7fffffff ? a_bytes : 0x7fffffff), 0x00020000);
-  const auto rsrc_b = __builtin_amdgcn_make_buffer_rsrc((void*)(p.W + (int64_t)col0 * p.ldw), 0,
-                                                        (int)(b_bytes < 0x7fffffff ? b_bytes : 0x7fffffff), 0x00020000);
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
+  const auto rsrc_a = rows_rsrc(p.X, tl.zb * p.sample_rows + base_row, p.rows_total, p.ldx, p.C);
+  const auto rsrc_b = rows_rsrc(p.W, tl.col0, p.C, p.ldw, p.K);
   // byte offset of this lane's source row for tap (a, b, c) of DMA group i: the tile-wide row shift, clamped to the centre tap where
   // the tap leaves the grid (the sum is >= 0: the clamped row is a voxel, and no voxel the tile reads lies below base_row)
   auto a_voff = [&](int i, int a, int b, int c) -> int {
     return a_off[i] + a * d_t[i] + (b == 0 ? d_up[i] : b == 2 ? d_dn[i] : 0) + (c == 0 ? d_lf[i] : c == 2 ? d_rt[i] : 0);
   };
-  auto dma_a = [&](int i, int voff, int kc, int slot) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (lds_ptr_t)(smem + slot * A_SLOT + (wave_u * 64 + i * 16) * 64), 16, voff,
-                                             kc * (BK * 2), 0, 0);
+  auto pad_mask = [&](int b, int c) -> int {
+    return (b == 0 ? mask.m[0] : 0) | (b == 2 ? mask.m[1] : 0) | (c == 0 ? mask.m[2] : 0) | (c == 2 ? mask.m[3] : 0);
   };
-  auto dma_w = [&](int i, int t, int slot) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (lds_ptr_t)(smem + W_BASE + slot * W_SLOT + (wave_u * 32 + i * 16) * 64), 16,
-                                             b_off[i], t * (BK * 2), 0, 0);
-  };
-  // k-tile counters (temporal tap, kh, kw, channel chunk), carried
-  auto advance = [&](int& a, int& b, int& c, int& kc) {
-    if (++kc == p.nkc) {
-      kc = 0;
-      if (++c == 3) {
-        c = 0;
-        if (++b == 3) { b = 0; ++a; }
-      }
-    }
-  };
-
-  const int fsw = (lq ^ ((0x78 >> (2 * ((l15 >> 2) & 3))) & 3)) << 4;
-  const int xo = (wm * 128 + l15) * 64 + fsw;           // + i*1024 for token block i
-  const int wo_ = W_BASE + (wn * 64 + l15) * 64 + fsw;  // + j*1024 for column block j
 
   f32x4 acc16[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc16[i][j][r] = 0.f;
+  zero_acc(acc16);
+  k_loop(smem, tl, rsrc_a, rsrc_b, p.K / BK, p.nkc, a_voff, pad_mask, acc16);   // 27 C / 32 >= 108 k-tiles
 
-  const int nt = p.K / BK;              // 27 C / 32 >= 108
-  int pa = 0, pb = 0, pc = 0, pk = 0;   // the k-tile being fetched
-  int mb = 0, mc = 0, mk = 0, ma = 0;   // the k-tile being multiplied
-#pragma unroll
-  for (int i = 0; i < 4; ++i) dma_a(i, a_voff(i, pa, pb, pc), pk, 0);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) dma_w(i, 0, 0);
-  advance(pa, pb, pc, pk);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) dma_a(i, a_voff(i, pa, pb, pc), pk, 1);
-  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  advance(pa, pb, pc, pk);
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-
-  int sa = 0, sw = 0;
-  for (int t = 0; t < nt; ++t) {
-    const int sa1 = sa == 2 ? 0 : sa + 1, sa2 = sa1 == 2 ? 0 : sa1 + 1, sw1 = sw ^ 1;
-    const bool n1 = t + 1 < nt, n2 = t + 2 < nt;
-    int v2[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v2[i] = a_voff(i, pa, pb, pc);
-    const int k2 = pk;
-    // fragment voxels whose tap is padding
-    const int mz = (mb == 0 ? mask_top : 0) | (mb == 2 ? mask_bot : 0) | (mc == 0 ? mask_left : 0) | (mc == 2 ? mask_right : 0);
-    const char* ab = smem + sa * A_SLOT;
-    const char* wb = smem + sw * W_SLOT;
-    bf16x8 x0, x1, x2, x3, w0, w1, v0, v1;
-    // (w0, w1, v0, v1) = the four column blocks, x0..x3 = token blocks 0..3, reloaded with blocks 4..7 behind their MFMAs
-    x0 = *reinterpret_cast<const bf16x8*>(ab + xo);
-    w0 = *reinterpret_cast<const bf16x8*>(wb + wo_);
-    w1 = *reinterpret_cast<const bf16x8*>(wb + wo_ + 1024);
-    v0 = *reinterpret_cast<const bf16x8*>(wb + wo_ + 2048);
-    v1 = *reinterpret_cast<const bf16x8*>(wb + wo_ + 3072);
-    x1 = *reinterpret_cast<const bf16x8*>(ab + xo + 1024);
-    x2 = *reinterpret_cast<const bf16x8*>(ab + xo + 2048);
-    x3 = *reinterpret_cast<const bf16x8*>(ab + xo + 3072);
-    __builtin_amdgcn_sched_barrier(0);
-#define CT16_ROW(i_, X_)                                                                              \
-  X_ = zero_if(X_, (mz >> (i_)) & 1);                                                                 \
-  acc16[i_][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, X_, acc16[i_][0], 0, 0, 0);              \
-  acc16[i_][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, X_, acc16[i_][1], 0, 0, 0);              \
-  acc16[i_][2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v0, X_, acc16[i_][2], 0, 0, 0);              \
-  acc16[i_][3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v1, X_, acc16[i_][3], 0, 0, 0)
-    CT16_ROW(0, x0);
-    __builtin_amdgcn_sched_barrier(0);
-    x0 = *reinterpret_cast<const bf16x8*>(ab + xo + 4096);
-    if (n1) { dma_w(0, t + 1, sw1); dma_w(1, t + 1, sw1); }
-    __builtin_amdgcn_sched_barrier(0);
-    CT16_ROW(1, x1);
-    __builtin_amdgcn_sched_barrier(0);
-    x1 = *reinterpret_cast<const bf16x8*>(ab + xo + 5120);
-    if (n2) { dma_a(0, v2[0], k2, sa2); dma_a(1, v2[1], k2, sa2); }
-    __builtin_amdgcn_sched_barrier(0);
-    CT16_ROW(2, x2);
-    __builtin_amdgcn_sched_barrier(0);
-    x2 = *reinterpret_cast<const bf16x8*>(ab + xo + 6144);
-    if (n2) dma_a(2, v2[2], k2, sa2);
-    __builtin_amdgcn_sched_barrier(0);
-    CT16_ROW(3, x3);
-    __builtin_amdgcn_sched_barrier(0);
-    x3 = *reinterpret_cast<const bf16x8*>(ab + xo + 7168);
-    if (n2) dma_a(3, v2[3], k2, sa2);
-    __builtin_amdgcn_sched_barrier(0);
-    CT16_ROW(4, x0);
-    CT16_ROW(5, x1);
-    CT16_ROW(6, x2);
-    CT16_ROW(7, x3);
-#undef CT16_ROW
-    __builtin_amdgcn_sched_barrier(0);
-    if (n2) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();  // stage t+1 has landed everywhere; nobody reads the slots of stage t any more
-    __builtin_amdgcn_sched_barrier(0);
-    sa = sa1;
-    sw = sw1;
-    advance(pa, pb, pc, pk);
-    advance(ma, mb, mc, mk);
-  }
-
-  // bias + pooled residual + bf16 output through a per-wave LDS image (two passes of 64 rows), so the global stores are whole 128-byte
-  // row segments; element (voxel 16 i + l15, channel 16 j + 4 lq + r) sits in acc16[i][j][r], and its lane fetches the three source
-  // values of that voxel and channel quad itself (8 bytes each; the frame step is dropped on output frame 0)
-  const int ncol0 = col0 + wn * 64;
-  bf16_t* ob = p.out + zb * (int64_t)p.M * p.ldo;
-  char* st = smem + wave * OUT_WAVE_BYTES;
+  // the pooled residual, between the bias add and the rounding: the lane that owns (voxel, column quad) fetches the three source values
+  // of that voxel and channel quad itself (8 bytes each; the frame step is dropped on output frame 0)
+  const int ncol0 = tl.col0 + tl.wn * 64;
   const float a3 = p.a3;
-  uint2 bb16[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    bb16[j] = p.bias != nullptr ? *reinterpret_cast<const uint2*>(p.bias + ncol0 + j * 16 + 4 * lq) : make_uint2(0, 0);
-#pragma unroll
-  for (int ih = 0; ih < 2; ++ih) {
-    const int wrow0 = row0 + wm * 128 + ih * 64;
-#pragma unroll
-    for (int i2 = 0; i2 < 4; ++i2) {
-      const int i = ih * 4 + i2;
-      const int rr = wrow0 + i2 * 16 + l15;
+  const bf16_t* xr = nullptr;   // the hook's voxel, set at its first column quad (the epilogue walks j = 0..3 of a token block in order)
+  int64_t fstep = 0;
+  auto residual = [&](int, int j, int rr, float (&v)[4]) {
+    if (j == 0) {
       int f;
       const int centre = src_of(p, rr < p.M ? rr : p.M - 1, f);
-      const bf16_t* xr = p.X + (zb * p.sample_rows + centre) * p.ldx + ncol0 + 4 * lq;
-      const int64_t fstep = (f & F_FIRST) ? 0 : (int64_t)p.plane * p.ldx;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const uint2 q0 = *reinterpret_cast<const uint2*>(xr + j * 16);
-        const uint2 q1 = *reinterpret_cast<const uint2*>(xr + fstep + j * 16);
-        const uint2 q2 = *reinterpret_cast<const uint2*>(xr + 2 * fstep + j * 16);
-        float v[4], s[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = acc16[i][j][r];
-        v[0] += bflo(bb16[j].x); v[1] += bfhi(bb16[j].x); v[2] += bflo(bb16[j].y); v[3] += bfhi(bb16[j].y);
-        s[0] = (bflo(q0.x) + bflo(q1.x)) + bflo(q2.x); s[1] = (bfhi(q0.x) + bfhi(q1.x)) + bfhi(q2.x);
-        s[2] = (bflo(q0.y) + bflo(q1.y)) + bflo(q2.y); s[3] = (bfhi(q0.y) + bfhi(q1.y)) + bfhi(q2.y);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = __builtin_fmaf(a3, s[r], v[r]);
-        uint2 o;
-        o.x = pack2bf(v[0], v[1]);
-        o.y = pack2bf(v[2], v[3]);
-        *reinterpret_cast<uint2*>(st + (i2 * 16 + l15) * OUT_ROW_BYTES + (j * 16 + 4 * lq) * 2) = o;
-      }
+      xr = p.X + (tl.zb * p.sample_rows + centre) * p.ldx + ncol0 + 4 * tl.lq;
+      fstep = (f & F_FIRST) ? 0 : (int64_t)p.plane * p.ldx;
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    uint4 val[8];
+    const uint2 q0 = *reinterpret_cast<const uint2*>(xr + j * 16);
+    const uint2 q1 = *reinterpret_cast<const uint2*>(xr + fstep + j * 16);
+    const uint2 q2 = *reinterpret_cast<const uint2*>(xr + 2 * fstep + j * 16);
+    float s[4];
+    s[0] = (bflo(q0.x) + bflo(q1.x)) + bflo(q2.x); s[1] = (bfhi(q0.x) + bfhi(q1.x)) + bfhi(q2.x);
+    s[2] = (bflo(q0.y) + bflo(q1.y)) + bflo(q2.y); s[3] = (bfhi(q0.y) + bfhi(q1.y)) + bfhi(q2.y);
 #pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int q = lane + 64 * it;
-      val[it] = *reinterpret_cast<const uint4*>(st + (q >> 3) * OUT_ROW_BYTES + (q & 7) * 16);
-    }
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int q = lane + 64 * it;
-      const int64_t grow = wrow0 + (q >> 3);
-      if (grow < p.M) *reinterpret_cast<uint4*>(ob + grow * p.ldo + ncol0 + (q & 7) * 8) = val[it];
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // image reads done before the next pass overwrites it
-    __builtin_amdgcn_wave_barrier();
-  }
+    for (int r = 0; r < 4; ++r) v[r] = __builtin_fmaf(a3, s[r], v[r]);
+  };
+  store_tile_bf16(smem, tl, acc16, p.bias, p.out, p.ldo, p.M, residual);
 #endif
 }
 
@@ -363,16 +168,14 @@ __global__ __launch_bounds__(256) void time_pool_down2_kernel(TimeDownParams p) 
   }
 }
 
-inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 }  // namespace
 
 int launch_conv_time_down2(const bf16_t* x, int64_t ldx, const VaeGrid& g, int64_t nsamples, const bf16_t* w, int64_t ldw, const bf16_t* bias,
                            bf16_t* out, int64_t ldo, int64_t C, float a3, hipStream_t stream) {
-  if (g.T < 1 || g.H < 2 || g.W < 2 || g.pad < 0 || g.tf < 0 || nsamples < 0 || nsamples > 65535) return VSYS_ERR_SHAPE;
+  SrcGrid s;
+  if (int e = refuse_grid(g, nsamples, s)) return e;
   if (C <= 0 || C > (1 << 20) || C % (w != nullptr ? BN : 8) != 0) return VSYS_ERR_SHAPE;
-  const int64_t Hp = g.H + 2 * g.pad, Wp = g.W + 2 * g.pad, plane = Hp * Wp;
-  if ((g.T + g.tf) * plane > g.sample_rows || g.sample_rows > 0x7fffffff) return VSYS_ERR_SHAPE;
+  const int64_t Wp = s.Wp, plane = s.plane;
   const int64_t To = (g.T - 1) / 2 + 1, HW = (int64_t)g.H * g.W, K = 27 * C;
   if (ldx < C || ldo < C || (w != nullptr && ldw < K)) return VSYS_ERR_SHAPE;
   // tile-relative operand offsets are 32-bit (buffer addressing): the widest source span of BM consecutive output voxels and their taps —
@@ -384,8 +187,7 @@ int launch_conv_time_down2(const bf16_t* x, int64_t ldx, const VaeGrid& g, int64
   const int64_t M = To * HW;
   const int64_t nbm = (M + BM - 1) / BM, nbn = C / BN, npool = (HW * (C / 8) + 255) / 256;
   if (M > 0x7fffffff || nbm * nbn > 0x7fffffff || npool > 0x7fffffff) return VSYS_ERR_SHAPE;
-  if ((ldx % 8) || (ldo % 8) || (w != nullptr && (ldw % 8))) return VSYS_ERR_ALIGN;
-  if (!aligned16(x) || !aligned16(w) || !aligned16(out) || (reinterpret_cast<uintptr_t>(bias) & 7)) return VSYS_ERR_ALIGN;
+  if (int e = refuse_align(x, ldx, w, w != nullptr ? ldw : 0, bias, out, ldo)) return e;
   if (!(a3 >= 0.f && a3 <= 1.0f / 3.0f)) return VSYS_ERR_ARG;
   if (nsamples == 0) return 0;
   TimeDownParams p;
@@ -393,7 +195,7 @@ int launch_conv_time_down2(const bf16_t* x, int64_t ldx, const VaeGrid& g, int64
   p.W = w; p.ldw = ldw; p.bias = bias; p.out = out; p.ldo = ldo;
   p.M = (int)M; p.C = (int)C; p.K = (int)K; p.nkc = (int)(C / BK);
   p.To = (int)To; p.H = g.H; p.Wd = g.W; p.Wp = (int)Wp; p.plane = (int)plane;
-  p.row00 = (int)((g.tf * Hp + g.pad) * Wp + g.pad);
+  p.row00 = (int)s.row00;
   p.a3 = a3;
   if (w == nullptr)
     hipLaunchKernelGGL(time_pool_down2_kernel, dim3((unsigned)npool, (unsigned)nsamples), dim3(256), 0, stream, p);

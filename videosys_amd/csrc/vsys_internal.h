@@ -133,7 +133,9 @@ struct VaeGrid {
   int T, H, W, pad, tf;
   int64_t sample_rows;
 };
-// stride-2 implicit-GEMM convolution of the VAE encoders (conv_down_bf16.hip), filled in by launch_conv_down2
+// stride-2 implicit-GEMM convolutions of the VAE encoders on the tile engine of conv_tile16.h: conv_down2_kernel (conv_down_bf16.hip,
+// filled in by launch_conv_down2) and conv_pool_down2_kernel (conv_pool_down_bf16.hip, launch_conv_pool_down2).  kt does double duty:
+// the number of time taps for the former, T & 1 (the first frame is a lone one) for the latter, which has no time taps.
 struct ConvDownParams {
   const bf16_t* X = nullptr; int64_t ldx = 0;   // source rows over the grid, [*, >= cin]
   int64_t sample_rows = 0, rows_total = 0;      // rows per sample / of the whole operand
@@ -141,7 +143,7 @@ struct ConvDownParams {
   const bf16_t* bias = nullptr;                 // [N] or null
   bf16_t* out = nullptr; int64_t ldo = 0;       // dense rows [samples * M, N]
   int M = 0, N = 0, K = 0;                      // M = To*Ho*Wo output voxels per sample
-  int cin = 0, nkc = 0, kt = 0;                 // nkc = cin / 32; kt = 1 (spatial) or 3 (spatio-temporal, causal)
+  int cin = 0, nkc = 0, kt = 0;                 // nkc = cin / 32; kt = 1 (spatial) or 3 (spatio-temporal, causal) | pool kernel: T & 1
   int H = 0, Wd = 0, Ho = 0, Wo = 0;
   int Wp = 0, plane = 0, row00 = 0;             // source row pitch, plane pitch, row of voxel (0, 0, 0) inside a sample
 };
