@@ -660,6 +660,19 @@ int vsys_conv_pool_down2_bf16(void* stream, const void* x, int64_t ldx, const in
  * 75 entries, and a recorded program issues the call from a host closure (program.host_call). */
 int vsys_conv_time_down2_bf16(void* stream, const void* x, int64_t ldx, const int64_t* grid_src, int64_t nsamples, const void* w_s, int64_t ldw,
                               const void* bias_s, void* out, int64_t ldo, int64_t C, float a3);
+/* Time-stride-2 causal convolution of the Open-Sora v1.2 VAE ENCODER (csrc/conv_causal_tdown_bf16.hip): the stride-(2, 1, 1)
+ * CausalConv3d of VAE_Temporal's Encoder (autoencoder_kl_open_sora.py:107-125,229-236) in one launch, in place of the stride-1
+ * vsys_conv_bf16 over a zero-bordered copy sampled by vsys_subsample.  x rows [*, ldx] over grid_src (any pad / tf; only voxels are
+ * read) -> out DENSE rows [nsamples * To * H * W, ldo], To = T / 2 rounded down (an odd T leaves its last frame unread).  Tap
+ * (a, kh, kw) of output (t', h, w) reads frame 2 t' + a - 1 at (h + kh - 1, w + kw - 1): ONE ZERO frame in front (frame -1, reached by
+ * output frame 0 alone) and zero outside 0..H-1 / 0..W-1 — not vsys_conv_time_down2_bf16's copies of the first frame.  w [cout, 27 cin],
+ * k = ((a 3 + kh) 3 + kw) cin + c; bias bf16 [cout] or NULL; fp32 accumulation, one rounding.  cout % 128 == 0, cin % 32 == 0, T >= 2,
+ * H, W >= 2, nsamples <= 65535, a tile of 256 output voxels must span less than 2 GiB of source rows (VSYS_ERR_SHAPE); strides % 8 == 0,
+ * x / w / out 16-byte aligned (VSYS_ERR_ALIGN); nsamples == 0 returns 0 without a launch.  The stream is the FIRST argument, as for
+ * vsys_conv_down2_bf16: no VSYS_OP code, the launch-program table keeps its 75 entries, and a recorded program issues the call from a
+ * host closure (program.host_call). */
+int vsys_conv_causal_tdown2_bf16(void* stream, const void* x, int64_t ldx, const int64_t* grid_src, int64_t nsamples, const void* w, int64_t ldw,
+                                 const void* bias, void* out, int64_t ldo, int64_t cin, int64_t cout);
 /* CogVideoXSpatialNorm3D + SiLU (autoencoder_kl_cogvideox.py:165-178,275-276): y = silu(GN(x) * Y + B); yb = [conv_y(zq) |
  * conv_b(zq)] computed at LATENT resolution, rows (n, zt, zh, zw) of 2C columns; the latent voxel of (t, h, w) follows
  * F.interpolate(zq, size=f.shape) including the first-frame split for odd frame counts.  stats from vsys_gn_stats. */

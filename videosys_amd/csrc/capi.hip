@@ -771,6 +771,14 @@ int vsys_conv_time_down2_bf16(void* stream, const void* x, int64_t ldx, const in
   return launch_conv_time_down2(B16(x), ldx, gs, nsamples, B16(w_s), ldw, B16(bias_s), B16(out), ldo, C, a3, S(stream));
 }
 
+int vsys_conv_causal_tdown2_bf16(void* stream, const void* x, int64_t ldx, const int64_t* grid_src, int64_t nsamples, const void* w, int64_t ldw,
+                                 const void* bias, void* out, int64_t ldo, int64_t cin, int64_t cout) {
+  VaeGrid gs;
+  if (!x || !w || !out || !to_grid(grid_src, gs)) return VSYS_ERR_ARG;
+  if (!fits_int(ldx, ldw, ldo, nsamples, cin, cout)) return VSYS_ERR_SHAPE;
+  return launch_conv_causal_tdown2(B16(x), ldx, gs, nsamples, B16(w), ldw, B16(bias), B16(out), ldo, cin, cout, S(stream));
+}
+
 int vsys_spatial_norm_apply(const void* x, const int64_t* grid_src, void* y, const int64_t* grid_dst, int64_t N, int64_t C,
                             int64_t groups, const void* stats_f32, const void* gamma, const void* beta, const void* yb, int64_t zT,
                             int64_t zH, int64_t zW, void* stream) {

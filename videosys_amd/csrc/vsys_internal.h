@@ -157,6 +157,10 @@ int launch_conv_pool_down2(const bf16_t* x, int64_t ldx, const VaeGrid& g, int64
 // three-frame pool as a fused residual, out = bf16(acc + bias + a3 (x0 + x1 + x2)); w == nullptr: the pool alone
 int launch_conv_time_down2(const bf16_t* x, int64_t ldx, const VaeGrid& g, int64_t nsamples, const bf16_t* w, int64_t ldw, const bf16_t* bias,
                            bf16_t* out, int64_t ldo, int64_t C, float a3, hipStream_t stream);
+// time-stride-2 CausalConv3d of the Open-Sora v1.2 temporal encoder (conv_causal_tdown_bf16.hip): 3 x 3 x 3 behind ONE ZERO frame, tap a of
+// output frame t' reads frame 2 t' + a - 1, To = T / 2.  Its kernel takes a ConvDownParams with kt = 3 and Ho x Wo = H x W.
+int launch_conv_causal_tdown2(const bf16_t* x, int64_t ldx, const VaeGrid& g, int64_t nsamples, const bf16_t* w, int64_t ldw, const bf16_t* bias,
+                              bf16_t* out, int64_t ldo, int64_t cin, int64_t cout, hipStream_t stream);
 int launch_gn_stats(const bf16_t* x, const VaeGrid& g, int N, int C, int groups, float eps, float* partial, int nblk, float* stats,
                     hipStream_t stream);
 int launch_gn_apply(const bf16_t* x, const VaeGrid& gs, bf16_t* y, const VaeGrid& gd, int N, int C, int groups, const float* stats,

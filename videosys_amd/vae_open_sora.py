@@ -16,11 +16,15 @@ single-head d = 512 mid-block attention is three batched GEMMs + a row softmax. 
 
 ``encode`` (reference :653-670, VAE_Temporal.encode :441-451, VideoAutoencoderKL.encode :503-520) is what the pipeline's
 conditioning needs (reference frames, ``loop`` > 1): the 2-D SDXL encoder per frame, then the temporal encoder per 17-frame
-micro batch, each followed by a draw from its diagonal Gaussian.  It runs on the same kernels; the three stride-2 convolutions of
-the 2-D encoder and the two stride-2-in-time causal convolutions of the temporal encoder are computed as the stride-1
-convolution sampled at the odd positions (vsys_subsample) — 4x / 2x the arithmetic of a strided kernel on those five layers of
-a path that runs once per conditioning clip, in exchange for no new convolution kernel.  Encoder weights are optional: a
-checkpoint without ``*.encoder.*`` keys gives a decode-only object.
+micro batch, each followed by a draw from its diagonal Gaussian.  It runs on the same kernels but for its five strided layers, which
+are launches of the stride-2 tile engine (csrc/conv_tile16.h) on the rows the block before them wrote — no padded copy, no sampled
+stride-1 convolution: the three diffusers Downsample2D layers of the 2-D encoder (F.pad (0, 1, 0, 1) + 3 x 3 stride 2) are
+vsys_conv_down2_bf16 in its kt = 1 mode, the two stride-(2, 1, 1) CausalConv3d layers of the temporal encoder (:107-125, :229-236: one
+zero frame in front) are vsys_conv_causal_tdown2_bf16 (csrc/conv_causal_tdown_bf16.hip).  The route these replaced — the stride-1
+convolution over a zero-bordered copy, sampled at the odd positions by vsys_subsample, 4x / 2x the arithmetic — stays in
+``_strided_conv_composed``: ``VSYS_VAE_ENCODE_STRIDED=0`` (read at every call) selects it, it is what
+tools/opensora_vae_encode_bench.py times the strided route against, and it serves a grid with H or W below 2, which the tile engine
+refuses.  Encoder weights are optional: a checkpoint without ``*.encoder.*`` keys gives a decode-only object.
 
 The weight holders, the staging cache, the residual block, the attention and the diffusers 2-D decoder body are the shared ones of
 vae_blocks.py (``VaeBlocks``); this module holds the temporal VAE, the encoders, the two ends of the 2-D decoder and the chunking.
@@ -29,10 +33,13 @@ There is no CPU path: without the HIP library / a GPU every call raises.
 """
 from __future__ import annotations
 
+import os
 from typing import Callable, Dict, Optional
 
 import torch
 
+from . import open_sora_plan_ops as osp_ops
+from . import open_sora_vae_ops as vae_ops
 from . import ops
 from .ops import VaeGrid
 from .vae_blocks import (AttnWeights, Decoder2DWeights, VaeBlocks, _Conv, _Norm, _Res, _conv_w, _vec, conv2, conv3,
@@ -281,8 +288,23 @@ class OpenSoraVAE(_SpatialDecoder):
     _IDENT = [1.0] * 4 + [0.0] * 4 + [1.0, 0, 0, 0, 0, 1.0, 0, 0, 0, 0, 1.0, 0, 0, 0, 0, 1.0] + [0.0] * 4   # first-layer params: x as is
 
     def _strided_conv(self, x, g: VaeGrid, cv: "_Conv", t_stride: int, s_stride: int):
-        """3x3(x3) convolution with stride (t_stride, s_stride, s_stride) in the encoders' padding conventions: the stride-1
-        convolution over the zero-bordered grid, sampled at the odd positions (module docstring)."""
+        """3x3(x3) convolution with stride (1, 2, 2) or (2, 1, 1) in the encoders' padding conventions (module docstring): one launch of
+        the stride-2 tile engine on the rows ``x`` as they lie, whatever border ``g`` has.  The composed route serves
+        VSYS_VAE_ENCODE_STRIDED=0, a grid narrower than 2 (refused by the tile engine) and CPU tensors — ``encode`` refuses those, so
+        they get here only under the torch restatements of the ``ops`` wrappers (tests/vae_cpu_emul.py), which cover that route alone."""
+        if os.environ.get("VSYS_VAE_ENCODE_STRIDED", "1") == "0" or min(g.H, g.W) < 2 or not x.is_cuda:
+            return self._strided_conv_composed(x, g, cv, t_stride, s_stride)
+        return self._strided_conv_tile(x, g, cv, t_stride, s_stride)
+
+    def _strided_conv_tile(self, x, g: VaeGrid, cv: "_Conv", t_stride: int, s_stride: int):
+        """One launch: vsys_conv_down2_bf16 (kt = 1) for stride (1, 2, 2), vsys_conv_causal_tdown2_bf16 for stride (2, 1, 1)."""
+        if (t_stride, s_stride) == (1, 2) and cv.kt == 1:
+            return osp_ops.conv_down2(x, g, cv.w, cv.b, cv.cin, 1), g.down2(1)
+        assert (t_stride, s_stride) == (2, 1) and cv.kt == 3, (t_stride, s_stride, cv.kt)
+        return vae_ops.conv_causal_tdown2(x, g, cv.w, cv.b, cv.cin), vae_ops.causal_tdown2_grid(g)
+
+    def _strided_conv_composed(self, x, g: VaeGrid, cv: "_Conv", t_stride: int, s_stride: int):
+        """The same convolution the long way: the stride-1 convolution over a zero-bordered copy, sampled at the odd positions."""
         tf = cv.kt - 1
         gp = VaeGrid(g.n, g.T, g.H, g.W, 1, tf)
         xp = self._padded_buf(gp, cv.cin)
